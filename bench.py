@@ -17,9 +17,16 @@ One step = the reference's timed region train.py:143-166: zero_grad -> forward -
 backward -> (N>1: one RCCL sum all-reduce per gradient bucket, overlapped with backward) -> clamp + Adam.  fp32
 throughout.  Rank 0 prints ONE JSON line; `value` is the whole-job aggregate over all N GPUs.
 
-The default single-GPU line also carries `"secondary": {"c2", "c5_beam5", "c5_greedy", "c5_rl"}`: BASELINE configs 2 (eager and
-replayed from a HIP graph) and 5 (beam = 5, greedy, the RL step at B = 128) timed in the same process after the headline and the
-bf16x3 leg, each with ms_per_step, value, step_frac and the roofline it is priced against (`--no-secondary` skips them).
+A plain run does only what the headline needs: set-up, the --settle seconds of untimed steps, the seeded start state put
+back, W warm-up steps, K timed steps, the line.  Because the counted W + K steps always start from the seeded weights, the same
+arguments compute the same outputs run after run: `--dump-outputs DIR` writes what the last timed step handed its caller as
+DIR/<name>.npy (fixed seeded samples of the large ones; see `train_outputs` / `beam_outputs`).
+
+`--full` adds everything else the line used to carry: the roofline of the dominant kernel (HIP events around its launches
+inside the timed steps and five stand-alone launches), the bf16x3 re-timing, the strong-scaling re-timing (N > 1), the CPU
+baseline, and on the default single-GPU run `"secondary": {"c2", "c5_beam5", "c5_greedy", "c5_rl"}`: BASELINE configs 2 (eager
+and replayed from a HIP graph) and 5 (beam = 5, greedy, the RL step at B = 128) timed in the same process after the headline and
+the bf16x3 leg, each with ms_per_step, value, step_frac and the roofline it is priced against (`--no-secondary` skips them).
 
 Other lines (same schema, not the headline): --workload c2 | c3het (the reference's shipped 5 heterogeneous encoders,
 feat_array.py:240-244) | c5 (BASELINE configs[4]: greedy / beam=5 decode and the self-critical RL step at B=128);
@@ -42,6 +49,10 @@ FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 de
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA peak (spec); --gemm bf16x3 is priced against it
 METRIC = 'captions/sec (train fwd+bwd) at B=256, M=4, L=196, D=2048, seq=16; 1/2/4/8 GPU'
 CPU_SAMPLE_B = 32               # captions in the CPU-baseline sample: fixed, so rounds and hosts are comparable
+DUMP_ROWS = 16                  # --dump-outputs: caption / image rows of the per-row outputs (a fixed seeded sample)
+DUMP_PER_PARAM = 1024           # --dump-outputs: values of every parameter and of its gradient (a fixed seeded sample)
+DUMP_SEED = 1234
+DUMP_MAX_BYTES = 64 << 20
 
 WORKLOADS = {
     # encoders: (att_num L, att_feat_size D, fc_feat_size F) per encoder; B = captions per GPU
@@ -209,6 +220,68 @@ def cpu_baseline(cfg, sample_B, seed, mode='train'):
                 sample='%s of the same model at B=%d, %.1f s' % (what, sample_B, dt))
 
 
+def _host(t):
+    """A device tensor as a numpy array: float32 for floating tensors, float64 for integer ones (token ids stay exact)."""
+    import numpy as np
+    a = t.detach().cpu().numpy()
+    return a.astype(np.float32 if a.dtype.kind == 'f' else np.float64)
+
+
+def _dump_rows(n):
+    """The fixed seeded sample of rows (of n) whose per-row outputs --dump-outputs writes, ascending."""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_ROWS), replace=False))
+
+
+def train_outputs(model, opt, kept):
+    """What the caller of the timed train step holds after its last step, as float32 arrays: `loss`; `log_prob`
+    (rows, steps, V+1) and `reason_pred` (M+1, rows, K) on the `_dump_rows` sample of caption rows (neither exists with
+    --fused-loss, nor under --graph, where the loss is the step's only output); `params` and `grads`: a fixed seeded sample of
+    up to DUMP_PER_PARAM values of every parameter after the update and of its gradient, parameters in name order."""
+    import numpy as np
+    import torch
+    opt.wait_params()               # a sharded / overlapped update may still be writing parameters on another stream
+    out = {'loss': _host(kept['loss'].reshape(1))}
+    lp, rp = kept.get('log_prob'), kept.get('reason_pred')
+    if lp is not None or rp is not None:
+        ref = lp if lp is not None else rp[0]
+        rows = torch.as_tensor(_dump_rows(ref.size(0)), device=ref.device)
+        if lp is not None:
+            out['log_prob'] = _host(lp.index_select(0, rows))
+        if rp is not None:
+            out['reason_pred'] = _host(torch.stack(list(rp)).index_select(1, rows))
+    rng = np.random.default_rng(DUMP_SEED + 1)
+    ps, gs = [], []
+    for _, p in sorted(model.named_parameters()):
+        n = p.numel()
+        pick = np.arange(n) if n <= DUMP_PER_PARAM else np.sort(rng.choice(n, size=DUMP_PER_PARAM, replace=False))
+        pick = torch.as_tensor(pick, device=p.device)
+        ps.append(p.detach().reshape(-1).index_select(0, pick))
+        gs.append(torch.zeros_like(ps[-1]) if p.grad is None else p.grad.detach().reshape(-1).index_select(0, pick))
+    out['params'], out['grads'] = _host(torch.cat(ps)), _host(torch.cat(gs))
+    return out
+
+
+def beam_outputs(res):
+    """What the caller of the timed beam search holds after its last call (`sample_beam`'s return), as arrays: `seq` (B, S)
+    token ids as float64, `seq_logprobs` (B, S), and `reason_pred` (B, M+1, K): the review heads every beam of an image shares."""
+    import torch
+    seq, seq_lp, _, _, reason = res
+    heads = torch.stack([torch.stack([t[0] for t in per_image]) for per_image in reason])
+    return {'seq': _host(seq), 'seq_logprobs': _host(seq_lp), 'reason_pred': _host(heads)}
+
+
+def write_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array; refuses more than DUMP_MAX_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes of outputs, more than the %d allowed' % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -273,7 +346,15 @@ def parse_args(argv=None):
                          'bucket (parallel.OverlappedUpdate) instead of one launch after backward; bit-identical parameters')
     ap.add_argument('--selftest-launch', action='store_true',
                     help='launcher / rendezvous check without a GPU: ranks meet, reduce a timing, rank 0 prints the line')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: roofline of the dominant kernel, the bf16x3 and strong-scaling '
+                         're-timings, the secondary BASELINE configs, the CPU baseline, the greedy / RL modes of --workload c5')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one handed its caller as DIR/<name>.npy (float32 / '
+                         'float64; fixed seeded samples of the large outputs, at most 64 MB in all)')
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.recipe:
         args.drop_lm, args.label_smoothing, args.ss_prob = 0.3, True, 0.25
     return args
@@ -358,7 +439,7 @@ def selftest_rank(args):
                    'rccl_ranks': torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
                    'config': {'workload': 'launcher self-test (no GPU work)', 'captions_per_gpu': B}}
             guard.line = out
-        if world > 1 and not args.strong:     # an optional leg, with the real run's discipline
+        if world > 1 and not args.strong and args.full:     # an optional leg, with the real run's discipline
             guard.begin_optional('strong', 60.0)
             try:
                 if fail and where == 'strong':
@@ -404,27 +485,35 @@ def run_decode(args, rank, world, dev):
     rl_crit = R.ReviewNetRewardCriterion(cfg)
     opt = R.FusedClampAdam(model, lr=5e-5, weight_decay=0.0, grad_clip=1.0)
 
+    kept = {} if args.dump_outputs else None
     t_beam, t_greedy, t_rl = decode_legs(model, opt, rl_crit, cfg, (fc, att, labels, masks, top), B, dev, world, args.steps,
-                                         args.warmup, beam=not unhoisted)
+                                         args.warmup, beam=not unhoisted,
+                                         legs=('beam5', 'greedy', 'rl') if args.full else ('beam5',), keep=kept)
     if rank != 0:
         return
-    fwd_flops = (train_step_flops(cfg, B) / 7.667 * 3.680)    # forward-only share (SURVEY 8d: 3.680 of 7.667 TF at C3)
+    if kept:
+        write_outputs(args.dump_outputs, beam_outputs(kept['beam5']))
     out = {'metric': 'images/sec (beam=5 sample_beam eval) at B=128, M=4, L=196, D=2048, seq=16',
            'value': round(world * B / t_beam, 2), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
            'warmup': args.warmup, 'ms_per_step': round(t_beam * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
            'config': {'workload': 'C5: beam=5 sample_beam (stages I/II once per image + 16 device-resident beam steps) '
                                   'at M=4, L=196, D=2048, B=%d per GPU; also greedy sample and the self-critical RL step' % B,
-                      'images_per_gpu': B, 'parallelism': 'replicas only'},
-           'modes': {'beam5_images_per_s': round(world * B / t_beam, 2), 'beam5_ms': round(t_beam * 1e3, 3),
-                     'greedy_images_per_s': round(world * B / t_greedy, 2), 'greedy_ms': round(t_greedy * 1e3, 3),
-                     'rl_step_images_per_s': round(world * B / t_rl, 2), 'rl_step_ms': round(t_rl * 1e3, 3)}}
-    secs, flops = time_dominant_kernel(model, att, reps=5)
-    achieved = flops / secs / 1e12
-    mult, peak = (6, BF16_MFMA_PEAK_TFLOPS) if args.gemm == 'bf16x3' else (1, FP32_MFMA_PEAK_TFLOPS)
+                      'images_per_gpu': B, 'parallelism': 'replicas only'}}
     if args.gemm == 'bf16x3':
         out['dtype'] = 'f32 (stage-I projections as 3 bf16 planes x 6 MFMA products, f32 accumulate; the rest exact f32)'
         out['config']['gemm'] = 'bf16x3'
+    if not args.full:
+        flush_c_stdio()
+        print(json.dumps(out), flush=True)
+        return
+    out['modes'] = {'beam5_images_per_s': round(world * B / t_beam, 2), 'beam5_ms': round(t_beam * 1e3, 3),
+                    'greedy_images_per_s': round(world * B / t_greedy, 2), 'greedy_ms': round(t_greedy * 1e3, 3),
+                    'rl_step_images_per_s': round(world * B / t_rl, 2), 'rl_step_ms': round(t_rl * 1e3, 3)}
+    fwd_flops = (train_step_flops(cfg, B) / 7.667 * 3.680)    # forward-only share (SURVEY 8d: 3.680 of 7.667 TF at C3)
+    secs, flops = time_dominant_kernel(model, att, reps=5)
+    achieved = flops / secs / 1e12
+    mult, peak = (6, BF16_MFMA_PEAK_TFLOPS) if args.gemm == 'bf16x3' else (1, FP32_MFMA_PEAK_TFLOPS)
     out['roofline'] = {'bound': 'mfma', 'achieved': round(mult * achieved, 2), 'peak': peak, 'unit': 'TFLOP/s',
                        'frac': round(mult * achieved / peak, 4), 'traffic': None,
                        'kernel': 'grouped att_2_att_h projection (%.3f TFLOP of f32 product, %.3f ms per launch)' % (flops / 1e12, secs * 1e3),
@@ -436,9 +525,11 @@ def run_decode(args, rank, world, dev):
     print(json.dumps(out), flush=True)
 
 
-def decode_legs(model, opt, rl_crit, cfg, inputs, B, dev, world, steps, warmup, beam=True):
+def decode_legs(model, opt, rl_crit, cfg, inputs, B, dev, world, steps, warmup, beam=True, legs=('beam5', 'greedy', 'rl'),
+                keep=None):
     """BASELINE configs[4] on `model`: seconds per call of beam = 5 sample_beam, greedy sample and the self-critical RL step
-    (train_rl.py:160-203: multinomial sample with grad, greedy baseline, reward criterion, backward, clamp + Adam)."""
+    (train_rl.py:160-203: multinomial sample with grad, greedy baseline, reward criterion, backward, clamp + Adam); NaN for a
+    leg not in `legs`.  `keep`: a dict that receives the return value of each timed leg's last call, under the leg's name."""
     import torch
     from recurrent_fusion_network_amd import parallel as DP
     fc, att, labels, masks, top = inputs
@@ -470,19 +561,24 @@ def decode_legs(model, opt, rl_crit, cfg, inputs, B, dev, world, steps, warmup, 
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn):
+    def timed(name, fn):
+        if name not in legs:
+            return float('nan')
         for _ in range(warmup):
             fn()
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            fn()
+        for k in range(steps):
+            if keep is not None and k == steps - 1:
+                keep[name] = fn()
+            else:
+                fn()
         fence()
         return DP.max_over_ranks(time.perf_counter() - t0, world, dev) / steps
 
     was_training = model.training
     try:
-        return (timed(beam5) if beam else float('nan')), timed(greedy), timed(rl_step)
+        return (timed('beam5', beam5) if beam else float('nan')), timed('greedy', greedy), timed('rl', rl_step)
     finally:
         model.train(was_training)
 
@@ -848,7 +944,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
     if args.strong:
         inputs = tuple(inputs) + (DP.shard_loss_scale(B, global_B, world),)
 
-    if args.graph and (in_group or (not x3 and not args.no_alt_line)):
+    if args.graph and (in_group or (args.full and not x3 and not args.no_alt_line)):
         raise SystemExit('--graph: single GPU, one GEMM mode per run (add --no-alt-line)')
     sync = DP.GradSync(model, world, shard_optimizer=opt if shard else None)     # per-bucket async exchange, overlapped with the rest of backward
     if args.graph:
@@ -857,7 +953,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
         if in_group or args.graph:
             raise SystemExit('--overlap-update: single GPU, eager steps')
         sync = DP.OverlappedUpdate(model, opt)
-    start = opt.snapshot() if (not x3 and not args.no_alt_line) else None     # the bf16x3 leg restarts from here
+    start = opt.snapshot()          # the headline's and the bf16x3 leg's counted steps start from here
 
     trace = [] if args.trace_steps else None
     fail_rank = os.environ.get('RFN_BENCH_FAIL_RANK') == str(rank)            # test hooks: a rank that dies mid-run
@@ -873,18 +969,23 @@ def run_train(args, rank, world, dev, R, DP, guard):
     graphed = {}
     in_step = {}                # per timed step and encoder: ms of the projection / weight-gradient launch (headline leg)
 
-    def step(inp, leg='headline'):
+    def step(inp, leg='headline', keep=None):
+        """One train step; `keep`: a dict that receives what the step hands its caller (loss, log_prob, reason_pred)."""
         if args.graph:                      # one captured graph per input set (its buffers are the graph's static inputs)
             if id(inp) not in graphed:
                 from recurrent_fusion_network_amd.graphed import GraphedTrainStep
                 graphed[id(inp)] = GraphedTrainStep(model, crit, opt, *inp[:5])
             counts[leg] = counts.get(leg, 0) + 1
-            return graphed[id(inp)]()
+            loss = graphed[id(inp)]()
+            if keep is not None:
+                keep['loss'] = loss
+            return loss
         fc, att, labels, masks, top = inp[:5]
         loss_scale = inp[5] if len(inp) > 5 else 1.0      # uneven shards weigh their local mean (parallel.shard_loss_scale)
         row = []
         mark(row)
         opt.zero_grad()
+        log_prob = None
         if args.fused_loss:
             loss, top_pred = model.forward_loss(fc, att, labels, masks, top, crit, 1.0)
         else:
@@ -900,6 +1001,8 @@ def run_train(args, rank, world, dev, R, DP, guard):
         mark(row)
         if trace is not None:
             trace.append((row, time.perf_counter()))
+        if keep is not None:
+            keep.update(loss=loss, log_prob=log_prob, reason_pred=top_pred)
         counts[leg] = counts.get(leg, 0) + 1
         if fail_rank and leg == fail_where and counts[leg] == 2:
             torch.cuda.synchronize()
@@ -948,18 +1051,22 @@ def run_train(args, rank, world, dev, R, DP, guard):
                     break
         return n
 
-    def time_leg(inp, leg, seconds=0.0, n_settle=None):
+    def time_leg(inp, leg, seconds=0.0, n_settle=None, restart=None, keep=None):
         """settle + W warm-up steps + EXACTLY K timed steps bracketed by barrier + synchronize.  Local times only: the
-        max over ranks is taken by the caller, outside any try block."""
+        max over ranks is taken by the caller, outside any try block.  `restart`: an opt.snapshot() put back after the
+        settle, so that the W + K counted steps do not depend on how many steps the settle seconds held.  `keep`: receives
+        what the last timed step hands its caller."""
         n = settle(inp, leg, seconds, n_settle)
+        if restart is not None:
+            opt.restore(restart)
         loss = None
         for _ in range(args.warmup):
             loss = step(inp, leg)
-        # the dominant launches INSIDE the timed steps: HIP events recorded by the path itself around every encoder's
-        # hoisted projection and weight-gradient launch (rfn_dims.probe_events), one event set per timed step, read
+        # the dominant launches INSIDE the timed steps (--full): HIP events recorded by the path itself around every
+        # encoder's hoisted projection and weight-gradient launch (rfn_dims.probe_events), one event set per timed step, read
         # after the region's own fence -- nothing is synchronised for them
         probes = None
-        if leg == 'headline' and not args.graph:
+        if leg == 'headline' and not args.graph and args.full:
             n_ev = 4 * len(w['enc'])
             probes = [[torch.cuda.Event(enable_timing=True) for _ in range(n_ev)] for _ in range(args.steps)]
             for evs in probes:
@@ -971,7 +1078,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
         for k in range(args.steps):
             if probes is not None:
                 model.set_probe_events(probes[k])
-            loss = step(inp, leg)
+            loss = step(inp, leg, keep if k == args.steps - 1 else None)
         fence()
         local = time.perf_counter() - t0
         model.set_probe_events(None)
@@ -996,7 +1103,12 @@ def run_train(args, rank, world, dev, R, DP, guard):
                 'exposed_measured_by': r['exposed_how']}
 
     # ---- the headline leg: nothing optional runs before this is measured and in rank 0's hands -------------------------
-    head = time_leg(inputs, 'headline', seconds=args.settle)
+    kept = {} if args.dump_outputs else None
+    head = time_leg(inputs, 'headline', seconds=args.settle, restart=start, keep=kept)
+    if kept is not None:
+        if rank == 0:
+            write_outputs(args.dump_outputs, train_outputs(model, opt, kept))
+        kept.clear()
     elapsed = DP.max_over_ranks(head['local'], world, dev)
     head_x = exposed_fields(head)
     dump_trace('exact' if not x3 else 'bf16x3', args.steps)
@@ -1043,7 +1155,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
                        'captions_per_gpu': B, 'global_batch': global_B,
                        'parallelism': 'dp%d (batch sharded, RCCL all-reduce of grads)' % world if world > 1 else 'single GPU',
                        'micro_batches': int(getattr(model, 'micro_batches', 1) or 1),
-                       'final_loss': round(final_loss, 4), 'updates': head['settle_n'] + args.warmup + args.steps,
+                       'final_loss': round(final_loss, 4), 'updates': args.warmup + args.steps,
                        'hip_graph': bool(args.graph), 'shard_optimizer': bool(shard), 'overlap_update': bool(args.overlap_update),
                        'fused_loss': bool(args.fused_loss),
                        'gemm_flags': int(model.gemm_flags), 'digest': digest},
@@ -1053,6 +1165,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
         if x3:
             out['dtype'] = 'f32 (the two long products as 3 bf16 planes x 6 MFMA products, f32 accumulate; the rest exact f32)'
             out['config']['gemm'] = 'bf16x3'
+    if rank == 0 and args.full:
         # roofline of the dominant kernel, timed live with HIP events on the launch stream
         att = inputs[1]
         secs_alone, flops = time_dominant_kernel(model, att, reps=5)
@@ -1107,6 +1220,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
         step_flops = (w['step_tflop'] * 1e12 * (B / w['B'])) if w['step_tflop'] else train_step_flops(cfg, B)
         out['roofline']['step_frac'] = round(step_flops / (ms * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4)
         out['roofline']['step_tflop'] = round(step_flops / 1e12, 4)
+    if rank == 0:
         guard.line = out                   # from here on the headline cannot be lost to an optional leg
 
     # ---- optional legs: re-timings reported beside the headline, never as `value` ---------------------------------------
@@ -1130,7 +1244,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
 
     # (1) the other reading of the metric: the SAME global batch one GPU runs (B captions), sharded over the ranks
     strong = None
-    if in_group and not args.strong:
+    if args.full and in_group and not args.strong:
         lo, hi = DP.shard_rows(B, rank, world)
         if DP.max_over_ranks(1.0 if hi - lo < 1 else 0.0, world, dev) > 0.0:
             strong = {'error': 'a global batch of %d rows cannot be sharded over %d ranks' % (B, world)}
@@ -1157,12 +1271,12 @@ def run_train(args, rank, world, dev, R, DP, guard):
     # starting weights and optimizer state and after the same number of updates as the headline leg, so that the two
     # `final_loss` values are comparable
     alt = None
-    if not x3 and not args.no_alt_line:
+    if args.full and not x3 and not args.no_alt_line:
         def x3_leg():
             opt.restore(start)
             model.gemm_flags |= N.GEMM_OPT_BF16X3
             try:
-                return time_leg(inputs, 'bf16x3', n_settle=head['settle_n'])
+                return time_leg(inputs, 'bf16x3', n_settle=head['settle_n'], restart=start)
             finally:
                 model.gemm_flags &= ~N.GEMM_OPT_BF16X3
         err, r = optional('bf16x3', x3_leg)
@@ -1173,7 +1287,7 @@ def run_train(args, rank, world, dev, R, DP, guard):
             dump_trace('bf16x3', args.steps)
             alt = {'value': round(global_B * args.steps / alt_elapsed, 2), 'unit': 'captions/s',
                    'ms_per_step': round(alt_elapsed / args.steps * 1e3, 3), 'final_loss': round(r['loss'], 4),
-                   'updates': r['settle_n'] + args.warmup + args.steps,
+                   'updates': args.warmup + args.steps,
                    'final_loss_note': 'same start, same number of updates as config.final_loss',
                    'device_mallocs_frees_in_timed_region': r['allocs'],
                    'dtype': 'f32 (the two long products as 3 bf16 planes x 6 MFMA products, f32 accumulate; the rest exact f32)'}
@@ -1195,14 +1309,14 @@ def run_train(args, rank, world, dev, R, DP, guard):
                     model.gemm_flags &= ~N.GEMM_OPT_BF16X3
         if rank == 0:
             out['bf16x3'] = alt
-    # (3) BASELINE configs 2 and 5 beside the headline (single GPU, the default run only)
-    if (world == 1 and args.workload == 'c3' and not args.batch and not args.no_alt_line and not args.no_secondary and not x3
-            and not args.graph and not args.persist):
+    # (3) BASELINE configs 2 and 5 beside the headline (single GPU, the default --full run only)
+    if (args.full and world == 1 and args.workload == 'c3' and not args.batch and not args.no_alt_line and not args.no_secondary
+            and not x3 and not args.graph and not args.persist):
         err, sec = optional('secondary', lambda: secondary_legs(args, dev, model, opt, start, R, N))
         out['secondary'] = {'error': err} if err else sec
     if rank != 0:
         return
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(cfg, args.cpu_sample, 100)
     guard.emit(out)
 

@@ -38,6 +38,50 @@ def test_two_ranks_self_launch_one_line_over_gloo():
     out = lines[0]
     assert out['n_gpus'] == 2 and out['rccl_ranks'] == 2 and out['selftest'] is True
     assert out['metric'].startswith('captions/sec') and out['scaling'] == 'weak' and out['value'] is None
+    assert 'strong' not in out          # optional legs run with --full only
+
+
+def test_full_and_dump_options_parse():
+    import bench
+    a = bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert a.full and a.dump_outputs == 'out'
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+
+
+def test_dumped_train_outputs_are_fixed_samples(tmp_path):
+    """train_outputs on a CPU stand-in for the model: the same rows and parameter positions on every call, float32 arrays,
+    every parameter and gradient represented; write_outputs refuses more than DUMP_MAX_BYTES."""
+    import numpy as np
+    import torch
+    import bench
+
+    class Opt:
+        def wait_params(self):
+            pass
+
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(40, 50), torch.nn.Linear(50, 3))
+    model(torch.randn(7, 40)).sum().backward()
+    B, S, V, K = 20, 5, 11, 6
+    kept = {'loss': torch.tensor(2.5), 'log_prob': torch.randn(B, S, V), 'reason_pred': [torch.randn(B, K) for _ in range(3)]}
+    a, b = bench.train_outputs(model, Opt(), kept), bench.train_outputs(model, Opt(), kept)
+    assert set(a) == {'loss', 'log_prob', 'reason_pred', 'params', 'grads'}
+    rows = bench._dump_rows(B)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a['log_prob'], kept['log_prob'].numpy()[rows])
+    assert np.array_equal(a['reason_pred'], torch.stack(kept['reason_pred']).numpy()[:, rows])
+    n = min(2000, bench.DUMP_PER_PARAM) + 50 + 150 + 3          # the 50 x 40 weight is sampled, the rest is whole
+    assert a['params'].shape == a['grads'].shape == (n,) and a['loss'].tolist() == [2.5]
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    bench.write_outputs(str(tmp_path / 'o'), a)
+    assert np.array_equal(np.load(str(tmp_path / 'o' / 'grads.npy')), a['grads'])
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / 'big'), {'x': np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / 'big').exists()
 
 
 def _failed_at(stderr):
@@ -63,7 +107,7 @@ def test_strong_flag_and_failing_rank_propagates():
 
 def test_eight_ranks_self_launch_over_gloo():
     """The N = 8 launch the driver will make, on CPU: 8 fresh ranks, one line, weak + strong legs."""
-    r = subprocess.run([sys.executable, BENCH, '--gpus', '8', '--steps', '1', '--selftest-launch'],
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '8', '--steps', '1', '--selftest-launch', '--full'],
                        env=_env(RFN_DIST_BACKEND='gloo', OMP_NUM_THREADS='1'), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -75,7 +119,7 @@ def test_eight_ranks_self_launch_over_gloo():
 def test_a_failing_optional_leg_cannot_lose_the_headline(where):
     """Once the headline is measured, a rank that raises (or hangs past the deadline) inside an optional leg ends the job
     through the flag file: rank 0 prints the line it holds with the leg's error, exit code 0."""
-    r = subprocess.run([sys.executable, BENCH, '--gpus', '4', '--steps', '1', '--selftest-launch'],
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '4', '--steps', '1', '--selftest-launch', '--full'],
                        env=_env(RFN_DIST_BACKEND='gloo', RFN_BENCH_FAIL_RANK='2', RFN_BENCH_FAIL_WHERE=where, OMP_NUM_THREADS='1'),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -89,7 +133,7 @@ def test_two_rank_train_step_line_on_one_gpu():
     """The real N=2 path end to end (model, GradSync buckets, fused Adam, max-over-ranks timing); the two ranks share
     cuda:0 and exchange the buckets over gloo because a one-GPU box cannot host two RCCL ranks."""
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--workload', 'c2', '--batch', '4', '--steps', '1',
-                        '--warmup', '1', '--no-cpu-baseline'],
+                        '--warmup', '1', '--no-cpu-baseline', '--full'],
                        env=_env(RFN_DIST_BACKEND='gloo', RFN_DEVICE_INDEX='0', HSA_ENABLE_IPC_MODE_LEGACY='0'),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -103,7 +147,7 @@ def test_two_rank_train_step_line_on_one_gpu():
 @pytest.mark.gpu
 def test_single_gpu_line_has_roofline_and_cpu_baseline():
     r = subprocess.run([sys.executable, BENCH, '--workload', 'c2', '--batch', '8', '--steps', '2', '--warmup', '1',
-                        '--cpu-sample', '2'], env=_env(), capture_output=True, text=True, timeout=900)
+                        '--cpu-sample', '2', '--full'], env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_lines(r.stdout)[0]
     assert out['n_gpus'] == 1 and out['rccl_ranks'] == 1
@@ -152,8 +196,8 @@ def test_one_rank_rccl_group_runs_the_sharded_updates_rccl_branches_bit_equal_an
     assert plain.returncode == 0, plain.stderr[-2000:]
     a = json.loads([l for l in plain.stdout.splitlines() if l.startswith('{"metric"')][-1])
     env_d = dict(env, RFN_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(29500 + os.getpid() % 1000))
-    dist = subprocess.run(base + ['--shard-optimizer'], env=env_d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                          timeout=900)
+    dist = subprocess.run(base + ['--shard-optimizer', '--full'], env=env_d, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          text=True, timeout=900)
     assert dist.returncode == 0, dist.stderr[-2000:]
     b = json.loads([l for l in dist.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert a['config']['shard_optimizer'] is False and a['dist_backend'] is None
@@ -180,7 +224,7 @@ def test_failing_rank_inside_the_train_step_exits_fast():
 @pytest.mark.gpu
 def test_failing_rank_inside_the_strong_leg_keeps_the_headline():
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--workload', 'c2', '--batch', '8', '--steps', '2',
-                        '--warmup', '1', '--settle', '0.5', '--no-cpu-baseline', '--no-alt-line'],
+                        '--warmup', '1', '--settle', '0.5', '--no-cpu-baseline', '--no-alt-line', '--full'],
                        env=_env(RFN_DIST_BACKEND='gloo', RFN_DEVICE_INDEX='0', HSA_ENABLE_IPC_MODE_LEGACY='0',
                                 RFN_BENCH_FAIL_RANK='1', RFN_BENCH_FAIL_WHERE='strong'),
                        capture_output=True, text=True, timeout=900)
@@ -194,7 +238,7 @@ def test_two_rank_line_carries_weak_and_strong_legs_with_exposed_wait():
     """one run answers both readings of the metric -- the weak headline (B captions per rank) and the
     SAME global batch sharded (`strong`) -- each with the time its step waited for the gradient exchange."""
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--workload', 'c2', '--batch', '8', '--steps', '2',
-                        '--warmup', '1', '--settle', '0.5', '--no-cpu-baseline'],
+                        '--warmup', '1', '--settle', '0.5', '--no-cpu-baseline', '--full'],
                        env=_env(RFN_DIST_BACKEND='gloo', RFN_DEVICE_INDEX='0', HSA_ENABLE_IPC_MODE_LEGACY='0'),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -212,8 +256,53 @@ def test_one_rank_rccl_line_carries_strong_and_exposed_ms():
     env = _env(RFN_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(29500 + os.getpid() % 1000),
                HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run([sys.executable, BENCH, '--workload', 'c2', '--batch', '16', '--steps', '3', '--warmup', '1',
-                        '--settle', '0.5', '--no-cpu-baseline', '--no-alt-line'], env=env, capture_output=True, text=True, timeout=900)
+                        '--settle', '0.5', '--no-cpu-baseline', '--no-alt-line', '--full'], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _json_lines(r.stdout)[0]
     assert out['dist_backend'] == 'nccl' and out['exposed_measured_by'].startswith('hip events')
     assert out['exposed_ms'] >= 0.0 and out['strong']['exposed_ms'] >= 0.0 and out['strong']['captions_per_gpu'] == 16
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_its_outputs_do_not_depend_on_the_settle(tmp_path):
+    """A plain run carries the headline alone; --dump-outputs writes what the last timed step handed its caller, and because
+    the counted steps restart from the seeded state after the settle, runs with different settle seconds write the same arrays
+    (without the restart, the extra Adam updates of the 0.5 s settle would move every parameter)."""
+    import numpy as np
+    outs = []
+    for settle in ('0', '0.5'):
+        d = tmp_path / ('settle_' + settle)
+        r = subprocess.run([sys.executable, BENCH, '--workload', 'c2', '--batch', '8', '--steps', '2', '--warmup', '1',
+                            '--settle', settle, '--dump-outputs', str(d)], env=_env(), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1
+        out = lines[0]
+        assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['value'] > 0 and out['config']['updates'] == 3
+        assert not set(out) & {'roofline', 'bf16x3', 'secondary', 'cpu_baseline', 'strong'}, sorted(out)
+        outs.append({f.name[:-4]: np.load(str(f)) for f in sorted(d.glob('*.npy'))})
+    a, b = outs
+    assert set(a) == set(b) == {'loss', 'log_prob', 'reason_pred', 'params', 'grads'}
+    assert a['log_prob'].shape == (8, 17, 9488) and a['reason_pred'].shape == (3, 8, 1000)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6 * max(1.0, float(np.abs(b[k]).max())), err_msg=k)
+
+
+@pytest.mark.gpu
+def test_c5_plain_line_dumps_the_beam_search_and_full_adds_the_modes(tmp_path):
+    base = [sys.executable, BENCH, '--workload', 'c5', '--batch', '4', '--steps', '1', '--warmup', '1', '--no-cpu-baseline']
+    r = subprocess.run(base + ['--dump-outputs', str(tmp_path)], env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_lines(r.stdout)[0]
+    assert out['value'] > 0 and out['ms_per_step'] > 0 and 'modes' not in out and 'roofline' not in out
+    import numpy as np
+    seq, lp, heads = (np.load(str(tmp_path / (n + '.npy'))) for n in ('seq', 'seq_logprobs', 'reason_pred'))
+    assert seq.dtype == np.float64 and seq.shape[0] == 4 and np.array_equal(seq, np.round(seq)) and seq.max() <= 9487
+    assert lp.dtype == np.float32 and lp.shape == seq.shape and np.all(lp <= 0)
+    assert heads.shape == (4, 5, 1000)
+    r = subprocess.run(base + ['--full'], env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_lines(r.stdout)[0]
+    assert out['modes']['greedy_ms'] > 0 and out['modes']['rl_step_ms'] > 0 and out['roofline']['frac'] > 0

@@ -12,7 +12,7 @@ cd $R
 : > $O/lines.jsonl
 run() {   # name, args...
   name=$1; shift
-  line=$(python bench.py --no-cpu-baseline --no-alt-line --settle 1 "$@" 2>$O/err.log | tail -1)
+  line=$(python bench.py --full --no-cpu-baseline --no-alt-line --settle 1 "$@" 2>$O/err.log | tail -1)
   echo "{\"tag\": \"$name\", \"line\": $line}" >> $O/lines.jsonl
   echo "$name $(echo "$line" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d.get("ms_per_step"), d.get("modes", ""))')"
 }

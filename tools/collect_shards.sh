@@ -18,6 +18,6 @@ done
 cd $R
 : > $O/lines.jsonl
 for args in "--batch 32" "--batch 64" "--batch 128" "--workload c2" ""; do
-  python bench.py --no-cpu-baseline $args 2>/dev/null | tail -1 >> $O/lines.jsonl
+  python bench.py --full --no-cpu-baseline $args 2>/dev/null | tail -1 >> $O/lines.jsonl
 done
 ls -la $O

@@ -1,5 +1,5 @@
 """What `roofline.frac` of the bench line should read, from the kernel trace of the same command: the projection launches
-INSIDE the timed steps are the last 4 x K launches before the 5 stand-alone launches `bench.py` makes after the timed region
+INSIDE the timed steps are the last 4 x K launches before the 5 stand-alone launches `bench.py --full` makes after the timed region
 (`time_dominant_kernel`); the launches before them belong to the settle seconds and the warm-up steps, where the clocks are
 still ramping (they run 3-5 % slower).   python tools/dominant_summary.py profiles/r05_dominant_launches.csv [--steps 10] [--encoders 4]"""
 import argparse
