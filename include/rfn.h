@@ -36,7 +36,7 @@ extern "C" {
 #define RFN_ERR_ARG (-5)         /* null / misaligned pointer */
 
 #define RFN_MAX_ENC 8
-#define RFN_ABI_VERSION 7
+#define RFN_ABI_VERSION 8
 
 /* Model dimensions: the fields RecurrentFusionModel.__init__ reads from `opt`
  * (misc/RecurrentFusionModel.py:118-151).  Limits (RFN_ERR_SHAPE otherwise): M <= RFN_MAX_ENC,
@@ -788,6 +788,36 @@ int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const float* const* p
                   float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
                   float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
                   void* stream);
+
+/* ---- self-critical reward: CIDEr-D of token-id captions (get_rewards.py:39-112, cider/pyciderevalcap/ciderD) ---------
+ * CiderD(n=4, sigma) as compute_reward calls it (csrc/rfn_reward.hip).  A caption is the ids of its row up to and including
+ * the first 0, or all of them when there is none (array_to_str); the end token 0 is a word.  Score row r is caption
+ * res[r, :T_res] of image row_img[r], scored against references gts[row_img[r], j, :T_gt] for j < n_refs[image].
+ * Document frequencies:
+ *   - corpus mode (table == NULL): df[g] = sum over images whose references contain g of the number of score rows pointing at
+ *     that image, ref_len = log(n_rows) -- compute_reward's crefs, one entry per score row;
+ *   - table mode: a table built by rfn_ciderd_table_build (the reference's df='coco-train-idxs' pickle), ref_len =
+ *     log(ref_docs) (113287 for coco-train, 123287 for coco-all, 5000 for coco-val).
+ * Arithmetic is fp64 in fixed orders: scores are bitwise reproducible run to run; the only atomics are integer df counts.
+ * A row whose caption, or one of whose image's references, holds an id outside [0, vocab] (or whose row_img / n_refs is out of
+ * range) scores NaN; other rows are unaffected (a bad reference's n-grams are left out of the corpus df).
+ * Limits (RFN_ERR_SHAPE otherwise): 1 <= T_res, T_gt <= 64, 1 <= max_refs <= 32, 0 <= vocab <= 32767.
+ * Four launches in corpus mode, three in table mode; no allocation, no synchronisation (capturable in a graph).
+ * res, gts: int64; row_img (n_rows), n_refs (n_img): int32; scores: n_rows doubles; ws: rfn_ciderd_ws_bytes, 16-B aligned.
+ * table: rfn_ciderd_table_bytes(slots) bytes (slots a power of two).  ngram_ids: n_entries x 4 int32, the n-gram's ids
+ * followed by -1 padding; counts: its df (doubles).  Keys must be unique; entries with an id above vocab are skipped.  At most
+ * slots / 2 entries. */
+size_t rfn_ciderd_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt, int corpus);
+size_t rfn_ciderd_table_bytes(int64_t slots);
+int rfn_ciderd_table_build(const int32_t* ngram_ids, const double* counts, int64_t n_entries, int vocab, void* table, int64_t slots,
+                           void* stream);
+int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                     const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots, double ref_docs,
+                     int vocab, double sigma, double* scores, void* ws, size_t ws_bytes, void* stream);
+/* train_rl.py's reward from the scores of B sampled rows followed by B greedy rows: reward[b, :] = weight * (s[b] - s[B + b])
+ * (use_baseline) or weight * s[b], broadcast over T; out (B, T) f32 and / or out64 (B, T) f64, either may be NULL. */
+int rfn_scst_reward(const double* scores, int B, int T, double weight, int use_baseline, float* out, double* out64,
+                    void* stream);
 
 #ifdef __cplusplus
 }

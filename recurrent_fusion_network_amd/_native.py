@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get('RFN_HIP_LIB') or os.path.join(_HERE, 'librfn_hip.so')
 RFN_MAX_ENC = 8
 RFN_GEMM_MAXSEG = 8
 RFN_GEMM_MAXGROUP = 8
-ABI_VERSION = 7
+ABI_VERSION = 8
 PATH_OPT_PERSIST_DEC_FWD, PATH_OPT_PERSIST_S2_FWD, PATH_OPT_PERSIST_DEC_BWD, PATH_OPT_PERSIST_S2_BWD = 1, 2, 4, 8   # rfn.h
 PATH_OPT_PERSIST_ALL = 15
 PATH_OPT_DEEP_CELLS = 16          # rfn.h RFN_PATH_OPT_DEEP_CELLS (A/B hook)
@@ -183,6 +183,11 @@ def _load():
         'rfn_dec_du': (C.c_int, [P, P, I, I, I, I, P, L, L, P]),
         'rfn_decoder_step': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, L, P, SZ, U64, I, P]),
         'rfn_decoder_step_embedded': (C.c_int, [DP, I, P, P, P, P, L, P, P, P, P, L, P, SZ, U64, I, P]),
+        'rfn_ciderd_ws_bytes': (SZ, [I, I, I, I, I, I]),
+        'rfn_ciderd_table_bytes': (SZ, [L]),
+        'rfn_ciderd_table_build': (C.c_int, [P, P, L, I, P, L, P]),
+        'rfn_ciderd_score': (C.c_int, [P, I, I, P, P, P, I, I, I, P, L, C.c_double, I, C.c_double, P, P, SZ, P]),
+        'rfn_scst_reward': (C.c_int, [P, I, I, C.c_double, I, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

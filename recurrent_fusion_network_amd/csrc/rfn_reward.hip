@@ -1,0 +1,452 @@
+// CIDEr-D of token-id captions and the self-critical reward (get_rewards.py:39-112 with
+// cider/pyciderevalcap/ciderD/ciderD_scorer.py, CiderD(n=4, sigma=6.0)) on the GPU.
+//
+// A caption is the ids of its row up to and including the first 0 (all T ids when there is none), as
+// array_to_str builds it.  An n-gram (n = 1..4) packs into one uint64: four 15-bit ids and n in bits 60-62,
+// so no valid key is 0 and equal keys are equal n-grams (no hash collision can change a result).  Document
+// frequencies live in an open-addressing, linear-probe table:
+//   - corpus mode: the workspace table is cleared and filled every call; one integer atomicAdd per unique
+//     n-gram of an image adds the number of score rows that point at that image (compute_reward's crefs);
+//   - table mode: rfn_ciderd_table_build inserts a precomputed df once and stores log(max(1, df)).
+// Launches of one call: [clear], refs (cook every reference caption, insert df), ref_vec (tf-idf values and
+// per-n norms of every reference), hyp (one workgroup per score row: its vector, the clipped similarity
+// against every reference of its image, the score).  Everything after the df counts is fp64 in fixed
+// summation orders, so scores are bitwise reproducible; the only atomics are the integer df counts.
+#include <math.h>
+
+#include <algorithm>
+
+#include "rfn_common.h"
+
+#define CD_N 4
+#define CD_MAX_T 64
+#define CD_MAX_REFS 32
+#define CD_MAX_ID 32767
+#define CD_THREADS 256   // >= CD_N * CD_MAX_T: one thread per n-gram slot (n, position)
+
+__device__ __forceinline__ uint64_t cd_hash(uint64_t k) {   // splitmix64 finaliser
+    k ^= k >> 30;
+    k *= 0xBF58476D1CE4E5B9ull;
+    k ^= k >> 27;
+    k *= 0x94D049BB133111EBull;
+    k ^= k >> 31;
+    return k;
+}
+
+// slot of `key` in a table of `slots` (a power of two) entries, -1 when absent
+__device__ __forceinline__ long cd_find(const uint64_t* keys, long slots, uint64_t key) {
+    long h = (long)(cd_hash(key) & (uint64_t)(slots - 1));
+    for (long probe = 0; probe < slots; ++probe) {
+        const uint64_t k = keys[h];
+        if (k == key) return h;
+        if (k == 0) return -1;
+        h = (h + 1) & (slots - 1);
+    }
+    return -1;
+}
+
+// slot that holds `key` after inserting it (-1 when the table is full)
+__device__ __forceinline__ long cd_insert(uint64_t* keys, long slots, uint64_t key) {
+    long h = (long)(cd_hash(key) & (uint64_t)(slots - 1));
+    for (long probe = 0; probe < slots; ++probe) {
+        const unsigned long long prev = atomicCAS((unsigned long long*)(keys + h), 0ull, (unsigned long long)key);
+        if (prev == 0ull || prev == (unsigned long long)key) return h;
+        h = (h + 1) & (slots - 1);
+    }
+    return -1;
+}
+
+// log(max(1, df)) of `key`: corpus mode counts integer df in cnt[], table mode stores the log itself
+struct CdDf {
+    const uint64_t* keys;
+    const uint32_t* cnt;      // corpus mode
+    const double* logdf;      // table mode
+    long slots;
+};
+__device__ __forceinline__ double cd_logdf(const CdDf& df, uint64_t key) {
+    const long h = cd_find(df.keys, df.slots, key);
+    if (df.logdf) return h < 0 ? 0.0 : df.logdf[h];
+    return log(fmax(1.0, h < 0 ? 0.0 : (double)df.cnt[h]));
+}
+
+// Cook one caption of T ids (block-wide; blockDim.x = CD_THREADS).  Thread t < 4T owns n-gram slot (n = t / T,
+// p = t % T); it returns the key when its slot holds the FIRST occurrence of an n-gram in the caption (0 otherwise) and
+// the n-gram's term count in *tf.  *words: the caption's word count; the return of *bad: an id outside [0, vocab].
+// skey: CD_THREADS keys of LDS; sw / sbad: LDS ints.  All threads must call it.
+__device__ uint64_t cd_cook(const int64_t* __restrict__ ids, int T, int vocab, uint64_t* skey, int* sw, int* sbad,
+                            int* tf, int* words, int* bad) {
+    const int t = threadIdx.x;
+    if (t == 0) {
+        *sw = T;
+        *sbad = 0;
+    }
+    __syncthreads();
+    int64_t id = -1;
+    if (t < T) {
+        id = ids[t];
+        if (id == 0) atomicMin(sw, t + 1);
+    }
+    __syncthreads();
+    const int W = *sw;
+    if (t < W && (id < 0 || id > vocab)) atomicOr(sbad, 1);
+    __syncthreads();
+    const int b = *sbad;
+    uint64_t key = 0;
+    int n = 0, p = 0;
+    if (t < CD_N * T) {
+        n = t / T;
+        p = t - n * T;
+        if (!b && p + n < W) {
+            key = (uint64_t)(n + 1) << 60;
+            for (int k = 0; k <= n; ++k) key |= (uint64_t)ids[p + k] << (15 * k);
+        }
+    }
+    skey[t] = key;
+    __syncthreads();
+    int cnt = 0;
+    if (key) {
+        bool first = true;
+        for (int q = n * T; q < n * T + T; ++q) {
+            if (skey[q] == key) {
+                ++cnt;
+                if (q < t) first = false;
+            }
+        }
+        if (!first) key = 0;
+    }
+    __syncthreads();   // the caller may overwrite skey next
+    *tf = cnt;
+    *words = W;
+    *bad = b;
+    return key;
+}
+
+// ---- corpus mode: clear the df table ----------------------------------------------------------------
+__global__ void cd_clear_k(uint64_t* __restrict__ keys, uint32_t* __restrict__ cnt, long slots) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (long)gridDim.x * blockDim.x) {
+        keys[i] = 0;
+        cnt[i] = 0;
+    }
+}
+
+// ---- references: one workgroup per image ----------------------------------------------------------------
+// Writes, per (image, ref) slot: rkey[4*Tg] (first occurrences), rval[4*Tg] (the term count, made tf-idf by ref_vec_k),
+// rlen; per image img_bad.  Corpus mode (dkeys != NULL) then adds the image's row count to the df of every n-gram its
+// references hold (once per image).  Dynamic LDS: max_refs * 4 * Tg keys.
+__global__ __launch_bounds__(CD_THREADS) void cd_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
+                                                        int max_refs, int Tg, const int32_t* __restrict__ row_img, int n_rows,
+                                                        int vocab, uint64_t* __restrict__ rkey, double* __restrict__ rval,
+                                                        int32_t* __restrict__ rlen, int32_t* __restrict__ img_bad,
+                                                        uint64_t* dkeys, uint32_t* dcnt, long dslots) {
+    extern __shared__ uint64_t all[];
+    __shared__ uint64_t skey[CD_THREADS];
+    __shared__ int sw, sbad, srows;
+    const int i = blockIdx.x, t = threadIdx.x, S = CD_N * Tg;
+    const int nr = n_refs[i];
+    int bad_img = (nr < 1 || nr > max_refs);
+    const int nrc = bad_img ? 0 : nr;
+    for (int j = 0; j < nrc; ++j) {
+        int tf, words, bad;
+        const uint64_t key = cd_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+        const long o = ((long)i * max_refs + j) * S;
+        if (t < S) {
+            rkey[o + t] = key;
+            rval[o + t] = (double)tf;
+            all[j * S + t] = key;
+        }
+        if (t == 0) rlen[(long)i * max_refs + j] = words > 1 ? words - 1 : 0;
+        bad_img |= bad;
+    }
+    if (t == 0) img_bad[i] = bad_img;
+    if (!dkeys || bad_img) return;   // bad_img is block-uniform
+    if (t == 0) srows = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int r = t; r < n_rows; r += CD_THREADS) mine += (row_img[r] == i);
+    if (mine) atomicAdd(&srows, mine);
+    __syncthreads();
+    const int rows = srows;
+    if (rows == 0) return;
+    for (int x = t; x < nrc * S; x += CD_THREADS) {
+        const uint64_t key = all[x];
+        if (!key) continue;
+        const int j = x / S, s = x - j * S, n = s / Tg;
+        bool seen = false;
+        for (int jj = 0; jj < j && !seen; ++jj)
+            for (int q = 0; q < Tg; ++q)
+                if (all[jj * S + n * Tg + q] == key) {
+                    seen = true;
+                    break;
+                }
+        if (seen) continue;
+        const long h = cd_insert(dkeys, dslots, key);
+        if (h >= 0) atomicAdd(dcnt + h, (uint32_t)rows);
+    }
+}
+
+// ---- reference vectors: one thread per (image, ref, n) -------------------------------------------------
+__global__ void cd_ref_vec_k(const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad, int n_img, int max_refs,
+                             int Tg, const uint64_t* __restrict__ rkey, double* __restrict__ rval, double* __restrict__ rnorm,
+                             CdDf df, double ref_docs) {
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long)n_img * max_refs * CD_N) return;
+    const int n = (int)(g % CD_N);
+    const long ij = g / CD_N;
+    const int i = (int)(ij / max_refs), j = (int)(ij % max_refs);
+    if (img_bad[i] || j >= n_refs[i]) return;
+    const double ref_len = log(ref_docs);
+    const long o = ij * CD_N * Tg + (long)n * Tg;
+    double nrm = 0.0;
+    for (int p = 0; p < Tg; ++p) {
+        const uint64_t key = rkey[o + p];
+        if (!key) continue;
+        const double v = rval[o + p] * (ref_len - cd_logdf(df, key));
+        rval[o + p] = v;
+        nrm += v * v;
+    }
+    rnorm[g] = sqrt(nrm);
+}
+
+// ---- hypotheses: one workgroup per score row -----------------------------------------------------------
+__global__ __launch_bounds__(CD_THREADS) void cd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
+                                                       int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
+                                                       int max_refs, int Tg, const uint64_t* __restrict__ rkey,
+                                                       const double* __restrict__ rval, const double* __restrict__ rnorm,
+                                                       const int32_t* __restrict__ rlen, int vocab, CdDf df, double ref_docs,
+                                                       double sigma, double* __restrict__ scores) {
+    __shared__ uint64_t skey[CD_THREADS], hk[CD_THREADS], rk[CD_THREADS];
+    __shared__ double hv[CD_THREADS], rv[CD_THREADS], contrib[CD_THREADS];
+    __shared__ double hnorm[CD_N], acc[CD_N];
+    __shared__ int sw, sbad;
+    const int r = blockIdx.x, t = threadIdx.x, S = CD_N * T, Sg = CD_N * Tg;
+    const int i = row_img[r];
+    if (i < 0 || i >= n_img || img_bad[i]) {   // block-uniform
+        if (t == 0) scores[r] = __builtin_nan("");
+        return;
+    }
+    const int nr = n_refs[i];
+    int tf, words, bad;
+    const uint64_t key = cd_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    if (bad) {
+        if (t == 0) scores[r] = __builtin_nan("");
+        return;
+    }
+    const double ref_len = log(ref_docs);
+    hk[t] = key;
+    hv[t] = key ? (double)tf * (ref_len - cd_logdf(df, key)) : 0.0;
+    __syncthreads();
+    double a = 0.0;
+    if (t < CD_N) {   // the reference's order: n-grams of one n in first-occurrence order
+        double s = 0.0;
+        for (int p = 0; p < T; ++p)
+            if (hk[t * T + p]) s += hv[t * T + p] * hv[t * T + p];
+        hnorm[t] = sqrt(s);
+    }
+    const int hlen = words > 1 ? words - 1 : 0;
+    const int n = t / (T > 0 ? T : 1);
+    for (int j = 0; j < nr; ++j) {
+        const long ij = (long)i * max_refs + j;
+        if (t < Sg) {
+            rk[t] = rkey[ij * Sg + t];
+            rv[t] = rval[ij * Sg + t];
+        }
+        __syncthreads();
+        if (key) {
+            double vr = 0.0;
+            for (int q = n * Tg; q < n * Tg + Tg; ++q)
+                if (rk[q] == key) {
+                    vr = rv[q];
+                    break;
+                }
+            const double vh = hv[t];
+            contrib[t] = (vr < vh ? vr : vh) * vr;
+        }
+        __syncthreads();
+        if (t < CD_N) {
+            double s = 0.0;
+            for (int p = 0; p < T; ++p)
+                if (hk[t * T + p]) s += contrib[t * T + p];
+            const double nh = hnorm[t], nrf = rnorm[ij * CD_N + t];
+            if (nh != 0.0 && nrf != 0.0) s /= nh * nrf;
+            const double delta = (double)(hlen - rlen[ij]);
+            s *= exp(-(delta * delta) / (2.0 * sigma * sigma));
+            a += s;
+        }
+        __syncthreads();
+    }
+    if (t < CD_N) acc[t] = a;
+    __syncthreads();
+    if (t == 0) {
+        double m = (((0.0 + acc[0]) + acc[1]) + acc[2]) + acc[3];
+        m /= (double)CD_N;
+        m /= (double)nr;
+        scores[r] = m * 10.0;
+    }
+    (void)S;
+}
+
+// ---- table mode: build ------------------------------------------------------------------------------------
+__global__ void cd_table_clear_k(uint64_t* __restrict__ keys, double* __restrict__ logdf, long slots) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (long)gridDim.x * blockDim.x) {
+        keys[i] = 0;
+        logdf[i] = 0.0;
+    }
+}
+__global__ void cd_table_insert_k(const int32_t* __restrict__ ids, const double* __restrict__ counts, long n_entries, int vocab,
+                                  uint64_t* __restrict__ keys, double* __restrict__ logdf, long slots) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_entries) return;
+    int len = 0;
+    while (len < CD_N && ids[e * CD_N + len] >= 0) ++len;
+    if (len == 0) return;
+    uint64_t key = (uint64_t)len << 60;
+    for (int k = 0; k < CD_N; ++k) {
+        const int id = ids[e * CD_N + k];
+        if (k < len) {
+            if (id > vocab) return;   // can never match a caption of this vocabulary
+            key |= (uint64_t)id << (15 * k);
+        } else if (id >= 0) {
+            return;                   // ids after the padding: not an n-gram
+        }
+    }
+    const long h = cd_insert(keys, slots, key);
+    if (h >= 0) logdf[h] = log(fmax(1.0, counts[e]));
+}
+
+__global__ void cd_scst_k(const double* __restrict__ scores, int B, int T, double weight, int use_baseline, float* __restrict__ out,
+                          double* __restrict__ out64) {
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long)B * T) return;
+    const int b = (int)(g / T);
+    const double c = use_baseline ? scores[b] - scores[B + b] : scores[b];
+    // compute_reward: bleu4 * 0 + cider * weight + spice * 0 (the zero terms turn a -0 into +0)
+    const double v = (0.0 + c * weight) + 0.0;
+    if (out) out[g] = (float)v;
+    if (out64) out64[g] = v;
+}
+
+// ---- host side --------------------------------------------------------------------------------------------
+namespace {
+const size_t kAlign = 256;
+size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+
+long corpus_slots(int n_img, int max_refs, int T_gt) {
+    const long distinct = (long)n_img * max_refs * CD_N * T_gt;   // an upper bound of the distinct reference n-grams
+    long s = 1024;
+    while (s < 2 * distinct) s <<= 1;
+    return s;
+}
+
+bool dims_ok(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
+    return n_rows >= 1 && n_img >= 1 && T_res >= 1 && T_res <= CD_MAX_T && T_gt >= 1 && T_gt <= CD_MAX_T && max_refs >= 1 &&
+           max_refs <= CD_MAX_REFS;
+}
+
+struct Layout {
+    size_t dkeys, dcnt, rkey, rval, rnorm, rlen, bad, total;
+    long dslots;
+};
+Layout layout(int n_rows, int T_res, int n_img, int max_refs, int T_gt, int corpus) {
+    (void)n_rows;
+    (void)T_res;
+    Layout L{};
+    const size_t nref = (size_t)n_img * max_refs;
+    size_t o = 0;
+    L.dslots = corpus ? corpus_slots(n_img, max_refs, T_gt) : 0;
+    L.dkeys = o; o = up(o + (size_t)L.dslots * 8);
+    L.dcnt = o;  o = up(o + (size_t)L.dslots * 4);
+    L.rkey = o;  o = up(o + nref * CD_N * T_gt * 8);
+    L.rval = o;  o = up(o + nref * CD_N * T_gt * 8);
+    L.rnorm = o; o = up(o + nref * CD_N * 8);
+    L.rlen = o;  o = up(o + nref * 4);
+    L.bad = o;   o = up(o + (size_t)n_img * 4);
+    L.total = o;
+    return L;
+}
+}  // namespace
+
+extern "C" size_t rfn_ciderd_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt, int corpus) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
+    return layout(n_rows, T_res, n_img, max_refs, T_gt, corpus).total;
+}
+
+extern "C" size_t rfn_ciderd_table_bytes(int64_t slots) {
+    if (slots < 2 || (slots & (slots - 1))) return 0;
+    return (size_t)slots * 16;
+}
+
+extern "C" int rfn_ciderd_table_build(const int32_t* ngram_ids, const double* counts, int64_t n_entries, int vocab, void* table,
+                                      int64_t slots, void* stream) {
+    if (n_entries < 0 || slots < 2 || (slots & (slots - 1)) || n_entries > slots / 2 || vocab < 0 || vocab > CD_MAX_ID)
+        return RFN_ERR_SHAPE;
+    if (!table || (n_entries > 0 && (!ngram_ids || !counts)) || !rfn_aligned16(table)) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    uint64_t* keys = (uint64_t*)table;
+    double* logdf = (double*)(keys + slots);
+    cd_table_clear_k<<<(int)std::min<long>(rfn_cdiv(slots, 256), 4096), 256, 0, st>>>(keys, logdf, slots);
+    RFN_CHECK_LAUNCH();
+    if (n_entries > 0) {
+        cd_table_insert_k<<<rfn_cdiv(n_entries, 256), 256, 0, st>>>(ngram_ids, counts, n_entries, vocab, keys, logdf, slots);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+
+extern "C" int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                                const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots,
+                                double ref_docs, int vocab, double sigma, double* scores, void* ws, size_t ws_bytes,
+                                void* stream) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > CD_MAX_ID) return RFN_ERR_SHAPE;
+    const int corpus = table == nullptr;
+    if (!corpus && (slots < 2 || (slots & (slots - 1)) || !(ref_docs > 0.0))) return RFN_ERR_SHAPE;
+    if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
+    const Layout L = layout(n_rows, T_res, n_img, max_refs, T_gt, corpus);
+    if (ws_bytes < L.total) return RFN_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    uint64_t* dkeys = corpus ? (uint64_t*)(w + L.dkeys) : nullptr;
+    uint32_t* dcnt = corpus ? (uint32_t*)(w + L.dcnt) : nullptr;
+    uint64_t* rkey = (uint64_t*)(w + L.rkey);
+    double* rval = (double*)(w + L.rval);
+    double* rnorm = (double*)(w + L.rnorm);
+    int32_t* rlen = (int32_t*)(w + L.rlen);
+    int32_t* bad = (int32_t*)(w + L.bad);
+    CdDf df;
+    if (corpus) {
+        df.keys = dkeys;
+        df.cnt = dcnt;
+        df.logdf = nullptr;
+        df.slots = L.dslots;
+        ref_docs = (double)n_rows;   // compute_reward: ref_len = log(len(crefs)), one entry per score row
+        cd_clear_k<<<(int)std::min<long>(rfn_cdiv(L.dslots, 256), 4096), 256, 0, st>>>(dkeys, dcnt, L.dslots);
+        RFN_CHECK_LAUNCH();
+    } else {
+        df.keys = (const uint64_t*)table;
+        df.cnt = nullptr;
+        df.logdf = (const double*)((const uint64_t*)table + slots);
+        df.slots = slots;
+    }
+    const size_t lds = (size_t)max_refs * CD_N * T_gt * 8;   // <= 64 KiB
+    if (lds > 48 * 1024)
+        hipFuncSetAttribute((const void*)cd_refs_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    cd_refs_k<<<n_img, CD_THREADS, lds, st>>>(gts, n_refs, max_refs, T_gt, row_img, n_rows, vocab, rkey, rval, rlen, bad, dkeys,
+                                              dcnt, L.dslots);
+    RFN_CHECK_LAUNCH();
+    const long nvec = (long)n_img * max_refs * CD_N;
+    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rval, rnorm, df, ref_docs);
+    RFN_CHECK_LAUNCH();
+    cd_hyp_k<<<n_rows, CD_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rval, rnorm, rlen, vocab,
+                                            df, ref_docs, sigma, scores);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+extern "C" int rfn_scst_reward(const double* scores, int B, int T, double weight, int use_baseline, float* out, double* out64,
+                               void* stream) {
+    if (B < 1 || T < 1) return RFN_ERR_SHAPE;
+    if (!scores || (!out && !out64)) return RFN_ERR_ARG;
+    const long n = (long)B * T;
+    cd_scst_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(scores, B, T, weight, use_baseline, out, out64);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}

@@ -1,0 +1,263 @@
+"""Self-critical reward on the GPU: CIDEr-D of token-id captions (csrc/rfn_reward.hip) and drop-ins for the reference's
+get_rewards.py (get_self_critical_reward_feat_array / get_self_critical_reward).
+
+CiderD reproduces cider/pyciderevalcap/ciderD's CiderD(n=4, sigma=6.0) as compute_reward calls it, on captions given as id
+rows (the ids up to and including the first 0, as array_to_str keeps them).  Document frequencies come from the scored
+rows themselves (df='corpus') or from a precomputed table (the reference's df='coco-train-idxs' pickle, or any dict of
+id-string tuples).  Corpus df is per call: under data parallelism each rank scores its own shard, as per-rank runs of the
+reference would.  BLEU-D and SPICE-D are not ported.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import pickle
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+MAX_T, MAX_REFS, MAX_ID = 64, 32, 32767
+_DOC_COUNTS = (('coco-all', 123287), ('coco-train', 113287), ('coco-val', 5000))   # ciderD_scorer.compute_cider
+
+
+def _ref_docs_of(mode):
+    for name, n in _DOC_COUNTS:
+        if name in mode:
+            return n
+    raise ValueError('df mode %r names none of coco-all / coco-train / coco-val: its document count is unknown' % mode)
+
+
+class CiderD:
+    """CIDEr-D scorer.  df: 'corpus', a dict {tuple of id strings: df}, a pickle path, or a reference mode name such as
+    'coco-train-idxs' (read from data/<name>.p like the reference).  df_mode names the document count of a table
+    (defaults to the name / file name of df)."""
+
+    def __init__(self, n=4, sigma=6.0, df='corpus', df_mode=None):
+        if n != 4:
+            raise NotImplementedError('only n = 4 (CiderD\'s default) is implemented')
+        self._n, self._sigma = n, float(sigma)
+        self._ws = None
+        self._tables = {}
+        self._table_src = None
+        if isinstance(df, str) and df == 'corpus':
+            self.df_mode, self.ref_docs = 'corpus', None
+            return
+        if isinstance(df, str):
+            path = df if os.path.exists(df) else os.path.join('data', df + '.p')
+            if df_mode is None:
+                df_mode = os.path.splitext(os.path.basename(path))[0]
+            with open(path, 'rb') as f:
+                df = pickle.load(f)
+        if not isinstance(df, dict):
+            raise TypeError('df must be \'corpus\', a dict or a pickle path')
+        if df_mode is None:
+            raise ValueError('a df dict needs df_mode (e.g. \'coco-train\') for its document count')
+        self.df_mode, self.ref_docs = df_mode, float(_ref_docs_of(df_mode))
+        ids, counts = [], []
+        for g, c in df.items():
+            try:
+                row = [_int_word(w) for w in g]
+            except ValueError:
+                continue          # not an id n-gram: can never match a caption of ids
+            if not 1 <= len(row) <= 4 or min(row) < 0 or max(row) > MAX_ID:
+                continue
+            ids.append(row + [-1] * (4 - len(row)))
+            counts.append(float(c))
+        self._table_src = (np.array(ids, dtype=np.int32).reshape(-1, 4), np.array(counts, dtype=np.float64))
+        self._slots = 1024
+        while self._slots < 2 * max(1, len(counts)):
+            self._slots *= 2
+
+    # -- device state --------------------------------------------------------------------------------------------
+    def _table(self, dev):
+        """The device df table (built once per device, with every n-gram of ids <= MAX_ID)."""
+        if self._table_src is None:
+            return None
+        key = str(dev)
+        if key not in self._tables:
+            ids, counts = self._table_src
+            table = torch.empty(N.lib.rfn_ciderd_table_bytes(self._slots), dtype=torch.uint8, device=dev)
+            ids_d = torch.from_numpy(ids).to(dev)
+            counts_d = torch.from_numpy(counts).to(dev)
+            N.check(N.lib.rfn_ciderd_table_build(N.ptr(ids_d) if len(counts) else None, N.ptr(counts_d) if len(counts) else None,
+                                                 len(counts), MAX_ID, table.data_ptr(), self._slots, N.stream_ptr()),
+                    'rfn_ciderd_table_build')
+            torch.cuda.current_stream(dev).synchronize()   # the host arrays' device copies are freed below
+            self._tables[key] = table
+        return self._tables[key]
+
+    def _workspace(self, dev, nbytes):
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self._ws
+
+    # -- scoring ---------------------------------------------------------------------------------------------------
+    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None):
+        """res (N, T) int64 ids, row_img (N,) image of each row, gts (n_img, R, Tg) int64 references padded to R,
+        n_refs (n_img,) references per image; all on one GPU.  -> (N,) float64 scores on the device (NaN for a row whose
+        caption or references hold an id outside [0, vocab])."""
+        dev = res.device
+        if dev.type != 'cuda':
+            raise N.RfnError('res must live on the GPU: the reward has no CPU fallback')
+        res = res.to(torch.int64).contiguous()
+        gts = gts.to(dev, torch.int64).contiguous()
+        row_img = row_img.to(dev, torch.int32).contiguous()
+        n_refs = n_refs.to(dev, torch.int32).contiguous()
+        n_rows, T = res.shape
+        n_img, R, Tg = gts.shape
+        if row_img.numel() != n_rows or n_refs.numel() != n_img:
+            raise ValueError('row_img needs one entry per row and n_refs one per image')
+        table = self._table(dev)
+        nbytes = N.lib.rfn_ciderd_ws_bytes(n_rows, T, n_img, R, Tg, int(table is None))
+        if nbytes == 0:
+            raise ValueError('CIDEr-D limits: 1 <= T <= %d, 1 <= refs per image <= %d' % (MAX_T, MAX_REFS))
+        ws = self._workspace(dev, nbytes)
+        if out is None:
+            out = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        N.check(N.lib.rfn_ciderd_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(),
+                                       n_img, R, Tg, None if table is None else table.data_ptr(),
+                                       0 if table is None else self._slots, C.c_double(self.ref_docs or 0.0), vocab,
+                                       C.c_double(self._sigma), out.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()),
+                'rfn_ciderd_score')
+        return out
+
+    def compute_score(self, gts, res):
+        """The reference's interface: gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}], captions
+        being space-separated id strings as array_to_str writes them.  -> (mean, np.ndarray of per-entry scores)."""
+        images, img_of = [], {}
+        rows = []
+        for entry in res:
+            hyp = entry['caption']
+            if not isinstance(hyp, list) or len(hyp) != 1:
+                raise ValueError('each res caption is a list of one string')
+            iid = entry['image_id']
+            if iid not in img_of:
+                refs = gts[iid]
+                if not isinstance(refs, list) or not refs:
+                    raise ValueError('gts[%r] must be a non-empty list of captions' % (iid,))
+                img_of[iid] = len(images)
+                images.append([_words(s) for s in refs])
+            rows.append((_words(hyp[0]), img_of[iid]))
+        T = max(len(w) for w, _ in rows)
+        Tg = max(len(w) for refs in images for w in refs)
+        res_a = np.array([_row(w, T) for w, _ in rows], dtype=np.int64)
+        R = max(len(refs) for refs in images)
+        gts_a = np.zeros((len(images), R, Tg), dtype=np.int64)
+        for i, refs in enumerate(images):
+            for j, w in enumerate(refs):
+                gts_a[i, j] = _row(w, Tg)
+        vocab = int(max(res_a.max(), gts_a.max(), 0))
+        dev = torch.device('cuda', torch.cuda.current_device())
+        s = self.score_ids(torch.from_numpy(res_a).to(dev), torch.tensor([i for _, i in rows], dtype=torch.int32),
+                           torch.from_numpy(gts_a), torch.tensor([len(r) for r in images], dtype=torch.int32),
+                           vocab=min(vocab, MAX_ID)).cpu().numpy()
+        return np.mean(s), s
+
+    def method(self):
+        return 'CIDEr-D'
+
+
+def _int_word(w):
+    x = int(w)
+    if str(x) != str(w):
+        raise ValueError('token %r is not an id in canonical form' % (w,))
+    return x
+
+
+def _words(s):
+    try:
+        return [_int_word(w) for w in s.split()]
+    except ValueError as e:
+        raise ValueError('CIDEr-D scores token-id captions: %s' % e) from None
+
+
+def _row(words, T):
+    """One id row whose array_to_str is `words`: a caption either ends at its only 0 or fills all T ids."""
+    if words and words[-1] == 0 and 0 not in words[:-1]:
+        return words + [0] * (T - len(words))
+    if 0 not in words and len(words) == T:
+        return words
+    raise ValueError('caption %r is not an id row of width %d as array_to_str writes it (words up to and including the '
+                     'first 0, or exactly T ids without one)' % (' '.join(map(str, words)), T))
+
+
+_ROW_CACHE = {}
+
+
+def _scst_row_img(B, seq_per_img, dev):
+    key = (B, seq_per_img, str(dev))
+    if key not in _ROW_CACHE:
+        _ROW_CACHE[key] = torch.tensor([(r % B) // seq_per_img for r in range(2 * B)], dtype=torch.int32, device=dev)
+    return _ROW_CACHE[key]
+
+
+def pad_gts(gts_list, dev):
+    """data['gts'] (a list of per-image (n_refs_i, T) id arrays) -> device (n_img, max_refs, T) int64, n_refs int32."""
+    arrs = [np.asarray(g.cpu() if torch.is_tensor(g) else g) for g in gts_list]
+    widths = {a.shape[1] for a in arrs}
+    if len(widths) != 1:
+        raise ValueError('every data[\'gts\'] array needs the same width (got %s)' % sorted(widths))
+    n_refs = np.array([a.shape[0] for a in arrs], dtype=np.int32)
+    out = np.zeros((len(arrs), int(n_refs.max()), widths.pop()), dtype=np.int64)
+    for i, a in enumerate(arrs):
+        out[i, :a.shape[0]] = a
+    return torch.from_numpy(out).to(dev), torch.from_numpy(n_refs).to(dev)
+
+
+def scst_reward(scorer, gen_result, greedy_res, gts, n_refs, seq_per_img, cider_weight=1.0, use_baseline=True, out64=None):
+    """compute_reward's CIDEr-D term on the device: scores the B sampled rows then the B greedy rows (row r points at image
+    (r % B) // seq_per_img), -> (B, T) float32 reward = cider_weight * (s[b] - s[B + b]) (or cider_weight * s[b]).  gts:
+    (n_img, R, Tg) padded references, n_refs (n_img,).  out64: optional (B, T) float64 tensor that receives the same reward
+    before the cast."""
+    B, T = gen_result.shape
+    if greedy_res.shape != gen_result.shape:
+        raise ValueError('gen_result and greedy_res must have the same shape')
+    dev = gen_result.device
+    res = torch.cat([gen_result.to(torch.int64), greedy_res.to(dev, torch.int64)], 0)
+    scores = scorer.score_ids(res, _scst_row_img(B, seq_per_img, dev), gts, n_refs)
+    out = torch.empty(B, T, dtype=torch.float32, device=dev)
+    N.check(N.lib.rfn_scst_reward(scores.data_ptr(), B, T, C.c_double(cider_weight), int(bool(use_baseline)), out.data_ptr(),
+                                  N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward')
+    return out
+
+
+_DEFAULT = {}
+
+
+def default_scorer():
+    """The reference's module-level scorer, CiderD(df='coco-train-idxs') (reads data/coco-train-idxs.p)."""
+    if 'scorer' not in _DEFAULT:
+        _DEFAULT['scorer'] = CiderD(df='coco-train-idxs')
+    return _DEFAULT['scorer']
+
+
+def _reward(model_sample, data, gen_result, opt, device, scorer):
+    if getattr(opt, 'bleu4_weight', 0) > 0 or getattr(opt, 'spice_weight', 0) > 0:
+        raise NotImplementedError('BLEU-D and SPICE-D rewards are not ported; set bleu4_weight = spice_weight = 0')
+    scorer = scorer or default_scorer()
+    with torch.no_grad():
+        greedy_res = model_sample()[0]
+    B, T = gen_result.shape
+    gts, n_refs = pad_gts(data['gts'], gen_result.device)
+    spi = B // len(data['gts'])
+    w, base = getattr(opt, 'cider_weight', 1.0), getattr(opt, 'use_baseline', 1)
+    if device:
+        return scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base)
+    out64 = torch.empty(B, T, dtype=torch.float64, device=gen_result.device)
+    scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base, out64=out64)
+    return out64.cpu().numpy()
+
+
+def get_self_critical_reward_feat_array(idx_to_word, model, fc_feat_array, att_feat_array, data, gen_result, opt, device=False,
+                                        scorer=None):
+    """get_rewards.py:115-129: greedy baseline from model.sample (in the module's current mode, without gradients), then
+    the CIDEr-D reward.  -> numpy (B, T) float64 like the reference, or the device (B, T) float32 tensor with device=True.
+    scorer: a CiderD (default: default_scorer(), the reference's df='coco-train-idxs')."""
+    return _reward(lambda: model.sample(list(fc_feat_array), list(att_feat_array)), data, gen_result, opt, device, scorer)
+
+
+def get_self_critical_reward(idx_to_word, model, fc_feats, att_feats, data, gen_result, opt, device=False, scorer=None):
+    """get_rewards.py:132-140 (single-feature models): as get_self_critical_reward_feat_array."""
+    return _reward(lambda: model.sample(fc_feats, att_feats), data, gen_result, opt, device, scorer)

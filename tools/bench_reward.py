@@ -1,0 +1,106 @@
+"""Time the on-device CIDEr-D reward (recurrent_fusion_network_amd/rewards.py) and print one JSON line.
+
+  - ms per scst_reward call (B sampled + B greedy rows, T = 16, 5 refs per image, random ids of the C5 vocabulary) at
+    B = 128 (1 row per image), 640 and 1280 (5 rows per image), in corpus mode and in table mode (a synthetic df table);
+  - the C5 self-critical step (bench.py's RL leg: multinomial sample, greedy baseline, reward criterion, backward, clamp +
+    Adam at B = 128) with the real reward against the same step with a randn reward, and the difference.
+Usage: python tools/bench_reward.py [--steps 50] [--warmup 5]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def scoring_case(B, spi, dev, seed, T=16, refs=5, vocab=9487):
+    rng = np.random.default_rng(seed)
+    n_img = B // spi
+    gts = torch.from_numpy(rng.integers(1, vocab + 1, (n_img, refs, T))).to(dev)
+    gts[:, :, -1] = 0
+    n_refs = torch.full((n_img,), refs, dtype=torch.int32, device=dev)
+    gen = torch.from_numpy(rng.integers(1, vocab + 1, (B, T))).to(dev)
+    greedy = torch.from_numpy(rng.integers(1, vocab + 1, (B, T))).to(dev)
+    return gen, greedy, gts, n_refs
+
+
+def synthetic_table(seed, vocab=9487, n=200000):
+    rng = np.random.default_rng(seed)
+    df = {}
+    for k in range(n):
+        L = 1 + k % 4
+        df[tuple(str(x) for x in rng.integers(1, vocab + 1, L))] = float(rng.integers(1, 500))
+    return df
+
+
+def time_calls(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--warmup', type=int, default=5)
+    args = ap.parse_args()
+    import bench
+    import recurrent_fusion_network_amd as R
+    from recurrent_fusion_network_amd import rewards as RW
+    dev = torch.device('cuda:0')
+    out = {'metric': 'CIDEr-D self-critical reward, ms per call (sample + greedy rows, T = 16, 5 refs)', 'unit': 'ms',
+           'steps': args.steps, 'warmup': args.warmup, 'device': torch.cuda.get_device_name(0)}
+    corpus, table = RW.CiderD(), RW.CiderD(df=synthetic_table(1), df_mode='coco-train')
+    for B, spi in ((128, 1), (640, 5), (1280, 5)):
+        gen, greedy, gts, n_refs = scoring_case(B, spi, dev, B)
+        for name, sc in (('corpus', corpus), ('table', table)):
+            out['%s_%dx2' % (name, B)] = round(time_calls(lambda: RW.scst_reward(sc, gen, greedy, gts, n_refs, spi),
+                                                          args.steps, args.warmup), 4)
+    # the C5 self-critical step, bench.py's RL leg, with the real reward and with randn
+    w = dict(bench.WORKLOADS['c5'])
+    B = w['B']
+    cfg = bench.make_cfg(w)
+    model = R.RecurrentFusionModel(cfg).to(dev)
+    bench.seeded_weights_(model, 100)
+    fc, att, labels, masks, top = bench.synthetic_inputs(cfg, B, 100, dev)
+    rl_crit = R.ReviewNetRewardCriterion(cfg)
+    opt = R.FusedClampAdam(model, lr=5e-5, weight_decay=0.0, grad_clip=1.0)
+    _, _, gts, n_refs = scoring_case(B, 1, dev, 7, T=cfg.seq_length)
+    steps = max(5, args.steps // 5)
+
+    def rl_step(real):
+        model.train()
+        opt.zero_grad()
+        seq, lp, lp_all, reason = model.sample(fc, att, {'sample_max': 0})
+        with torch.no_grad():
+            model.eval()
+            greedy = model.sample(fc, att, {'sample_max': 1})[0]
+            model.train()
+        if real:
+            reward = RW.scst_reward(corpus, seq, greedy, gts, n_refs, 1)
+        else:
+            reward = torch.randn(B, 1, device=dev).expand(B, seq.size(1)).contiguous()
+        rl_crit(lp, seq, reward, lp_all, 0.01, reason, top, 1.0, None, cfg).backward()
+        opt.step()
+    t_randn = time_calls(lambda: rl_step(False), steps, 2)
+    t_real = time_calls(lambda: rl_step(True), steps, 2)
+    t_randn2 = time_calls(lambda: rl_step(False), steps, 2)
+    t_randn = min(t_randn, t_randn2)
+    out.update({'c5_rl_step_randn_ms': round(t_randn, 3), 'c5_rl_step_ciderd_ms': round(t_real, 3),
+                'c5_rl_step_added_ms': round(t_real - t_randn, 3), 'c5_rl_steps': steps})
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == '__main__':
+    main()
