@@ -36,7 +36,7 @@ extern "C" {
 #define RFN_ERR_ARG (-5)         /* null / misaligned pointer */
 
 #define RFN_MAX_ENC 8
-#define RFN_ABI_VERSION 8
+#define RFN_ABI_VERSION 9
 
 /* Model dimensions: the fields RecurrentFusionModel.__init__ reads from `opt`
  * (misc/RecurrentFusionModel.py:118-151).  Limits (RFN_ERR_SHAPE otherwise): M <= RFN_MAX_ENC,
@@ -89,6 +89,14 @@ typedef struct rfn_dims {
                                            * whose rows share their image's thought vectors, has no unhoisted form          */
 #define RFN_PATH_OPT_DEEP_CELLS 16u       /* A/B hook: per-step products with no more tiles than CUs on the deep-ring kernel
                                            * (rfn_cell_gemm, RFN_CELL_VARIANT_DEEP) instead of the 3-slot one; not faster      */
+/* ABI 9.  The `uint64_t seed` argument of every entry point that takes a `const rfn_dims*` (rfn_prefix_fwd / _bwd,
+ * rfn_decoder_fwd / _fwd_step / _fwd_sampled / _bwd, rfn_decoder_step / _step_embedded, rfn_decoder_loop, rfn_beam_loop) is not
+ * the dropout key but the DEVICE ADDRESS of one uint64_t holding it (8-byte aligned; 0 -> RFN_ERR_ARG).  The kernels read the key
+ * when they run, so a captured graph replays with whatever the host stored there before the replay.  Only the key moves: the
+ * call-site offsets (rfn_dropout_mask) are as without the bit, and the same value gives the same bits either way.  The library
+ * never writes to that location; the caller keeps its value unchanged from the forward launches of a step until the backward
+ * (and recompute) launches of that step have run.  rfn_dropout_mask_dev publishes the masks of such a call. */
+#define RFN_PATH_OPT_SEED_DEV 256u
 
 int rfn_abi_version(void);
 const char* rfn_error_string(int code);
@@ -444,6 +452,9 @@ int rfn_cell_gemm(int M, int nout, const rfn_cell_out* outs_host, int R, float d
 #define RFN_DROP_OFFSET_STAGE2 (1ull << 20)
 #define RFN_DROP_OFFSET_DECODER (1ull << 21)
 int rfn_dropout_mask(uint64_t seed, uint64_t offset, int64_t n, float drop_p, float* keep_out, void* stream);
+/* The same mask for the key stored at `seed_dev` (device memory, read when the launch runs): what the kernels of a call with
+ * RFN_PATH_OPT_SEED_DEV and seed = (uint64_t)seed_dev apply.  Errors as rfn_dropout_mask; a NULL seed_dev is RFN_ERR_ARG. */
+int rfn_dropout_mask_dev(const uint64_t* seed_dev, uint64_t offset, int64_t n, float drop_p, float* keep_out, void* stream);
 
 /* LSTM gate epilogue shared by the three cells (misc/RecurrentFusionModel.py:55-73,
  * misc/LSTMSoftMultiAttentionFeatArrayNoInputCore.py:54-72, misc/LSTMSoftAttentionCore.py:83-101):

@@ -18,13 +18,14 @@ LIB_PATH = os.environ.get('RFN_HIP_LIB') or os.path.join(_HERE, 'librfn_hip.so')
 RFN_MAX_ENC = 8
 RFN_GEMM_MAXSEG = 8
 RFN_GEMM_MAXGROUP = 8
-ABI_VERSION = 8
+ABI_VERSION = 9
 PATH_OPT_PERSIST_DEC_FWD, PATH_OPT_PERSIST_S2_FWD, PATH_OPT_PERSIST_DEC_BWD, PATH_OPT_PERSIST_S2_BWD = 1, 2, 4, 8   # rfn.h
 PATH_OPT_PERSIST_ALL = 15
 PATH_OPT_DEEP_CELLS = 16          # rfn.h RFN_PATH_OPT_DEEP_CELLS (A/B hook)
 PATH_OPT_NO_SMALL_TILES = 32      # rfn.h RFN_PATH_OPT_NO_SMALL_TILES (A/B hook)
 PATH_OPT_SHARED_SMALL_TILES = 64  # rfn.h RFN_PATH_OPT_SHARED_SMALL_TILES (A/B hook)
 PATH_OPT_DEC_UNHOISTED = 128      # rfn.h RFN_PATH_OPT_DEC_UNHOISTED (A/B hook: the three-launch decoder cell of rounds 3-5)
+PATH_OPT_SEED_DEV = 256           # rfn.h RFN_PATH_OPT_SEED_DEV: the `seed` argument is the device address of the dropout key
 CELL_VARIANT_DEEP = 256
 GEMM_OPT_LDS_LEAN = 1
 GEMM_OPT_NO_DMA = 2
@@ -125,6 +126,7 @@ def _load():
         'rfn_attn_small_fwd': (C.c_int, [I, P, L, L, P, P, P, P, L, L, I, I, I, I, P, P, L, P]),
         'rfn_attn_small_bwd': (C.c_int, [I, P, L, L, P, P, P, P, L, L, P, L, I, I, I, I, P, L, L, I, P, P, P, P]),
         'rfn_dropout_mask': (C.c_int, [U64, U64, L, F, P, P]),
+        'rfn_dropout_mask_dev': (C.c_int, [P, U64, L, F, P, P]),
         'rfn_cell_gemm_supported': (C.c_int, [I, I, C.POINTER(CellOut), I]),
         'rfn_cell_gemm': (C.c_int, [I, I, C.POINTER(CellOut), I, F, U64, I, P]),
         'rfn_lstm_fwd': (C.c_int, [P, L, P, L, P, L, P, L, I, I, I, F, U64, U64, P]),

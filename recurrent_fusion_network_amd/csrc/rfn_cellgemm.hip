@@ -297,7 +297,7 @@ extern "C" int rfn_cell_gemm_supported(int M, int nout, const rfn_cell_out* outs
 
 // The launch arguments of one cell product without launching it: rfn_cell_gemm = prepare + launch; the persistent recurrence
 // kernels (rfn_chain.hip) take the prepared form of every step and run them inside one launch.
-int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_p, uint64_t seed, int variant, CgPrepared* pz) {
+int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_p, RfnSeed seed, int variant, CgPrepared* pz) {
     if (!rfn_cell_gemm_supported(M, nout, outs, R)) return RFN_ERR_UNSUPPORTED;
     if (drop_p < 0.f || drop_p >= 1.f) return RFN_ERR_SHAPE;
     CgArgs& a = pz->a;
@@ -306,7 +306,8 @@ int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_
     a.nout = nout;
     a.R = R;
     a.drop_p = drop_p;
-    a.seed = seed;
+    a.seed = seed.val;
+    a.seed_dev = seed.dev;
     int ns = 0;
     for (int o = 0; o < nout; ++o) {
         const rfn_cell_out& t = outs[o];
@@ -331,6 +332,6 @@ int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_
 extern "C" int rfn_cell_gemm(int M, int nout, const rfn_cell_out* outs, int R, float drop_p, uint64_t seed, int variant,
                              void* stream) {
     CgPrepared pz;
-    RFN_TRY(rfn_cg_prepare(M, nout, outs, R, drop_p, seed, variant, &pz));
+    RFN_TRY(rfn_cg_prepare(M, nout, outs, R, drop_p, rfn_seed_value(seed), variant, &pz));
     return rfn_cg_launch(pz, stream);
 }

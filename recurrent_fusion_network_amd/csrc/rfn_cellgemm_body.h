@@ -57,6 +57,7 @@ struct CgArgs {
     float drop_p;
     int slots;
     unsigned long long seed;
+    const uint64_t* seed_dev;   // non-NULL: the dropout key is read from here, not `seed` (RfnSeed, rfn_common.h)
     CgOut out[RFN_CELL_MAXOUT];
     CgSeg seg[CG_MAXSEG];
 };
@@ -780,6 +781,7 @@ __device__ __forceinline__ void cg_tile(const CgArgs& a, const int bid, float* s
         }
     } else if constexpr (EPI == CG_EPI_LSTM) {
         // LSTM gate epilogue (rfn_cell.hip lstm_fwd_k, same formulas): tile column g * U + u = gate g of unit tn * U + u
+        const uint64_t key = a.drop_p > 0.f ? rfn_key(a.seed_dev, a.seed) : 0;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int idx = tid + p * T;
@@ -805,7 +807,7 @@ __device__ __forceinline__ void cg_tile(const CgArgs& a, const int bid, float* s
             xb_st1<XB>(O.c_next + (long)grow * O.ldcn + unit, c);
             float hv = og * tanhf(c);
             if (a.drop_p > 0.f) {
-                const float uu = rfn_philox_uniform(a.seed, O.drop_offset, (uint64_t)((long)grow * R + unit));
+                const float uu = rfn_philox_uniform(key, O.drop_offset, (uint64_t)((long)grow * R + unit));
                 hv = (uu >= a.drop_p) ? hv * (1.0f / (1.0f - a.drop_p)) : 0.f;
             }
             xb_st1<XB>(O.h_next + (long)grow * O.ldh + unit, hv);
@@ -817,6 +819,7 @@ __device__ __forceinline__ void cg_tile(const CgArgs& a, const int bid, float* s
         // an fma depended on how the compiler shaped the branch around them, which differs between the launch form (uniform
         // kernel arguments) and the persistent form (descriptor in LDS) -- one rounding, but the two forms must agree bit for bit.
 #pragma clang fp contract(off)
+        const uint64_t key = a.drop_p > 0.f ? rfn_key(a.seed_dev, a.seed) : 0;
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const int idx = tid + e * T;
@@ -829,7 +832,7 @@ __device__ __forceinline__ void cg_tile(const CgArgs& a, const int bid, float* s
             float dhv = (s + b_in[e][0]) + b_in[e][1];
             if (O.C) xb_st1<XB>(O.C + (long)grow * O.ldc + unit, dhv);   // total d h of that call (kept for the caller's bookkeeping)
             if (a.drop_p > 0.f) {
-                const float uu = rfn_philox_uniform(a.seed, O.drop_offset, (uint64_t)((long)grow * R + unit));
+                const float uu = rfn_philox_uniform(key, O.drop_offset, (uint64_t)((long)grow * R + unit));
                 dhv = (uu >= a.drop_p) ? dhv * (1.0f / (1.0f - a.drop_p)) : 0.f;
             }
             const float ig = b_in[e][2], fg = b_in[e][3], og = b_in[e][4], gg = b_in[e][5];

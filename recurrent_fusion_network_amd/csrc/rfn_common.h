@@ -26,6 +26,35 @@ static inline int rfn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 static inline bool rfn_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+// The dropout key of one call as the launchers carry it: by value, or -- `dev` set, RFN_PATH_OPT_SEED_DEV (rfn.h) -- one
+// uint64_t in device memory that the kernels read when they run (a captured graph then replays with whatever key the host
+// stored there last).  Kernels resolve it with rfn_key() before their first draw; nothing in the library writes to `dev`.
+struct RfnSeed {
+    const uint64_t* dev;
+    uint64_t val;
+};
+static inline RfnSeed rfn_seed_value(uint64_t v) { return RfnSeed{nullptr, v}; }
+// Library-internal forms of the C entry points that take a dropout seed (not exported; the C forms call them with a value).
+int rfn_lstm_fwd_grouped(float* gates, int64_t ldg, const float* c_prev, int64_t ldcp, float* c_next, int64_t ldcn,
+                         float* h_next, int64_t ldh, int B, int R, int maxout, float drop_p, RfnSeed seed, uint64_t offset, int G,
+                         int64_t gs_gates, int64_t gs_cprev, int64_t gs_cnext, int64_t gs_h, void* stream);
+int rfn_lstm_fwd(float* gates, int64_t ldg, const float* c_prev, int64_t ldcp, float* c_next, int64_t ldcn, float* h_next,
+                 int64_t ldh, int B, int R, int maxout, float drop_p, RfnSeed seed, uint64_t offset, void* stream);
+int rfn_lstm_bwd_grouped(float* gates, int64_t ldg, const float* c_prev, int64_t ldcp, const float* c_next, int64_t ldcn,
+                         const float* dh, int64_t lddh, const float* dc_next, int64_t lddcn, float* dc_prev, int64_t lddcp, int B,
+                         int R, int maxout, float drop_p, RfnSeed seed, uint64_t offset, int G, int64_t gs_gates, int64_t gs_c,
+                         int64_t gs_dh, int64_t gs_dc, void* stream);
+int rfn_lstm_bwd(float* gates, int64_t ldg, const float* c_prev, int64_t ldcp, const float* c_next, int64_t ldcn,
+                 const float* dh, int64_t lddh, const float* dc_next, int64_t lddcn, float* dc_prev, int64_t lddcp, int B, int R,
+                 int maxout, float drop_p, RfnSeed seed, uint64_t offset, void* stream);
+// lstm->seed is the key unless seed_dev is given
+int rfn_gemm_f32_lstm(int M, int R, int ngroups, const rfn_gemm_problem* problems_host, void* ws, size_t ws_bytes, unsigned flags,
+                      const rfn_gemm_lstm* lstm, const uint64_t* seed_dev, void* stream);
+int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out, const float* b_out,
+                     const float* U, int64_t usb, int64_t usl, const float* bz, float* gates, int64_t ldg, const float* c_prev,
+                     int64_t ldcp, float* c_next, int64_t ldcn, float* h_next, int64_t ldh, float* alpha, int B, int L, int A, int R,
+                     int maxout, int row_div, float drop_p, RfnSeed seed, uint64_t drop_offset, void* stream);
+
 #ifdef __HIPCC__
 __device__ __forceinline__ float rfn_wave_sum(float v) {
 #pragma unroll
@@ -49,6 +78,9 @@ __device__ __forceinline__ float rfn_tanh_fast(float x) {
 // backward regenerate the same dropout mask from (seed, offset) instead of storing it.  THE one definition: the LSTM
 // kernels (rfn_cell.hip), the gate GEMM's reduce (rfn_gemm.hip) and the cell GEMM's epilogues (rfn_cellgemm.hip) must
 // draw identical bits for a forward mask and its backward twin to agree; rfn_dropout_mask (rfn.h) publishes them.
+// The key of a launch: the value, or what the host left in device memory (RfnSeed).  A uniform read-only load; a kernel calls
+// it once per thread, before its first draw.
+__device__ __forceinline__ uint64_t rfn_key(const uint64_t* seed_dev, uint64_t seed) { return seed_dev ? *seed_dev : seed; }
 __device__ __forceinline__ float rfn_philox_uniform(uint64_t seed, uint64_t offset, uint64_t idx) {
     uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);

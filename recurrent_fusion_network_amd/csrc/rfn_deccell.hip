@@ -41,6 +41,7 @@ struct DecCellArgs {
     int B, L, A, R, row_div;
     float drop_p;
     uint64_t seed, drop_offset;
+    const uint64_t* seed_dev;   // non-NULL: the dropout key is read from here, not `seed` (RfnSeed, rfn_common.h)
 };
 
 
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256) void dec_cell_fwd_k(const DecCellArgs a) {
     a.c_next[(long)b * a.ldcn + unit] = c;
     float hv = og * tanhf(c);
     if (a.drop_p > 0.f) {
-        const float u = rfn_philox_uniform(a.seed, a.drop_offset, (uint64_t)((long)b * R + unit));
+        const float u = rfn_philox_uniform(rfn_key(a.seed_dev, a.seed), a.drop_offset, (uint64_t)((long)b * R + unit));
         hv = (u >= a.drop_p) ? hv * (1.0f / (1.0f - a.drop_p)) : 0.f;
     }
     a.h_next[(long)b * a.ldh + unit] = hv;
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(256) void dec_cell_fwd_fast_k(const DecCellArgs a) 
     a.c_next[(long)b * a.ldcn + unit] = c;
     float hv = og * tanhf(c);
     if (a.drop_p > 0.f) {
-        const float u = rfn_philox_uniform(a.seed, a.drop_offset, (uint64_t)((long)b * R + unit));
+        const float u = rfn_philox_uniform(rfn_key(a.seed_dev, a.seed), a.drop_offset, (uint64_t)((long)b * R + unit));
         hv = (u >= a.drop_p) ? hv * (1.0f / (1.0f - a.drop_p)) : 0.f;
     }
     a.h_next[(long)b * a.ldh + unit] = hv;
@@ -281,18 +282,18 @@ static int dec_device_cus() {
     return c > 0 ? c : 256;
 }
 
-extern "C" int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
-                                const float* b_out, const float* U, int64_t usb, int64_t usl, const float* bz, float* gates,
-                                int64_t ldg, const float* c_prev, int64_t ldcp, float* c_next, int64_t ldcn, float* h_next,
-                                int64_t ldh, float* alpha, int B, int L, int A, int R, int maxout, int row_div, float drop_p,
-                                uint64_t seed, uint64_t drop_offset, void* stream) {
+int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out, const float* b_out,
+                     const float* U, int64_t usb, int64_t usl, const float* bz, float* gates, int64_t ldg, const float* c_prev,
+                     int64_t ldcp, float* c_next, int64_t ldcn, float* h_next, int64_t ldh, float* alpha, int B, int L, int A, int R,
+                     int maxout, int row_div, float drop_p, RfnSeed seed, uint64_t drop_offset, void* stream) {
     if (B <= 0 || L <= 0 || L > ATS_MAX_L || A <= 0 || R <= 0 || row_div < 1 || drop_p < 0.f || drop_p >= 1.f) return RFN_ERR_SHAPE;
     if (!proj || !hproj || !w_out || !U || !bz || !gates || !c_prev || !c_next || !h_next || !alpha) return RFN_ERR_ARG;
     DecCellArgs a;
     a.proj = proj; a.hproj = hproj; a.w_out = w_out; a.b_out = b_out; a.U = U; a.bz = bz; a.gates = gates;
     a.c_prev = c_prev; a.c_next = c_next; a.h_next = h_next; a.alpha = alpha;
     a.psb = psb; a.psl = psl; a.usb = usb; a.usl = usl; a.ldg = ldg; a.ldcp = ldcp; a.ldcn = ldcn; a.ldh = ldh;
-    a.B = B; a.L = L; a.A = A; a.R = R; a.row_div = row_div; a.drop_p = drop_p; a.seed = seed; a.drop_offset = drop_offset;
+    a.B = B; a.L = L; a.A = A; a.R = R; a.row_div = row_div; a.drop_p = drop_p; a.seed = seed.val; a.drop_offset = drop_offset;
+    a.seed_dev = seed.dev;
     // units per block: the widest block that still gives every CU one (a row's result does not depend on the choice)
     const int cus = dec_device_cus();
     const bool fast = A % 4 == 0 && A <= 512 && L <= DEC_LREG && R % 256 == 0 && (psb | psl) % 4 == 0 && rfn_aligned16(proj) &&
@@ -314,6 +315,14 @@ extern "C" int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, con
     else hipLaunchKernelGGL(dec_cell_fwd_k<4>, grid, dim3(ub), lds, (hipStream_t)stream, a);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
+}
+extern "C" int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
+                                const float* b_out, const float* U, int64_t usb, int64_t usl, const float* bz, float* gates,
+                                int64_t ldg, const float* c_prev, int64_t ldcp, float* c_next, int64_t ldcn, float* h_next,
+                                int64_t ldh, float* alpha, int B, int L, int A, int R, int maxout, int row_div, float drop_p,
+                                uint64_t seed, uint64_t drop_offset, void* stream) {
+    return rfn_dec_cell_fwd(proj, psb, psl, hproj, w_out, b_out, U, usb, usl, bz, gates, ldg, c_prev, ldcp, c_next, ldcn, h_next, ldh,
+                            alpha, B, L, A, R, maxout, row_div, drop_p, rfn_seed_value(seed), drop_offset, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -142,6 +142,7 @@ struct GemmArgs {
     int* tickets; // non-NULL: one zeroed counter per output tile; the last K range to arrive finishes the tile in-kernel
     int n_tickets;
     rfn_gemm_lstm lstm;   // lstm.c_next != NULL: C is a gate buffer (M, 4R) and the split-K reduce ends in the LSTM update
+    const uint64_t* seed_dev;   // non-NULL: the dropout key of that update is read from here, not lstm.seed (RfnSeed)
     rfn_gemm_problem g[RFN_GEMM_MAXGROUP];
 };
 
@@ -1080,7 +1081,7 @@ __global__ __launch_bounds__(256) void rfn_gemm_reduce_lstm_k(const GemmArgs arg
     L.c_next[grp * L.gs_cnext + (long)row * L.ldcn + j] = c;
     float hv = og * tanhf(c);
     if (L.drop_p > 0.f) {
-        const float u = rfn_philox_uniform(L.seed, L.offset + (uint64_t)grp, (uint64_t)idx);
+        const float u = rfn_philox_uniform(rfn_key(args.seed_dev, L.seed), L.offset + (uint64_t)grp, (uint64_t)idx);
         hv = (u >= L.drop_p) ? hv * (1.0f / (1.0f - L.drop_p)) : 0.f;
     }
     L.h_next[grp * L.gs_h + (long)row * L.ldh + j] = hv;
@@ -1343,26 +1344,30 @@ extern "C" int rfn_gemm_f32_opt(int M, int N, int ngroups, const rfn_gemm_proble
 
 static int gemm_entry(int M, int N, int ngroups, const rfn_gemm_problem* problems, int accumulate, void* ws,
                       size_t ws_bytes, unsigned flags, int32_t* tickets, int n_tickets, const rfn_gemm_lstm* lstm,
-                      void* stream);
+                      const uint64_t* seed_dev, void* stream);
 
 extern "C" int rfn_gemm_f32_tk(int M, int N, int ngroups, const rfn_gemm_problem* problems, int accumulate, void* ws,
                                size_t ws_bytes, unsigned flags, int32_t* tickets, int n_tickets, void* stream) {
-    return gemm_entry(M, N, ngroups, problems, accumulate, ws, ws_bytes, flags, tickets, n_tickets, nullptr, stream);
+    return gemm_entry(M, N, ngroups, problems, accumulate, ws, ws_bytes, flags, tickets, n_tickets, nullptr, nullptr, stream);
 }
 
 // Gate GEMM + LSTM update: gates[M, 4R] = sum_s A_s W_s^T + b (rfn_gemm_f32 semantics, no accumulate), then the update of
 // rfn_lstm_fwd_grouped on it.  When the product is cut along K the update rides on the fixed-order reduce (one launch
 // less, the gate pre-activations never travel to HBM and back); otherwise it is the separate element-wise launch.
-extern "C" int rfn_gemm_f32_lstm(int M, int R, int ngroups, const rfn_gemm_problem* problems, void* ws, size_t ws_bytes,
-                                 unsigned flags, const rfn_gemm_lstm* lstm, void* stream) {
+int rfn_gemm_f32_lstm(int M, int R, int ngroups, const rfn_gemm_problem* problems, void* ws, size_t ws_bytes, unsigned flags,
+                      const rfn_gemm_lstm* lstm, const uint64_t* seed_dev, void* stream) {
     if (!lstm || !lstm->c_prev || !lstm->c_next || !lstm->h_next || R < 1) return RFN_ERR_ARG;
     if (lstm->drop_p < 0.f || lstm->drop_p >= 1.f) return RFN_ERR_SHAPE;
-    return gemm_entry(M, 4 * R, ngroups, problems, 0, ws, ws_bytes, flags, nullptr, 0, lstm, stream);
+    return gemm_entry(M, 4 * R, ngroups, problems, 0, ws, ws_bytes, flags, nullptr, 0, lstm, seed_dev, stream);
+}
+extern "C" int rfn_gemm_f32_lstm(int M, int R, int ngroups, const rfn_gemm_problem* problems, void* ws, size_t ws_bytes,
+                                 unsigned flags, const rfn_gemm_lstm* lstm, void* stream) {
+    return rfn_gemm_f32_lstm(M, R, ngroups, problems, ws, ws_bytes, flags, lstm, nullptr, stream);
 }
 
 static int gemm_entry(int M, int N, int ngroups, const rfn_gemm_problem* problems, int accumulate, void* ws,
                       size_t ws_bytes, unsigned flags, int32_t* tickets, int n_tickets, const rfn_gemm_lstm* lstm,
-                      void* stream) {
+                      const uint64_t* seed_dev, void* stream) {
     if (M <= 0 || N <= 0) return RFN_OK;
     if (ngroups < 1 || ngroups > RFN_GEMM_MAXGROUP || !problems) return RFN_ERR_SHAPE;
     GemmArgs a;
@@ -1379,6 +1384,7 @@ static int gemm_entry(int M, int N, int ngroups, const rfn_gemm_problem* problem
     a.n_tickets = a.tickets ? n_tickets : 0;
     memset(&a.lstm, 0, sizeof(a.lstm));
     if (lstm) a.lstm = *lstm;
+    a.seed_dev = lstm ? seed_dev : nullptr;
     a.part = (ws && ws_bytes >= (1u << 20) && rfn_aligned16(ws)) ? (float*)ws : nullptr;
     a.ws_mib = (int)(ws_bytes >> 20);
     const int ak = problems[0].seg[0].a_kfast, bk = problems[0].seg[0].b_kfast;
@@ -1408,7 +1414,7 @@ static int gemm_entry(int M, int N, int ngroups, const rfn_gemm_problem* problem
     if (rc != RFN_OK || !lstm || a.splitk > 1) return rc;     // launch_tile records its split in a.splitk
     // unsplit product: the gate pre-activations are in C, the update is the element-wise launch
     return rfn_lstm_fwd_grouped(problems[0].C, problems[0].ldc, lstm->c_prev, lstm->ldcp, lstm->c_next, lstm->ldcn, lstm->h_next,
-                                lstm->ldh, M, N / 4, 0, lstm->drop_p, lstm->seed, lstm->offset, ngroups,
+                                lstm->ldh, M, N / 4, 0, lstm->drop_p, RfnSeed{seed_dev, lstm->seed}, lstm->offset, ngroups,
                                 ngroups > 1 ? (int64_t)(problems[1].C - problems[0].C) : 0, lstm->gs_cprev, lstm->gs_cnext,
                                 lstm->gs_h, stream);
 }

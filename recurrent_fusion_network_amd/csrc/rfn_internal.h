@@ -13,7 +13,7 @@ struct CgPrepared {      // rfn_cell_gemm's launch, not launched (rfn_cellgemm.h
     bool bkf;            // B operands are [n][k] (forward products)
     bool deep;           // RFN_CELL_VARIANT_DEEP: take the deep-ring kernel when the tiles do not outnumber the CUs
 };
-int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_p, uint64_t seed, int variant, CgPrepared* pz);
+int rfn_cg_prepare(int M, int nout, const rfn_cell_out* outs, int R, float drop_p, RfnSeed seed, int variant, CgPrepared* pz);
 int rfn_cg_launch(const CgPrepared& pz, void* stream);
 int rfn_cg_replan32(CgPrepared* pz);      // re-tile a prepared launch on the 32-row variant (same results)
 // The decoder's hoisted attention backward (rfn_deccell.hip): argument block without the launch, whether its rows take the fast

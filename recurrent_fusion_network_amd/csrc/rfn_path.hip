@@ -57,6 +57,18 @@ struct PIdx {
     int count() const { return r_w() + 2 + 12; }
 };
 
+// The `seed` argument of an entry point as the launches carry it: the key itself, or -- RFN_PATH_OPT_SEED_DEV -- the device
+// address of the key (rfn.h).  Every entry point resolves it once, before anything is launched.
+int path_seed(const rfn_dims* d, uint64_t seed_arg, RfnSeed* out) {
+    if (!d) return RFN_ERR_ARG;
+    *out = RfnSeed{nullptr, seed_arg};
+    if (d->path_flags & RFN_PATH_OPT_SEED_DEV) {
+        if (!seed_arg || (seed_arg & 7u)) return RFN_ERR_ARG;
+        *out = RfnSeed{reinterpret_cast<const uint64_t*>((uintptr_t)seed_arg), 0};
+    }
+    return RFN_OK;
+}
+
 int check_dims(const rfn_dims* d) {
     if (!d) return RFN_ERR_ARG;
     if (d->M < 1 || d->M > RFN_MAX_ENC || d->R < 1 || d->A < 1 || d->E < 1 || d->T1 < 1 || d->T2 < 1 || d->K < 1 ||
@@ -252,15 +264,17 @@ bool cell_ok(int B, int n, const rfn_cell_out* outs, int R) {
     return n <= RFN_CELL_MAXOUT && rfn_cell_gemm_supported(B, n, outs, R) != 0;
 }
 // variant: 0, or RFN_CELL_VARIANT_DEEP from cell_variant(d) (A/B hook: few-tile launches on the deep-ring kernel)
-int cell_run(int B, int n, const rfn_cell_out* outs, int R, float drop_p, uint64_t seed, void* st, int variant) {
-    return rfn_cell_gemm(B, n, outs, R, drop_p, seed, variant, st);
+int cell_run(int B, int n, const rfn_cell_out* outs, int R, float drop_p, RfnSeed seed, void* st, int variant) {
+    CgPrepared pz;
+    RFN_TRY(rfn_cg_prepare(B, n, outs, R, drop_p, seed, variant, &pz));   // rfn_cell_gemm with the key as the path carries it
+    return rfn_cg_launch(pz, st);
 }
 inline int cell_variant(const rfn_dims* d) {
     const int tiles = (d->path_flags & RFN_PATH_OPT_NO_SMALL_TILES) ? 9 : (d->path_flags & RFN_PATH_OPT_SHARED_SMALL_TILES) ? 7 : 0;
     return ((d->path_flags & RFN_PATH_OPT_DEEP_CELLS) ? RFN_CELL_VARIANT_DEEP : 0) | tiles;
 }
 // the same launch prepared instead of launched: one phase of a recurrence-chain step (rfn_chain.hip)
-int cell_prepare(int B, int n, const rfn_cell_out* outs, int R, float drop_p, uint64_t seed, CgPrepared* pz, int variant) {
+int cell_prepare(int B, int n, const rfn_cell_out* outs, int R, float drop_p, RfnSeed seed, CgPrepared* pz, int variant) {
     return rfn_cg_prepare(B, n, outs, R, drop_p, seed, variant, pz);
 }
 inline int chain_persist(const rfn_dims* d, uint32_t which) { return (d->path_flags & which) ? 1 : 0; }
@@ -656,7 +670,7 @@ extern "C" size_t rfn_prefix_ws_bytes(const rfn_dims* d, int B, int train) {
 static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
                            const float* const* init_h, const float* const* init_c, const float* const* att,
                            float* comb, float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
-                           int train, uint64_t seed, void* st) {
+                           int train, RfnSeed seed, void* st) {
     RFN_TRY(check_dims(d));
     if (B < 1) return RFN_ERR_SHAPE;
     if (!prm || (!fc && !(init_h && init_c)) || !att || !ws) return RFN_ERR_ARG;
@@ -690,7 +704,7 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
             cell_lin(k0[i], fc[i], d->F[i], prm[P.fc_w(i)], d->F[i], d->F[i], prm[P.fc_b(i)]);
         }
         if (cell_ok(B, M, k0, R)) {   // the M fc2h products in one launch
-            RFN_TRY(cell_run(B, M, k0, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, M, k0, R, 0.f, RfnSeed{}, st, cell_variant(d)));
         } else {
             for (int i = 0; i < M; ++i)
                 RFN_TRY(gemm1(B, R, seg_lin(fc[i], d->F[i], prm[P.fc_w(i)], d->F[i], d->F[i], prm[P.fc_b(i)]), Hs + i * R,
@@ -748,7 +762,7 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
                 cell_lin(k1[i], Hc + i * R, MR, prm[P.s1(t, i, 2)], R, R, prm[P.s1(t, i, 3)]);
             }
             if (cell_ok(B, M, k1, R)) {
-                RFN_TRY(cell_run(B, M, k1, R, 0.f, 0, st, cell_variant(d)));
+                RFN_TRY(cell_run(B, M, k1, R, 0.f, RfnSeed{}, st, cell_variant(d)));
             } else {
                 for (int i = 0; i < M; ++i)
                     pr[i] = prob1(hp + (long)i * B * A, A,
@@ -841,8 +855,8 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
         lu.c_prev = Cc; lu.c_next = Cn; lu.h_next = Hn;
         lu.ldcp = lu.ldcn = lu.ldh = MR;
         lu.gs_cprev = lu.gs_cnext = lu.gs_h = R;
-        lu.drop_p = d->drop_fusion; lu.seed = seed; lu.offset = (uint64_t)(t * M);
-        RFN_TRY(rfn_gemm_f32_lstm(B, R, M, pr, gx.ws, gx.ws_bytes, gx.flags, &lu, st));
+        lu.drop_p = d->drop_fusion; lu.seed = seed.val; lu.offset = (uint64_t)(t * M);
+        RFN_TRY(rfn_gemm_f32_lstm(B, R, M, pr, gx.ws, gx.ws_bytes, gx.flags, &lu, seed.dev, st));
     }
 
     // reason heads of stage I: max over steps of reason_linear_individual (:217, :229)
@@ -906,7 +920,7 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
             a_al[i] = al + (long)i * B * T1;
             a_z[i] = z + i * BR;
         }
-        return cell_prepare(B, M + 1, k1, R, 0.f, 0, &cs->g0, cell_variant(d)) == RFN_OK &&
+        return cell_prepare(B, M + 1, k1, R, 0.f, RfnSeed{}, &cs->g0, cell_variant(d)) == RFN_OK &&
                rfn_attn_small_prepare_fwd(M, a_p, (long)T2 * A, (long)B * T2 * A, a_hp, a_w, a_b, a_x, MR, BMR, B, T1, A, R, a_al, a_z,
                                           R, &cs->at) == RFN_OK &&
                cell_prepare(B, 1, &k3, R, d->drop_reason, seed, &cs->g2, cell_variant(d)) == RFN_OK;
@@ -944,7 +958,7 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
         cell_lstm(k3, cc, R, cn, R, hn, R, OFF_STAGE2 + (uint64_t)t);
         const bool fused = !d->review_maxout && cell_ok(B, M + 1, k1, R) && cell_ok(B, 1, &k3, R);
         if (fused) {
-            RFN_TRY(cell_run(B, M + 1, k1, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, M + 1, k1, R, 0.f, RfnSeed{}, st, cell_variant(d)));
         } else {
             for (int i = 0; i < M; ++i)
                 pr[i] = prob1(hp + (long)i * B * A, A, seg_lin(hc, R, prm[P.s2(t, i, 4)], R, R, prm[P.s2(t, i, 5)]));
@@ -985,8 +999,10 @@ extern "C" int rfn_prefix_fwd(const rfn_dims* d, int B, const float* const* prm,
                               const float* const* att, float* comb, float* h_out, float* c_out, float* reason_pred,
                               void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
     if (!fc) return RFN_ERR_ARG;
+    RfnSeed sd;
+    RFN_TRY(path_seed(d, seed, &sd));
     return prefix_fwd_impl(d, B, prm, fc, nullptr, nullptr, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, train,
-                           seed, st);
+                           sd, st);
 }
 // get_thought_vectors with a caller-provided state_list (inference only: no backward through the given state)
 extern "C" int rfn_prefix_fwd_from_state(const rfn_dims* d, int B, const float* const* prm, const float* const* init_h,
@@ -994,15 +1010,17 @@ extern "C" int rfn_prefix_fwd_from_state(const rfn_dims* d, int B, const float* 
                                          float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
                                          void* st) {
     if (!init_h || !init_c) return RFN_ERR_ARG;
-    return prefix_fwd_impl(d, B, prm, nullptr, init_h, init_c, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, 0, 0,
-                           st);
+    return prefix_fwd_impl(d, B, prm, nullptr, init_h, init_c, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, 0,
+                           RfnSeed{}, st);
 }
 
 extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
                               const float* const* att, const float* d_comb, const float* d_h, const float* d_c,
-                              const float* d_reason, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed,
+                              const float* d_reason, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg,
                               int defer_wgrad, void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1) return RFN_ERR_SHAPE;
     if (!prm || !fc || !att || !grd || !ws) return RFN_ERR_ARG;
     const PrefixLayout Lo = prefix_layout(d, B, 1);
@@ -1108,7 +1126,7 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
                 a_dw[i] = dwp + ((long)t * M + i) * BA;
                 a_dx[i] = dHs + BMR + i * R;
             }
-            ok = cell_prepare(B, M + 1, kb1, R, 0.f, 0, &cs.g0, cell_variant(d)) == RFN_OK &&
+            ok = cell_prepare(B, M + 1, kb1, R, 0.f, RfnSeed{}, &cs.g0, cell_variant(d)) == RFN_OK &&
                  rfn_attn_small_prepare_bwd(M, a_p, (long)T2 * A, (long)B * T2 * A, a_hp, a_w, a_al, a_x, MR, BMR, a_dz, R, B, T1, A, R,
                                             a_dp, (long)T2 * A, (long)B * T2 * A, 0, a_dhp, a_dw, a_dx, &cs.at) == RFN_OK &&
                  cell_prepare(B, 1, &kb2, R, d->drop_reason, seed, &cs.g2, cell_variant(d)) == RFN_OK;
@@ -1140,7 +1158,7 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
         } else {
             rfn_cell_out kb1[RFN_MAX_ENC + 1];
             s2_kb1(t, kb1);
-            RFN_TRY(cell_run(B, M + 1, kb1, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, M + 1, kb1, R, 0.f, RfnSeed{}, st, cell_variant(d)));
         }
         {   // whole attention backward of the M encoders in one fused launch (dP overwrites P in place)
             const float *a_p[RFN_MAX_ENC], *a_hp[RFN_MAX_ENC], *a_w[RFN_MAX_ENC], *a_al[RFN_MAX_ENC], *a_x[RFN_MAX_ENC],
@@ -1281,7 +1299,7 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
         if (s1_small) {
             rfn_cell_out kx[2 * RFN_MAX_ENC];
             s1x_of(t, kx);
-            RFN_TRY(cell_run(B, 2 * M, kx, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, 2 * M, kx, R, 0.f, RfnSeed{}, st, cell_variant(d)));
         } else {
         // dH_t += sum_i dgates_i . W_H[t,i]   (every cell reads the whole concatenated H, :53)
         for (int i = 0; i < M; ++i) segs[i] = seg_dx(g + (long)i * B * 4 * R, 4 * R, prm[P.s1(t, i, 6)], MR, 4 * R);
@@ -1306,7 +1324,7 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
                 cell_dx(kz[i], g + (long)i * B * 4 * R, 4 * R, prm[P.s1(t, i, 8)], d->D[i], 4 * R);
             }
             if (cell_ok(B, M, kz, R)) {
-                RFN_TRY(cell_run(B, M, kz, R, 0.f, 0, st, cell_variant(d)));
+                RFN_TRY(cell_run(B, M, kz, R, 0.f, RfnSeed{}, st, cell_variant(d)));
                 dz_done = true;
             }
         }
@@ -1399,7 +1417,7 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
                 kb[i] = cell_out(dHc + i * R, MR, R, 1);
                 cell_dx(kb[i], dhp + i * BA, A, prm[P.s1(t, i, 2)], R, A);
             }
-            if (cell_ok(B, M, kb, R)) RFN_TRY(cell_run(B, M, kb, R, 0.f, 0, st, cell_variant(d)));
+            if (cell_ok(B, M, kb, R)) RFN_TRY(cell_run(B, M, kb, R, 0.f, RfnSeed{}, st, cell_variant(d)));
             else RFN_TRY(gemm_groups(B, R, M, pr, 1, gx));
         }
     }
@@ -1550,7 +1568,7 @@ extern "C" size_t rfn_decoder_ws_bytes(const rfn_dims* d, int B, int S, int trai
 // attention; K3 = g += z2h(z) with the LSTM update as its epilogue.  false: the cell GEMM cannot take the step (maxout, widths).
 static bool decoder_cell_prepare(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                                  const float* h, const float* c, float* h_next, float* c_next, float* hp, float* al, float* z,
-                                 float* g, uint64_t seed, int step, ChainStep* cs) {
+                                 float* g, RfnSeed seed, int step, ChainStep* cs) {
     const PIdx P(d);
     const int R = d->R, A = d->A, T2 = d->T2;
     const int GD = gate_width(d->decoder_maxout, R);
@@ -1566,7 +1584,7 @@ static bool decoder_cell_prepare(const rfn_dims* d, int B, const float* const* p
     cell_lstm(k3, c, R, c_next, R, h_next, R, OFF_DECODER + (uint64_t)step);
     if (!cell_ok(B, 2, k1, R) || !cell_ok(B, 1, &k3, R)) return false;
     const float *w = prm[P.dec(10)], *bo = prm[P.dec(11)];
-    return cell_prepare(B, 2, k1, R, 0.f, 0, &cs->g0, cell_variant(d)) == RFN_OK &&
+    return cell_prepare(B, 2, k1, R, 0.f, RfnSeed{}, &cs->g0, cell_variant(d)) == RFN_OK &&
            rfn_attn_small_prepare_fwd(1, &cproj, A, BA, &hp, &w, &bo, &comb, R, BR, B, T2, A, R, &al, &z, R, &cs->at) == RFN_OK &&
            cell_prepare(B, 1, &k3, R, d->drop_lm, seed, &cs->g2, cell_variant(d)) == RFN_OK;
 }
@@ -1576,7 +1594,7 @@ static bool decoder_cell_prepare(const rfn_dims* d, int B, const float* const* p
 // b of one beam-search image share row b / row_div of cproj / U).  z is not computed.
 static int decoder_cell_core(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                              const float* U, int row_div, const float* h, const float* c, float* h_next, float* c_next,
-                             float* hp, float* al, float* z, float* g, const GemmCtx& gx, uint64_t seed, int step, void* st) {
+                             float* hp, float* al, float* z, float* g, const GemmCtx& gx, RfnSeed seed, int step, void* st) {
     const PIdx P(d);
     const int R = d->R, A = d->A, T2 = d->T2;
     const int GD = gate_width(d->decoder_maxout, R);
@@ -1589,7 +1607,7 @@ static int decoder_cell_core(const rfn_dims* d, int B, const float* const* prm, 
         k1[1] = cell_out(g, GD, GD, 1);
         cell_lin(k1[1], h, R, prm[P.dec(2)], R, R, prm[P.dec(3)]);
         if (cell_ok(B, 2, k1, R)) {
-            RFN_TRY(cell_run(B, 2, k1, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, 2, k1, R, 0.f, RfnSeed{}, st, cell_variant(d)));
         } else {
             RFN_TRY(gemm1(B, A, seg_lin(h, R, prm[P.dec(8)], R, R, prm[P.dec(9)]), hp, A, 0, gx));
             RFN_TRY(gemm1(B, GD, seg_lin(h, R, prm[P.dec(2)], R, R, prm[P.dec(3)]), g, GD, 1, gx));
@@ -1617,7 +1635,7 @@ static int decoder_cell_core(const rfn_dims* d, int B, const float* const* prm, 
 // The decoder cell of step s on the training workspace (gd[s] already holds i2h(x_s)): h_2_att_h, attention over the
 // fused thoughts, h2h + z2h accumulated onto the gates, LSTM epilogue with the dropout mask of (seed, s).
 static int decoder_fwd_cell(const rfn_dims* d, int B, int s, const float* const* prm, const float* comb, float* W,
-                            const DecoderLayout& Lo, const GemmCtx& gx, uint64_t seed, void* st) {
+                            const DecoderLayout& Lo, const GemmCtx& gx, RfnSeed seed, void* st) {
     const PIdx P(d);
     const int R = d->R, A = d->A, T2 = d->T2;
     const int GD = gate_width(d->decoder_maxout, R);
@@ -1634,7 +1652,7 @@ static int decoder_fwd_cell(const rfn_dims* d, int B, int s, const float* const*
 }
 
 static bool decoder_fwd_cell_prepare(const rfn_dims* d, int B, int s, const float* const* prm, const float* comb, float* W,
-                                     const DecoderLayout& Lo, uint64_t seed, ChainStep* cs) {
+                                     const DecoderLayout& Lo, RfnSeed seed, ChainStep* cs) {
     const int R = d->R, A = d->A, T2 = d->T2;
     const int GD = gate_width(d->decoder_maxout, R);
     const long BR = (long)B * R, BA = (long)B * A;
@@ -1666,8 +1684,10 @@ static int decoder_fwd_begin(const rfn_dims* d, int B, const float* const* prm, 
 
 extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
                                const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
-                               void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
+                               void* ws, size_t ws_bytes, int train, uint64_t seed_arg, void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
     if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
     const DecoderLayout Lo = decoder_layout(d, B, S, train);
@@ -1721,8 +1741,10 @@ extern "C" int rfn_decoder_fwd_begin(const rfn_dims* d, int B, int S, const floa
 
 extern "C" int rfn_decoder_fwd_step(const rfn_dims* d, int B, int S, int s, const float* const* prm, const float* comb,
                                     const int64_t* ids_s, int64_t ld_ids, float* log_prob, void* ws, size_t ws_bytes,
-                                    int train, uint64_t seed, void* st) {
+                                    int train, uint64_t seed_arg, void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1 || s < 0 || s >= S) return RFN_ERR_SHAPE;
     if (!prm || !comb || !ids_s || !log_prob || !ws) return RFN_ERR_ARG;
     const DecoderLayout Lo = decoder_layout(d, B, S, train);
@@ -1745,8 +1767,10 @@ extern "C" int rfn_decoder_fwd_step(const rfn_dims* d, int B, int S, int s, cons
 extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
                                const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids,
                                const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0,
-                               float* d_c0, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed, void* st) {
+                               float* d_c0, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg, void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
     if (!prm || !comb || !ids || (!log_prob != !d_log_prob) || !d_comb || !d_h0 || !d_c0 || !grd || !ws)
         return RFN_ERR_ARG;
@@ -1831,7 +1855,7 @@ extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* con
             kx_of(s, kx);
             CgPrepared px;
             DecAttnBwdArgs da;
-            RFN_TRY(cell_prepare(B, DEC_KSPLIT, kx, R, 0.f, 0, &px, cell_variant(d)));
+            RFN_TRY(cell_prepare(B, DEC_KSPLIT, kx, R, 0.f, RfnSeed{}, &px, cell_variant(d)));
             RFN_TRY(rfn_dec_attn_bwd_args(W + Lo.Pd, A, BA, W + Lo.hpd + s * BA, prm[P.dec(10)], W + Lo.ald + (long)s * B * T2, Ud, GD,
                                           (long)B * GD, g, GD, B, T2, A, GD, dPd, A, BA, 1, dhp, W + Lo.dwp + s * BA, &da));
             const int rc = rfn_cg_launch_with_rows(px, da, B, st);
@@ -1909,7 +1933,7 @@ extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* con
             const float *proj = W + Lo.Pd, *hp = W + Lo.hpd + s * BA, *w = prm[P.dec(10)], *al = W + Lo.ald + (long)s * B * T2;
             const float* dzc = dz;
             float *dpr = dPd, *dhp = W + Lo.dhpd + s * BA, *dwp = W + Lo.dwp + s * BA, *dxc = d_comb;
-            ok = cell_prepare(B, 2, kb1, R, 0.f, 0, &cs.g0, cell_variant(d)) == RFN_OK &&
+            ok = cell_prepare(B, 2, kb1, R, 0.f, RfnSeed{}, &cs.g0, cell_variant(d)) == RFN_OK &&
                  rfn_attn_small_prepare_bwd(1, &proj, A, BA, &hp, &w, &al, &comb, R, BR, &dzc, R, B, T2, A, R, &dpr, A, BA, 1, &dhp,
                                             &dwp, &dxc, &cs.at) == RFN_OK &&
                  cell_prepare(B, 1, &kb2, R, d->drop_lm, seed, &cs.g2, cell_variant(d)) == RFN_OK;
@@ -1927,7 +1951,7 @@ extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* con
         if (fused) {
             rfn_cell_out kb1[2], kb2;
             dec_kb1(s, kb1);
-            RFN_TRY(cell_run(B, 2, kb1, R, 0.f, 0, st, cell_variant(d)));
+            RFN_TRY(cell_run(B, 2, kb1, R, 0.f, RfnSeed{}, st, cell_variant(d)));
             RFN_TRY(attn1_bwd(W + Lo.Pd, A, BA, W + Lo.hpd + s * BA, prm[P.dec(10)], al, comb, R, BR, dz, R, B, T2, A, R,
                               dPd, A, BA, 1, dhp, W + Lo.dwp + s * BA, d_comb, st));
             dec_kb2(s, kb2);
@@ -2000,9 +2024,11 @@ extern "C" int rfn_decoder_prepare(const rfn_dims* d, int B, const float* const*
 // (misc/RecurrentFusionModel.py:260-270, 623-631: the reference samples from the dropout-affected outputs themselves).
 static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                              const int64_t* ids, const float* xt, int64_t ld_xt, float* h, float* c, float* logits,
-                             float* logp, int64_t ld_logp, void* ws, size_t ws_bytes, uint64_t seed, int step,
+                             float* logp, int64_t ld_logp, void* ws, size_t ws_bytes, uint64_t seed_arg, int step,
                              void* st, float* topv = nullptr, int32_t* topi = nullptr, int topw = 0, int row_div = 1) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || step < 0 || row_div < 1 || B % row_div) return RFN_ERR_SHAPE;
     if (!prm || !comb || !cproj || (!ids && !xt) || !h || !c || !ws) return RFN_ERR_ARG;
     if (xt && ld_xt < d->E) return RFN_ERR_SHAPE;
@@ -2067,6 +2093,8 @@ extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float
                                 int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
                                 void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed_checked;
+    RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
     if (B < 1 || steps < 1 || (mode != 0 && mode != 1)) return RFN_ERR_SHAPE;
     if (!prm || !comb || !cproj || !h || !c || !logp_all || !seq || !seq_lp || !unf || !ids || !ws) return RFN_ERR_ARG;
     if (mode == 1 && !u) return RFN_ERR_ARG;
@@ -2095,6 +2123,8 @@ extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const fl
                                        float inv_temperature, const float* u_draw, const float* u_coin, float* log_prob,
                                        void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
     RFN_TRY(check_dims(d));
+    RfnSeed seed_checked;
+    RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
     if (!prm || !comb || !h0 || !c0 || !ids || !u_draw || !u_coin || !log_prob || !ws) return RFN_ERR_ARG;
     RFN_TRY(rfn_decoder_fwd_begin(d, B, S, prm, comb, h0, c0, ws, ws_bytes, train, st));
@@ -2119,6 +2149,8 @@ extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const floa
     // `logp` holds, per beam row, its W best log-probs and their tokens (2 * W values): the search never looks at more
     // (:463-466), so the full (rows, V+1) log-prob matrix is neither written nor read back
     RFN_TRY(check_dims(d));
+    RfnSeed seed_checked;
+    RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
     if (NB < 1 || W < 1 || S < 1) return RFN_ERR_SHAPE;
     if (!prm || !comb || !cproj || !h || !c || !h_alt || !c_alt || !logp || !ids || !order || !ws) return RFN_ERR_ARG;
     const int rows = NB * W, V1 = d->V1, R = d->R;

@@ -208,7 +208,11 @@ class _DecoderFn(torch.autograd.Function):
         if ss_prob > 0.0 and S > 1:
             ids = ids.clone()
             # one call queues begin + S x (draw, step): the host is off the critical path (uniforms drawn up front)
-            r = torch.rand(2, S, B, device=dev)
+            r = getattr(model, '_ss_uniforms', None)      # a captured step reads the buffer its owner refills (graphed.py)
+            if r is None:
+                r = torch.rand(2, S, B, device=dev)
+            elif tuple(r.shape) != (2, S, B) or r.device != dev:
+                raise N.RfnError('scheduled-sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S, B)))
             N.check(N.lib.rfn_decoder_fwd_sampled(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
                                                   ids.data_ptr(), ids.stride(0), float(ss_prob), float(inv_temp),
                                                   r[0].data_ptr(), r[1].data_ptr(), log_prob.data_ptr(), ws.data_ptr(),
@@ -430,6 +434,11 @@ class RecurrentFusionModel(nn.Module):
         # set by graphed.GraphedTrainStep while it captures / warms up: run exactly this many decoder steps instead of
         # stopping at the first all-zero label column (the loader's masks are zero on the extra steps)
         self.fixed_decoder_steps = None
+        # set by graphed.GraphedTrainStep(device_rng=True) while its step runs: a one-element int64 device tensor holding the
+        # dropout seed (the kernels read it when they run: RFN_PATH_OPT_SEED_DEV, rfn.h) and the (2, S, B) scheduled-sampling
+        # uniforms; None = a fresh seed and fresh uniforms per forward, drawn here
+        self._seed_dev = None
+        self._ss_uniforms = None
         self.done_beams = []
 
     def init_weights(self):
@@ -460,7 +469,8 @@ class RecurrentFusionModel(nn.Module):
         return d
 
     def _dims_cached(self, train: bool) -> N.Dims:
-        key = (bool(train), int(self.gemm_flags), int(self.path_flags))
+        path_flags = int(self.path_flags) | (N.PATH_OPT_SEED_DEV if getattr(self, '_seed_dev', None) is not None else 0)
+        key = (bool(train), int(self.gemm_flags), path_flags)
         if key not in self._dims:
             self._dims[key] = N.make_dims(
                 self.num_feat_array, self.rnn_size, self.att_hid_size, self.input_encoding_size,
@@ -469,7 +479,7 @@ class RecurrentFusionModel(nn.Module):
                 review_maxout=self.review_maxout, decoder_maxout=self.decoder_maxout,
                 drop_fusion=self.drop_prob_fusion if train else 0.0,
                 drop_reason=self.drop_prob_reason if train else 0.0,
-                drop_lm=self.drop_prob_lm if train else 0.0, gemm_flags=self.gemm_flags, path_flags=self.path_flags)
+                drop_lm=self.drop_prob_lm if train else 0.0, gemm_flags=self.gemm_flags, path_flags=path_flags)
         return self._dims[key]
 
     def _params_of(self, slots):
@@ -603,11 +613,19 @@ class RecurrentFusionModel(nn.Module):
         return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids0, comb, h, c, 1.0, float(inv_temp),
                                 *params)
 
+    def _step_seed(self, train):
+        """The `seed` argument of this forward's native calls (and of its backward): a fresh draw in training mode, or the
+        address of the seed tensor a captured step's owner has installed (`_dims_for` then sets RFN_PATH_OPT_SEED_DEV)."""
+        held = getattr(self, '_seed_dev', None)
+        if held is not None:
+            return held.data_ptr()
+        return _fresh_seed() if train else 0
+
     # ---- reference API ----------------------------------------------------------------------------
     def forward(self, fc_feats, att_feats, seq):
         """misc/RecurrentFusionModel.py:198-281 -> (log_prob (B,T,V+1), reason_pred list[M+1] of (B,K))."""
         train = bool(self.training)
-        seed = _fresh_seed() if train else 0
+        seed = self._step_seed(train)
         S = self._decoder_steps(seq)          # may read `seq` back once: do it before queueing phase 1
         g = int(self.dedup_seq_per_img)
         if g > 1:
@@ -644,7 +662,7 @@ class RecurrentFusionModel(nn.Module):
             log_prob, reason = self.forward(fc_feats, att_feats, seq)
             return crit(log_prob, seq[:, 1:], masks[:, 1:], reason, top_words, reason_weight), reason
         train = bool(self.training)
-        seed = _fresh_seed() if train else 0
+        seed = self._step_seed(train)
         S = self._decoder_steps(seq)
         if seq.size(1) < S + 1 or masks.size(1) < S + 1:
             raise N.RfnError('labels / masks need %d columns for %d decoder steps' % (S + 1, S))
@@ -758,7 +776,7 @@ class RecurrentFusionModel(nn.Module):
         # dropout follows the module's mode, as the reference's nn.Dropout layers do (train_rl.py samples in train()
         # mode)
         train = bool(self.training)
-        seed = _fresh_seed() if train else 0
+        seed = self._step_seed(train)
         with torch.set_grad_enabled(want_grad):
             comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1

@@ -6,7 +6,16 @@ default and the large configuration is device-bound either way.
 What a capture freezes, and how each is dealt with:
   * kernel arguments.  The only step-dependent ones are Adam's two bias-correction scalars: the update is captured in its
     rfn_adam_step_multi_coef form, which reads them from a 2-float device tensor the wrapper fills before every replay.
-  * the dropout seed (a kernel argument of every cell kernel): training-mode dropout > 0 and scheduled sampling are refused.
+  * the dropout seed (by default a kernel argument of every cell kernel) and scheduled sampling's per-step uniforms: refused
+    by default.  With `device_rng=True` both live in device memory the wrapper owns and refills before every replay, drawn
+    exactly as the eager forward draws them -- one `_fresh_seed()` from torch's CPU generator, written with a stream-ordered
+    fill into a one-element int64 tensor the cell kernels read their Philox key from (RFN_PATH_OPT_SEED_DEV, rfn.h: forward,
+    backward and recompute legs get the tensor's address where they otherwise get the seed), and one
+    `torch.rand(2, S, B, device=...)` copied into a static buffer the captured rfn_decoder_fwd_sampled call reads.  So a
+    replay is the eager step of the same generator states, bit for bit, and torch.manual_seed / torch.cuda.manual_seed
+    reproduce a run.  Still refused with `device_rng=True`: a `grad_ready_hook` (parallel.GradSync); and the model itself
+    refuses `dedup_seq_per_img` with fusion / review dropout.  Warm-up and capture consume draws: both generators are put
+    back afterwards, so constructing the wrapper disturbs nobody's random stream.
   * shapes: the batch is static; a replayed batch whose tensors do not have the captured shapes is refused (`copy_` would
     silently broadcast a smaller one).
   * the number of decoder steps (the reference breaks at the first all-zero label column, :274, so it varies with the longest
@@ -27,12 +36,14 @@ at the first all-zero column) runs longer weight-gradient reductions than that e
 import torch
 
 from . import _native as N
+from . import fusion_model
 
 
 class GraphedTrainStep:
     def __init__(self, model, crit, opt, fc_feats, att_feats, labels, masks, top_words, reason_weight=1.0, warmup=3,
-                 full_length=True):
+                 full_length=True, device_rng=False):
         self.model, self.crit, self.opt, self.reason_weight = model, crit, opt, float(reason_weight)
+        self.device_rng = bool(device_rng)
         self._check_capturable()
         dev = fc_feats[0].device
         if labels.dim() != 2 or labels.size(1) < 2:
@@ -45,17 +56,25 @@ class GraphedTrainStep:
         self.att = [t.clone() for t in att_feats]
         self.labels, self.masks, self.top = labels.clone(), masks.clone(), top_words.clone()
         self.coef = torch.zeros(2, device=dev)
+        # device_rng: the step's dropout seed and its (2, S, B) scheduled-sampling uniforms (see the module docstring)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if self.device_rng else None
+        self.ss_uniforms = None
+        if self.device_rng and model.ss_prob > 0 and self.steps > 1:
+            self.ss_uniforms = torch.zeros(2, self.steps, labels.size(0), device=dev)
         # eager warm-up on a side stream (first-use attribute calls, allocator, the cached decoder-step count); the run must
         # not train: parameters, moments and step count are put back afterwards
         snap = opt.snapshot()
+        rng = (torch.get_rng_state(), torch.cuda.get_rng_state(dev)) if self.device_rng else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         prev_fixed = model.fixed_decoder_steps
         model.fixed_decoder_steps = self.steps
+        model._seed_dev, model._ss_uniforms = self.seed, self.ss_uniforms
         try:
             with torch.cuda.stream(side):
                 for _ in range(max(1, warmup)):
                     self._fill_coef()
+                    self._fill_rng()
                     self._body()
             torch.cuda.current_stream(dev).wait_stream(side)
             torch.cuda.synchronize(dev)
@@ -67,6 +86,10 @@ class GraphedTrainStep:
             opt.step_count = count             # the capture ran opt.step() on the host without executing anything
         finally:
             model.fixed_decoder_steps = prev_fixed
+            model._seed_dev = model._ss_uniforms = None
+        if rng is not None:                    # the draws of the warm-up are nobody's: both generators as found
+            torch.set_rng_state(rng[0])
+            torch.cuda.set_rng_state(rng[1], dev)
         self.frozen = self._frozen_state()
         self._checked_labels = None
 
@@ -74,10 +97,13 @@ class GraphedTrainStep:
         model = self.model
         if model.grad_ready_hook is not None:
             raise N.RfnError('GraphedTrainStep: a grad_ready_hook (parallel.GradSync) cannot be combined with a captured step')
+        if self.device_rng:
+            return
         if model.training and (model.drop_prob_lm > 0 or model.drop_prob_reason > 0 or model.drop_prob_fusion > 0):
-            raise N.RfnError('GraphedTrainStep: dropout > 0 draws a fresh seed per step, a captured graph would freeze it')
+            raise N.RfnError('GraphedTrainStep: dropout > 0 draws a fresh seed per step, a captured graph would freeze it '
+                             '(device_rng=True keeps the seed in device memory)')
         if model.ss_prob > 0:
-            raise N.RfnError('GraphedTrainStep: scheduled sampling draws per step; not capturable')
+            raise N.RfnError('GraphedTrainStep: scheduled sampling draws per step; not capturable without device_rng=True')
 
     def _frozen_state(self):
         """Everything the captured launches hold as kernel arguments or as a choice of code path."""
@@ -93,6 +119,15 @@ class GraphedTrainStep:
         c0, c1 = self.opt.coefficients(self.opt.step_count + 1)
         self.coef[0].fill_(c0)                 # two scalar fills: stream-ordered, no host synchronisation
         self.coef[1].fill_(c1)
+
+    def _fill_rng(self):
+        """device_rng: this step's draws, made as the eager forward makes them (fusion_model.py: `_fresh_seed()`, then the
+        uniforms of `_DecoderFn.forward`) and written stream-ordered into the buffers the captured launches read."""
+        if not self.device_rng:
+            return
+        self.seed.fill_(fusion_model._fresh_seed() if self.model.training else 0)
+        if self.ss_uniforms is not None:
+            self.ss_uniforms.copy_(torch.rand(*self.ss_uniforms.shape, device=self.ss_uniforms.device))
 
     def _body(self):
         self.opt.zero_grad()
@@ -131,6 +166,7 @@ class GraphedTrainStep:
             if src is not None:
                 put(dst, src, what)
         self._fill_coef()
+        self._fill_rng()
         self.graph.replay()
         self.opt.step_count += 1
         self.model._weights_epoch = getattr(self.model, '_weights_epoch', 0) + 1
