@@ -830,6 +830,29 @@ int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const int32_t* r
 int rfn_scst_reward(const double* scores, int B, int T, double weight, int use_baseline, float* out, double* out64,
                     void* stream);
 
+/* ---- self-critical reward: BLEU-D of token-id captions (cider/pyciderevalcap/bleuD, BleuD(4), option 'closest') ------------
+ * The same captions, rows, references and limits as rfn_ciderd_score.  Per score row: testlen = the caption's word count (the
+ * end token counts), guess[n] = max(0, testlen - n + 1), correct[n] = sum over the row's distinct n-grams of min(its count, the
+ * largest count in any one reference of the image), reflen = the reference length closest to testlen (the shorter on a tie);
+ * scores[r, k] = (prod_{j <= k} (correct[j] + 1e-15) / (guess[j] + 1e-9)) ^ (1 / (k + 1)), times exp(1 - 1 / ratio) when
+ * ratio = (testlen + 1e-15) / (reflen + 1e-9) < 1.  corpus: the same formula over the sums of the rows' components.
+ * Integer counting, then fp64 in one thread per row: bitwise reproducible, no atomics.  A row whose caption, or one of whose
+ * image's references, holds an id outside [0, vocab] (or whose row_img / n_refs is out of range) scores NaN in all four
+ * columns, has zero components and is left out of the corpus sums; other rows are unaffected.
+ * Two launches, a third when corpus != NULL; no allocation, no synchronisation (capturable in a graph).
+ * scores: n_rows x 4 doubles; comps: NULL or n_rows x 10 int32 (testlen, reflen, guess[4], correct[4]); corpus: NULL or 4
+ * doubles; ws: rfn_bleud_ws_bytes (0 for sizes outside the limits; T_res takes part in the limits only), 16-B aligned. */
+size_t rfn_bleud_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt);
+int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                    const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, double* scores, int32_t* comps,
+                    double* corpus, void* ws, size_t ws_bytes, void* stream);
+/* compute_reward's mix of the two: reward[b, :] = ((b4 * bleu4_weight) + (c * cider_weight)) + 0.0 with b4 = bleu[b, 3] -
+ * bleu[B + b, 3] and c = cider[b] - cider[B + b] (use_baseline) or the sampled row's score alone; every product and sum is
+ * rounded on its own, as numpy does.  cider: NULL or 2B doubles, bleu: NULL or 2B x 4 doubles (not both NULL); a NULL term is
+ * the 0 * weight the reference adds.  out (B, T) f32 and / or out64 (B, T) f64, either may be NULL. */
+int rfn_scst_reward_mix(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int T,
+                        int use_baseline, float* out, double* out64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

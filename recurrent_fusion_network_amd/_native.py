@@ -190,6 +190,9 @@ def _load():
         'rfn_ciderd_table_build': (C.c_int, [P, P, L, I, P, L, P]),
         'rfn_ciderd_score': (C.c_int, [P, I, I, P, P, P, I, I, I, P, L, C.c_double, I, C.c_double, P, P, SZ, P]),
         'rfn_scst_reward': (C.c_int, [P, I, I, C.c_double, I, P, P, P]),
+        'rfn_bleud_ws_bytes': (SZ, [I, I, I, I, I]),
+        'rfn_bleud_score': (C.c_int, [P, I, I, P, P, P, I, I, I, I, P, P, P, P, SZ, P]),
+        'rfn_scst_reward_mix': (C.c_int, [P, C.c_double, P, C.c_double, I, I, I, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

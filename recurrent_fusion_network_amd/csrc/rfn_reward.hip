@@ -325,6 +325,184 @@ __global__ void cd_scst_k(const double* __restrict__ scores, int B, int T, doubl
     if (out64) out64[g] = v;
 }
 
+// ---- BLEU-D (cider/pyciderevalcap/bleuD, BleuD(4) with option 'closest') ---------------------------------------
+// Same captions, keys and limits as CIDEr-D.  Launches of one call: refs (cook every reference: first-occurrence keys, raw
+// term counts, word count), hyp (one workgroup per score row: clip every distinct n-gram of the row against the maximum
+// count over the image's references, reduce correct[4], pick the closest reference length, write the row's four scores and
+// its integer components) and, when asked for, corpus (the same formula over the sums of the components).  Everything before
+// the formula is integer counting, the formula is fp64 in one thread: bitwise reproducible, no atomics on global memory.
+#define BD_COMPS 10   // testlen, reflen, guess[4], correct[4]
+
+__device__ void bd_formula(const double* correct, const double* guess, double testlen, double reflen, double* bleu) {
+    const double small = 1e-9, tiny = 1e-15;
+    double p = 1.0;
+    for (int k = 0; k < CD_N; ++k) {
+        p *= (correct[k] + tiny) / (guess[k] + small);
+        bleu[k] = pow(p, 1.0 / (double)(k + 1));
+    }
+    const double ratio = (testlen + tiny) / (reflen + small);
+    if (ratio < 1.0) {
+        const double bp = exp(1.0 - 1.0 / ratio);
+        for (int k = 0; k < CD_N; ++k) bleu[k] *= bp;
+    }
+}
+
+// one workgroup per image: per (image, ref) slot rkey[4*Tg] (first occurrences), rcnt[4*Tg] (term counts), rlen (words)
+__global__ __launch_bounds__(CD_THREADS) void bd_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
+                                                        int max_refs, int Tg, int vocab, uint64_t* __restrict__ rkey,
+                                                        int32_t* __restrict__ rcnt, int32_t* __restrict__ rlen,
+                                                        int32_t* __restrict__ img_bad) {
+    __shared__ uint64_t skey[CD_THREADS];
+    __shared__ int sw, sbad;
+    const int i = blockIdx.x, t = threadIdx.x, S = CD_N * Tg;
+    const int nr = n_refs[i];
+    int bad_img = (nr < 1 || nr > max_refs);
+    const int nrc = bad_img ? 0 : nr;
+    for (int j = 0; j < nrc; ++j) {
+        int tf, words, bad;
+        const uint64_t key = cd_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+        const long o = ((long)i * max_refs + j) * S;
+        if (t < S) {
+            rkey[o + t] = key;
+            rcnt[o + t] = tf;
+        }
+        if (t == 0) rlen[(long)i * max_refs + j] = words;
+        bad_img |= bad;
+    }
+    if (t == 0) img_bad[i] = bad_img;
+}
+
+// one workgroup per score row.  comps: n_rows x BD_COMPS (testlen = -1 marks a row that scores NaN); ucomps: NULL or the
+// caller's copy of it (zeros for a NaN row).
+__global__ __launch_bounds__(CD_THREADS) void bd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
+                                                       int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
+                                                       int max_refs, int Tg, const uint64_t* __restrict__ rkey,
+                                                       const int32_t* __restrict__ rcnt, const int32_t* __restrict__ rlen, int vocab,
+                                                       double* __restrict__ scores, int32_t* __restrict__ comps,
+                                                       int32_t* __restrict__ ucomps) {
+    __shared__ uint64_t skey[CD_THREADS], rk[CD_THREADS];
+    __shared__ int rc[CD_THREADS], clip[CD_THREADS];
+    __shared__ int correct[CD_N];
+    __shared__ int sw, sbad;
+    const int r = blockIdx.x, t = threadIdx.x, Sg = CD_N * Tg;
+    const int i = row_img[r];
+    int tf = 0, words = 0, bad = (i < 0 || i >= n_img || img_bad[i]);   // block-uniform
+    uint64_t key = 0;
+    if (!bad) key = cd_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    if (bad) {
+        if (t < CD_N) scores[(long)r * CD_N + t] = __builtin_nan("");
+        if (t < BD_COMPS) {
+            comps[(long)r * BD_COMPS + t] = t == 0 ? -1 : 0;
+            if (ucomps) ucomps[(long)r * BD_COMPS + t] = 0;
+        }
+        return;
+    }
+    const int nr = n_refs[i];
+    const int n = t / T;
+    int maxc = 0;
+    for (int j = 0; j < nr; ++j) {
+        const long ij = (long)i * max_refs + j;
+        if (t < Sg) {
+            rk[t] = rkey[ij * Sg + t];
+            rc[t] = rcnt[ij * Sg + t];
+        }
+        __syncthreads();
+        if (key) {
+            for (int q = n * Tg; q < n * Tg + Tg; ++q)
+                if (rk[q] == key) {
+                    maxc = max(maxc, rc[q]);
+                    break;
+                }
+        }
+        __syncthreads();
+    }
+    clip[t] = key ? min(tf, maxc) : 0;
+    __syncthreads();
+    if (t < CD_N) {
+        int s = 0;
+        for (int p = 0; p < T; ++p) s += clip[t * T + p];
+        correct[t] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+        int reflen = rlen[(long)i * max_refs], best = abs(reflen - words);   // min((|l - testlen|, l)): a tie takes the shorter
+        for (int j = 1; j < nr; ++j) {
+            const int l = rlen[(long)i * max_refs + j], d = abs(l - words);
+            if (d < best || (d == best && l < reflen)) {
+                best = d;
+                reflen = l;
+            }
+        }
+        int c[BD_COMPS];
+        c[0] = words;
+        c[1] = reflen;
+        double cor[CD_N], gue[CD_N], bleu[CD_N];
+        for (int k = 0; k < CD_N; ++k) {
+            c[2 + k] = words - k > 0 ? words - k : 0;
+            c[2 + CD_N + k] = correct[k];
+            gue[k] = (double)c[2 + k];
+            cor[k] = (double)correct[k];
+        }
+        bd_formula(cor, gue, (double)words, (double)reflen, bleu);
+        for (int k = 0; k < CD_N; ++k) scores[(long)r * CD_N + k] = bleu[k];
+        for (int k = 0; k < BD_COMPS; ++k) {
+            comps[(long)r * BD_COMPS + k] = c[k];
+            if (ucomps) ucomps[(long)r * BD_COMPS + k] = c[k];
+        }
+    }
+}
+
+// one workgroup: the corpus-level four from the integer sums of the rows' components (NaN rows left out)
+__global__ __launch_bounds__(CD_THREADS) void bd_corpus_k(const int32_t* __restrict__ comps, int n_rows, double* __restrict__ corpus) {
+    __shared__ long long part[CD_THREADS];
+    __shared__ long long tot[BD_COMPS];
+    const int t = threadIdx.x;
+    for (int k = 0; k < BD_COMPS; ++k) {
+        long long s = 0;
+        for (int r = t; r < n_rows; r += CD_THREADS)
+            if (comps[(long)r * BD_COMPS] >= 0) s += comps[(long)r * BD_COMPS + k];
+        part[t] = s;
+        __syncthreads();
+        for (int w = CD_THREADS / 2; w > 0; w >>= 1) {
+            if (t < w) part[t] += part[t + w];
+            __syncthreads();
+        }
+        if (t == 0) tot[k] = part[0];
+        __syncthreads();
+    }
+    if (t == 0) {
+        double cor[CD_N], gue[CD_N], bleu[CD_N];
+        for (int k = 0; k < CD_N; ++k) {
+            gue[k] = (double)tot[2 + k];
+            cor[k] = (double)tot[2 + CD_N + k];
+        }
+        bd_formula(cor, gue, (double)tot[0], (double)tot[1], bleu);
+        for (int k = 0; k < CD_N; ++k) corpus[k] = bleu[k];
+    }
+}
+
+// compute_reward's mix: ((bleu4 * w_b) + (cider * w_c)) + spice * 0, each product and sum rounded on its own
+__global__ void bd_mix_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu, double bleu4_weight,
+                         int B, int T, int use_baseline, float* __restrict__ out, double* __restrict__ out64) {
+#pragma clang fp contract(off)
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long)B * T) return;
+    const int b = (int)(g / T);
+    double sb = 0.0, sc = 0.0;
+    if (bleu) {
+        sb = bleu[(long)b * CD_N + 3];
+        if (use_baseline) sb = sb - bleu[(long)(B + b) * CD_N + 3];
+    }
+    if (cider) {
+        sc = cider[b];
+        if (use_baseline) sc = sc - cider[B + b];
+    }
+    const double tb = sb * bleu4_weight, tc = sc * cider_weight;
+    const double v = (tb + tc) + 0.0;
+    if (out) out[g] = (float)v;
+    if (out64) out64[g] = v;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------
 namespace {
 const size_t kAlign = 256;
@@ -447,6 +625,66 @@ extern "C" int rfn_scst_reward(const double* scores, int B, int T, double weight
     if (!scores || (!out && !out64)) return RFN_ERR_ARG;
     const long n = (long)B * T;
     cd_scst_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(scores, B, T, weight, use_baseline, out, out64);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- BLEU-D host side ------------------------------------------------------------------------------------
+namespace {
+struct BleuLayout {
+    size_t rkey, rcnt, rlen, bad, comps, total;
+};
+BleuLayout bleu_layout(int n_rows, int n_img, int max_refs, int T_gt) {
+    BleuLayout L{};
+    const size_t nref = (size_t)n_img * max_refs;
+    size_t o = 0;
+    L.rkey = o;  o = up(o + nref * CD_N * T_gt * 8);
+    L.rcnt = o;  o = up(o + nref * CD_N * T_gt * 4);
+    L.rlen = o;  o = up(o + nref * 4);
+    L.bad = o;   o = up(o + (size_t)n_img * 4);
+    L.comps = o; o = up(o + (size_t)n_rows * BD_COMPS * 4);
+    L.total = o;
+    return L;
+}
+}  // namespace
+
+extern "C" size_t rfn_bleud_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
+    return bleu_layout(n_rows, n_img, max_refs, T_gt).total;
+}
+
+extern "C" int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                               const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, double* scores, int32_t* comps,
+                               double* corpus, void* ws, size_t ws_bytes, void* stream) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > CD_MAX_ID) return RFN_ERR_SHAPE;
+    if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
+    const BleuLayout L = bleu_layout(n_rows, n_img, max_refs, T_gt);
+    if (ws_bytes < L.total) return RFN_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    uint64_t* rkey = (uint64_t*)(w + L.rkey);
+    int32_t* rcnt = (int32_t*)(w + L.rcnt);
+    int32_t* rlen = (int32_t*)(w + L.rlen);
+    int32_t* bad = (int32_t*)(w + L.bad);
+    int32_t* wcomps = (int32_t*)(w + L.comps);
+    bd_refs_k<<<n_img, CD_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rlen, bad);
+    RFN_CHECK_LAUNCH();
+    bd_hyp_k<<<n_rows, CD_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rcnt, rlen, vocab, scores,
+                                            wcomps, comps);
+    RFN_CHECK_LAUNCH();
+    if (corpus) {
+        bd_corpus_k<<<1, CD_THREADS, 0, st>>>(wcomps, n_rows, corpus);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+
+extern "C" int rfn_scst_reward_mix(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int T,
+                                   int use_baseline, float* out, double* out64, void* stream) {
+    if (B < 1 || T < 1) return RFN_ERR_SHAPE;
+    if ((!cider && !bleu) || (!out && !out64)) return RFN_ERR_ARG;
+    const long n = (long)B * T;
+    bd_mix_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, T, use_baseline, out, out64);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -1,11 +1,15 @@
-"""Self-critical reward on the GPU: CIDEr-D of token-id captions (csrc/rfn_reward.hip) and drop-ins for the reference's
-get_rewards.py (get_self_critical_reward_feat_array / get_self_critical_reward).
+"""Self-critical reward on the GPU: CIDEr-D and BLEU-D of token-id captions (csrc/rfn_reward.hip) and drop-ins for the
+reference's get_rewards.py (get_self_critical_reward_feat_array / get_self_critical_reward).
 
 CiderD reproduces cider/pyciderevalcap/ciderD's CiderD(n=4, sigma=6.0) as compute_reward calls it, on captions given as id
 rows (the ids up to and including the first 0, as array_to_str keeps them).  Document frequencies come from the scored
 rows themselves (df='corpus') or from a precomputed table (the reference's df='coco-train-idxs' pickle, or any dict of
 id-string tuples).  Corpus df is per call: under data parallelism each rank scores its own shard, as per-rank runs of the
-reference would.  BLEU-D and SPICE-D are not ported.
+reference would.
+
+BleuD reproduces cider/pyciderevalcap/bleuD's BleuD(4) (closest reference length) on the same id rows: four scores per row, the
+row's integer components and the corpus-level four.  compute_reward's bleu4 * bleu4_weight + cider * cider_weight is mixed on
+the device (scst_reward with bleu_scorer=).  SPICE-D (a Java server behind a socket) is not ported.
 """
 from __future__ import annotations
 
@@ -126,37 +130,71 @@ class CiderD:
     def compute_score(self, gts, res):
         """The reference's interface: gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}], captions
         being space-separated id strings as array_to_str writes them.  -> (mean, np.ndarray of per-entry scores)."""
-        images, img_of = [], {}
-        rows = []
-        for entry in res:
-            hyp = entry['caption']
-            if not isinstance(hyp, list) or len(hyp) != 1:
-                raise ValueError('each res caption is a list of one string')
-            iid = entry['image_id']
-            if iid not in img_of:
-                refs = gts[iid]
-                if not isinstance(refs, list) or not refs:
-                    raise ValueError('gts[%r] must be a non-empty list of captions' % (iid,))
-                img_of[iid] = len(images)
-                images.append([_words(s) for s in refs])
-            rows.append((_words(hyp[0]), img_of[iid]))
-        T = max(len(w) for w, _ in rows)
-        Tg = max(len(w) for refs in images for w in refs)
-        res_a = np.array([_row(w, T) for w, _ in rows], dtype=np.int64)
-        R = max(len(refs) for refs in images)
-        gts_a = np.zeros((len(images), R, Tg), dtype=np.int64)
-        for i, refs in enumerate(images):
-            for j, w in enumerate(refs):
-                gts_a[i, j] = _row(w, Tg)
-        vocab = int(max(res_a.max(), gts_a.max(), 0))
+        res_a, row_img, gts_a, n_refs, vocab = _id_arrays(gts, res)
         dev = torch.device('cuda', torch.cuda.current_device())
-        s = self.score_ids(torch.from_numpy(res_a).to(dev), torch.tensor([i for _, i in rows], dtype=torch.int32),
-                           torch.from_numpy(gts_a), torch.tensor([len(r) for r in images], dtype=torch.int32),
-                           vocab=min(vocab, MAX_ID)).cpu().numpy()
+        s = self.score_ids(torch.from_numpy(res_a).to(dev), row_img, torch.from_numpy(gts_a), n_refs, vocab=vocab).cpu().numpy()
         return np.mean(s), s
 
     def method(self):
         return 'CIDEr-D'
+
+
+class BleuD:
+    """BLEU-D scorer: the reference's BleuD(4), whose rows take the closest reference length."""
+
+    def __init__(self, n=4):
+        if n != 4:
+            raise NotImplementedError('only n = 4 (compute_reward\'s BleuD(4)) is implemented')
+        self._n = n
+        self._ws = None
+
+    def _workspace(self, dev, nbytes):
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self._ws
+
+    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, comps=None, corpus=None):
+        """Arguments as CiderD.score_ids.  -> (N, 4) float64 BLEU-1..4 per row on the device (NaN in all four for a row whose
+        caption or references hold an id outside [0, vocab]).  comps: optional (N, 10) int32 device tensor that receives
+        testlen, reflen, guess[4], correct[4] of every row; corpus: optional (4,) float64 device tensor that receives the
+        corpus-level scores (one more small launch)."""
+        dev = res.device
+        if dev.type != 'cuda':
+            raise N.RfnError('res must live on the GPU: the reward has no CPU fallback')
+        res = res.to(torch.int64).contiguous()
+        gts = gts.to(dev, torch.int64).contiguous()
+        row_img = row_img.to(dev, torch.int32).contiguous()
+        n_refs = n_refs.to(dev, torch.int32).contiguous()
+        n_rows, T = res.shape
+        n_img, R, Tg = gts.shape
+        if row_img.numel() != n_rows or n_refs.numel() != n_img:
+            raise ValueError('row_img needs one entry per row and n_refs one per image')
+        nbytes = N.lib.rfn_bleud_ws_bytes(n_rows, T, n_img, R, Tg)
+        if nbytes == 0:
+            raise ValueError('BLEU-D limits: 1 <= T <= %d, 1 <= refs per image <= %d' % (MAX_T, MAX_REFS))
+        ws = self._workspace(dev, nbytes)
+        if out is None:
+            out = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
+        for t, name, shape, dtype in ((out, 'out', (n_rows, 4), torch.float64), (comps, 'comps', (n_rows, 10), torch.int32),
+                                      (corpus, 'corpus', (4,), torch.float64)):
+            if t is not None and (t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError('%s must be a contiguous %s %s tensor on %s' % (name, shape, dtype, dev))
+        N.check(N.lib.rfn_bleud_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(), n_img, R,
+                                      Tg, vocab, out.data_ptr(), N.ptr(comps), N.ptr(corpus), ws.data_ptr(), ws.numel(),
+                                      N.stream_ptr()), 'rfn_bleud_score')
+        return out
+
+    def compute_score(self, gts, res):
+        """The reference's interface (see CiderD.compute_score) -> (the corpus-level [BLEU-1 .. BLEU-4], four lists of
+        per-entry scores), as BleuD.compute_score returns them."""
+        res_a, row_img, gts_a, n_refs, vocab = _id_arrays(gts, res)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        corpus = torch.empty(4, dtype=torch.float64, device=dev)
+        s = self.score_ids(torch.from_numpy(res_a).to(dev), row_img, torch.from_numpy(gts_a), n_refs, vocab=vocab, corpus=corpus)
+        return corpus.cpu().tolist(), s.cpu().numpy().T.tolist()
+
+    def method(self):
+        return 'Bleu'
 
 
 def _int_word(w):
@@ -183,6 +221,36 @@ def _row(words, T):
                      'first 0, or exactly T ids without one)' % (' '.join(map(str, words)), T))
 
 
+def _id_arrays(gts, res):
+    """compute_score's dicts (gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}]) as id arrays:
+    res (N, T) int64, row_img (N,) int32 tensor, gts (n_img, R, Tg) int64, n_refs (n_img,) int32 tensor, vocab."""
+    images, img_of = [], {}
+    rows = []
+    for entry in res:
+        hyp = entry['caption']
+        if not isinstance(hyp, list) or len(hyp) != 1:
+            raise ValueError('each res caption is a list of one string')
+        iid = entry['image_id']
+        if iid not in img_of:
+            refs = gts[iid]
+            if not isinstance(refs, list) or not refs:
+                raise ValueError('gts[%r] must be a non-empty list of captions' % (iid,))
+            img_of[iid] = len(images)
+            images.append([_words(s) for s in refs])
+        rows.append((_words(hyp[0]), img_of[iid]))
+    T = max(len(w) for w, _ in rows)
+    Tg = max(len(w) for refs in images for w in refs)
+    res_a = np.array([_row(w, T) for w, _ in rows], dtype=np.int64)
+    R = max(len(refs) for refs in images)
+    gts_a = np.zeros((len(images), R, Tg), dtype=np.int64)
+    for i, refs in enumerate(images):
+        for j, w in enumerate(refs):
+            gts_a[i, j] = _row(w, Tg)
+    vocab = int(max(res_a.max(), gts_a.max(), 0))
+    return (res_a, torch.tensor([i for _, i in rows], dtype=torch.int32), gts_a,
+            torch.tensor([len(r) for r in images], dtype=torch.int32), min(vocab, MAX_ID))
+
+
 _ROW_CACHE = {}
 
 
@@ -206,20 +274,31 @@ def pad_gts(gts_list, dev):
     return torch.from_numpy(out).to(dev), torch.from_numpy(n_refs).to(dev)
 
 
-def scst_reward(scorer, gen_result, greedy_res, gts, n_refs, seq_per_img, cider_weight=1.0, use_baseline=True, out64=None):
-    """compute_reward's CIDEr-D term on the device: scores the B sampled rows then the B greedy rows (row r points at image
+def scst_reward(scorer, gen_result, greedy_res, gts, n_refs, seq_per_img, cider_weight=1.0, use_baseline=True, out64=None,
+                bleu_scorer=None, bleu4_weight=0.0):
+    """compute_reward on the device: scores the B sampled rows then the B greedy rows (row r points at image
     (r % B) // seq_per_img), -> (B, T) float32 reward = cider_weight * (s[b] - s[B + b]) (or cider_weight * s[b]).  gts:
     (n_img, R, Tg) padded references, n_refs (n_img,).  out64: optional (B, T) float64 tensor that receives the same reward
-    before the cast."""
+    before the cast.  bleu_scorer: a BleuD -> the reward is bleu4_weight * BLEU-4 + cider_weight * CIDEr-D, each as a
+    difference to the greedy row under use_baseline (`scorer` may then be None: the CIDEr-D term is the reference's 0)."""
     B, T = gen_result.shape
     if greedy_res.shape != gen_result.shape:
         raise ValueError('gen_result and greedy_res must have the same shape')
+    if scorer is None and bleu_scorer is None:
+        raise ValueError('scst_reward needs a CIDEr-D scorer, a BLEU-D scorer or both')
     dev = gen_result.device
     res = torch.cat([gen_result.to(torch.int64), greedy_res.to(dev, torch.int64)], 0)
-    scores = scorer.score_ids(res, _scst_row_img(B, seq_per_img, dev), gts, n_refs)
+    row_img = _scst_row_img(B, seq_per_img, dev)
+    scores = None if scorer is None else scorer.score_ids(res, row_img, gts, n_refs)
     out = torch.empty(B, T, dtype=torch.float32, device=dev)
-    N.check(N.lib.rfn_scst_reward(scores.data_ptr(), B, T, C.c_double(cider_weight), int(bool(use_baseline)), out.data_ptr(),
-                                  N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward')
+    if bleu_scorer is None:
+        N.check(N.lib.rfn_scst_reward(scores.data_ptr(), B, T, C.c_double(cider_weight), int(bool(use_baseline)),
+                                      out.data_ptr(), N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward')
+        return out
+    bleu = bleu_scorer.score_ids(res, row_img, gts, n_refs)
+    N.check(N.lib.rfn_scst_reward_mix(N.ptr(scores), C.c_double(cider_weight), bleu.data_ptr(), C.c_double(bleu4_weight), B, T,
+                                      int(bool(use_baseline)), out.data_ptr(), N.ptr(out64), N.stream_ptr()),
+            'rfn_scst_reward_mix')
     return out
 
 
@@ -233,31 +312,41 @@ def default_scorer():
     return _DEFAULT['scorer']
 
 
-def _reward(model_sample, data, gen_result, opt, device, scorer):
-    if getattr(opt, 'bleu4_weight', 0) > 0 or getattr(opt, 'spice_weight', 0) > 0:
-        raise NotImplementedError('BLEU-D and SPICE-D rewards are not ported; set bleu4_weight = spice_weight = 0')
-    scorer = scorer or default_scorer()
+def _reward(model_sample, data, gen_result, opt, device, scorer, bleu_scorer):
+    if getattr(opt, 'spice_weight', 0) > 0:
+        raise NotImplementedError('the SPICE-D reward is not ported (of BLEU-D and SPICE-D only BLEU-D is); set spice_weight = 0')
+    w_b = getattr(opt, 'bleu4_weight', 0)
+    if w_b > 0 and bleu_scorer is None:
+        raise NotImplementedError('of BLEU-D and SPICE-D only BLEU-D is ported, and bleu4_weight > 0 needs its scorer: pass '
+                                  'bleu_scorer=BleuD() (or set bleu4_weight = 0)')
+    if not w_b > 0:
+        bleu_scorer = None             # the reference does not run BleuD then
+    w, base = getattr(opt, 'cider_weight', 1.0), getattr(opt, 'use_baseline', 1)
+    if scorer is None and not (bleu_scorer is not None and w == 0):
+        scorer = default_scorer()      # not with cider_weight == 0 beside BLEU-D: that mix needs no df pickle
     with torch.no_grad():
         greedy_res = model_sample()[0]
     B, T = gen_result.shape
     gts, n_refs = pad_gts(data['gts'], gen_result.device)
     spi = B // len(data['gts'])
-    w, base = getattr(opt, 'cider_weight', 1.0), getattr(opt, 'use_baseline', 1)
     if device:
-        return scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base)
+        return scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
     out64 = torch.empty(B, T, dtype=torch.float64, device=gen_result.device)
-    scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base, out64=out64)
+    scst_reward(scorer, gen_result, greedy_res, gts, n_refs, spi, w, base, out64=out64, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
     return out64.cpu().numpy()
 
 
 def get_self_critical_reward_feat_array(idx_to_word, model, fc_feat_array, att_feat_array, data, gen_result, opt, device=False,
-                                        scorer=None):
+                                        scorer=None, bleu_scorer=None):
     """get_rewards.py:115-129: greedy baseline from model.sample (in the module's current mode, without gradients), then
-    the CIDEr-D reward.  -> numpy (B, T) float64 like the reference, or the device (B, T) float32 tensor with device=True.
-    scorer: a CiderD (default: default_scorer(), the reference's df='coco-train-idxs')."""
-    return _reward(lambda: model.sample(list(fc_feat_array), list(att_feat_array)), data, gen_result, opt, device, scorer)
+    the reward.  -> numpy (B, T) float64 like the reference, or the device (B, T) float32 tensor with device=True.
+    scorer: a CiderD (default: default_scorer(), the reference's df='coco-train-idxs'); bleu_scorer: a BleuD, needed when
+    opt.bleu4_weight > 0 (NotImplementedError without it; opt.spice_weight > 0 always raises it)."""
+    return _reward(lambda: model.sample(list(fc_feat_array), list(att_feat_array)), data, gen_result, opt, device, scorer,
+                   bleu_scorer)
 
 
-def get_self_critical_reward(idx_to_word, model, fc_feats, att_feats, data, gen_result, opt, device=False, scorer=None):
+def get_self_critical_reward(idx_to_word, model, fc_feats, att_feats, data, gen_result, opt, device=False, scorer=None,
+                             bleu_scorer=None):
     """get_rewards.py:132-140 (single-feature models): as get_self_critical_reward_feat_array."""
-    return _reward(lambda: model.sample(fc_feats, att_feats), data, gen_result, opt, device, scorer)
+    return _reward(lambda: model.sample(fc_feats, att_feats), data, gen_result, opt, device, scorer, bleu_scorer)

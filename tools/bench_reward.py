@@ -4,7 +4,10 @@
     B = 128 (1 row per image), 640 and 1280 (5 rows per image), in corpus mode and in table mode (a synthetic df table);
   - the C5 self-critical step (bench.py's RL leg: multinomial sample, greedy baseline, reward criterion, backward, clamp +
     Adam at B = 128) with the real reward against the same step with a randn reward, and the difference.
-Usage: python tools/bench_reward.py [--steps 50] [--warmup 5]
+  - --bleu: instead, the BLEU-D legs (profiles/bleud_reward.json): at the C5 shape (128 + 128 rows, 5 refs) and at the shape
+    of the spi5 golden tier (640 + 640 rows, 128 images, 5-7 refs) the CIDEr-only call (corpus mode, the call timed above), the
+    BLEU-only call and the mixed call, alternated in blocks of --block calls over --rounds rounds; min / median / max per leg.
+Usage: python tools/bench_reward.py [--steps 50] [--warmup 5] | --bleu [--block 2000] [--rounds 7]
 """
 import argparse
 import json
@@ -50,11 +53,43 @@ def time_calls(fn, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+def bleu_legs(args):
+    from recurrent_fusion_network_amd import rewards as RW
+    dev = torch.device('cuda:0')
+    out = {'metric': 'self-critical reward, ms per scst_reward call (sample + greedy rows, T = 16): CIDEr-D only (corpus df), '
+                     'BLEU-D only, mixed', 'unit': 'ms', 'calls_per_block': args.block, 'rounds': args.rounds,
+           'device': torch.cuda.get_device_name(0)}
+    cider, bleu = RW.CiderD(), RW.BleuD()
+    for tag, B, spi, refs in (('c5_128x2', 128, 1, 5), ('spi5_640x2', 640, 5, 7)):
+        gen, greedy, gts, n_refs = scoring_case(B, spi, dev, B, refs=refs)
+        if refs > 5:
+            n_refs = torch.from_numpy(np.random.default_rng(B).integers(5, refs + 1, B // spi).astype(np.int32)).to(dev)
+        legs = {'cider': lambda: RW.scst_reward(cider, gen, greedy, gts, n_refs, spi),
+                'bleu': lambda: RW.scst_reward(None, gen, greedy, gts, n_refs, spi, 0.0, bleu_scorer=bleu, bleu4_weight=1.0),
+                'mixed': lambda: RW.scst_reward(cider, gen, greedy, gts, n_refs, spi, 1.0, bleu_scorer=bleu, bleu4_weight=0.5)}
+        times = {k: [] for k in legs}
+        for k, fn in legs.items():
+            time_calls(fn, args.block // 4, 20)           # warm every leg at this shape
+        for _ in range(args.rounds):
+            for k, fn in legs.items():
+                times[k].append(time_calls(fn, args.block, 0))
+        for k, v in times.items():
+            v = sorted(v)
+            out['%s_%s' % (tag, k)] = {'min': round(v[0], 4), 'median': round(v[len(v) // 2], 4), 'max': round(v[-1], 4)}
+        out['%s_mixed_over_cider' % tag] = round(out[tag + '_mixed']['median'] / out[tag + '_cider']['median'], 3)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--bleu', action='store_true', help='time the BLEU-D and mixed reward calls next to the CIDEr-D call')
+    ap.add_argument('--block', type=int, default=2000)
+    ap.add_argument('--rounds', type=int, default=7)
     args = ap.parse_args()
+    if args.bleu:
+        return bleu_legs(args)
     import bench
     import recurrent_fusion_network_amd as R
     from recurrent_fusion_network_amd import rewards as RW
