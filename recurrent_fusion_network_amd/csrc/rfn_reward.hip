@@ -1,28 +1,39 @@
-// CIDEr-D of token-id captions and the self-critical reward (get_rewards.py:39-112 with
-// cider/pyciderevalcap/ciderD/ciderD_scorer.py, CiderD(n=4, sigma=6.0)) on the GPU.
+// The self-critical reward on the GPU (get_rewards.py:39-112): CIDEr-D (cider/pyciderevalcap/ciderD, CiderD(n=4,
+// sigma=6.0)) and BLEU-D (cider/pyciderevalcap/bleuD, BleuD(4) with option 'closest') of token-id captions, and
+// compute_reward's mix of the two.
 //
-// A caption is the ids of its row up to and including the first 0 (all T ids when there is none), as
-// array_to_str builds it.  An n-gram (n = 1..4) packs into one uint64: four 15-bit ids and n in bits 60-62,
-// so no valid key is 0 and equal keys are equal n-grams (no hash collision can change a result).  Document
-// frequencies live in an open-addressing, linear-probe table:
+// Shared by both scorers (rw_): a caption is the ids of its row up to and including the first 0 (all T ids when there
+// is none), as array_to_str builds it.  An n-gram (n = 1..4) packs into one uint64: four 15-bit ids and n in bits
+// 60-62, so no valid key is 0 and equal keys are equal n-grams (no hash collision can change a result).  rw_cook turns
+// a caption into first-occurrence keys, term counts and a word count; rw_refs_k stores that for every reference (one
+// workgroup per image); a hypothesis kernel cooks its score row (one workgroup per row) and walks the references of
+// its image through LDS with rw_lookup.  rw_reward_k forms the reward from the scores.
+//
+// CIDEr-D (cd_): document frequencies live in an open-addressing, linear-probe table:
 //   - corpus mode: the workspace table is cleared and filled every call; one integer atomicAdd per unique
 //     n-gram of an image adds the number of score rows that point at that image (compute_reward's crefs);
 //   - table mode: rfn_ciderd_table_build inserts a precomputed df once and stores log(max(1, df)).
-// Launches of one call: [clear], refs (cook every reference caption, insert df), ref_vec (tf-idf values and
-// per-n norms of every reference), hyp (one workgroup per score row: its vector, the clipped similarity
-// against every reference of its image, the score).  Everything after the df counts is fp64 in fixed
-// summation orders, so scores are bitwise reproducible; the only atomics are the integer df counts.
+// Launches of one call: [clear], refs (with the df insert in corpus mode), ref_vec (tf-idf values and per-n norms of
+// every reference), hyp (the row's vector, the clipped similarity against every reference of its image, the score).
+// Everything after the df counts is fp64 in fixed summation orders, so scores are bitwise reproducible; the only
+// atomics are the integer df counts.
+//
+// BLEU-D (bd_): launches of one call: refs, hyp (clip every distinct n-gram of the row against the maximum count over
+// the image's references, reduce correct[4], pick the closest reference length, write the row's four scores and its
+// integer components) and, when asked for, corpus (the same formula over the sums of the components).  Everything
+// before the formula is integer counting, the formula is fp64 in one thread: bitwise reproducible, no atomics on
+// global memory.
 #include <math.h>
 
 #include <algorithm>
 
 #include "rfn_common.h"
 
-#define CD_N 4
-#define CD_MAX_T 64
-#define CD_MAX_REFS 32
-#define CD_MAX_ID 32767
-#define CD_THREADS 256   // >= CD_N * CD_MAX_T: one thread per n-gram slot (n, position)
+#define RW_N 4
+#define RW_MAX_T 64
+#define RW_MAX_REFS 32
+#define RW_MAX_ID 32767
+#define RW_THREADS 256   // >= RW_N * RW_MAX_T: one thread per n-gram slot (n, position)
 
 __device__ __forceinline__ uint64_t cd_hash(uint64_t k) {   // splitmix64 finaliser
     k ^= k >> 30;
@@ -69,11 +80,11 @@ __device__ __forceinline__ double cd_logdf(const CdDf& df, uint64_t key) {
     return log(fmax(1.0, h < 0 ? 0.0 : (double)df.cnt[h]));
 }
 
-// Cook one caption of T ids (block-wide; blockDim.x = CD_THREADS).  Thread t < 4T owns n-gram slot (n = t / T,
+// Cook one caption of T ids (block-wide; blockDim.x = RW_THREADS).  Thread t < 4T owns n-gram slot (n = t / T,
 // p = t % T); it returns the key when its slot holds the FIRST occurrence of an n-gram in the caption (0 otherwise) and
 // the n-gram's term count in *tf.  *words: the caption's word count; the return of *bad: an id outside [0, vocab].
-// skey: CD_THREADS keys of LDS; sw / sbad: LDS ints.  All threads must call it.
-__device__ uint64_t cd_cook(const int64_t* __restrict__ ids, int T, int vocab, uint64_t* skey, int* sw, int* sbad,
+// skey: RW_THREADS keys of LDS; sw / sbad: LDS ints.  All threads must call it.
+__device__ uint64_t rw_cook(const int64_t* __restrict__ ids, int T, int vocab, uint64_t* skey, int* sw, int* sbad,
                             int* tf, int* words, int* bad) {
     const int t = threadIdx.x;
     if (t == 0) {
@@ -93,7 +104,7 @@ __device__ uint64_t cd_cook(const int64_t* __restrict__ ids, int T, int vocab, u
     const int b = *sbad;
     uint64_t key = 0;
     int n = 0, p = 0;
-    if (t < CD_N * T) {
+    if (t < RW_N * T) {
         n = t / T;
         p = t - n * T;
         if (!b && p + n < W) {
@@ -130,44 +141,45 @@ __global__ void cd_clear_k(uint64_t* __restrict__ keys, uint32_t* __restrict__ c
 }
 
 // ---- references: one workgroup per image ----------------------------------------------------------------
-// Writes, per (image, ref) slot: rkey[4*Tg] (first occurrences), rval[4*Tg] (the term count, made tf-idf by ref_vec_k),
-// rlen; per image img_bad.  Corpus mode (dkeys != NULL) then adds the image's row count to the df of every n-gram its
-// references hold (once per image).  Dynamic LDS: max_refs * 4 * Tg keys.
-__global__ __launch_bounds__(CD_THREADS) void cd_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
-                                                        int max_refs, int Tg, const int32_t* __restrict__ row_img, int n_rows,
-                                                        int vocab, uint64_t* __restrict__ rkey, double* __restrict__ rval,
-                                                        int32_t* __restrict__ rlen, int32_t* __restrict__ img_bad,
-                                                        uint64_t* dkeys, uint32_t* dcnt, long dslots) {
+// Writes, per (image, ref) slot: rkey[4*Tg] (first occurrences), rcnt[4*Tg] (term counts), rwords (the word count); per
+// image img_bad.  CORPUS_DF (CIDEr-D's corpus mode) then adds the image's row count to the df of every n-gram its
+// references hold (once per image); only that instantiation uses dynamic LDS: max_refs * 4 * Tg keys.
+template <bool CORPUS_DF>
+__global__ __launch_bounds__(RW_THREADS) void rw_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
+                                                        int max_refs, int Tg, int vocab, uint64_t* __restrict__ rkey,
+                                                        int32_t* __restrict__ rcnt, int32_t* __restrict__ rwords,
+                                                        int32_t* __restrict__ img_bad, const int32_t* __restrict__ row_img,
+                                                        int n_rows, uint64_t* dkeys, uint32_t* dcnt, long dslots) {
     extern __shared__ uint64_t all[];
-    __shared__ uint64_t skey[CD_THREADS];
+    __shared__ uint64_t skey[RW_THREADS];
     __shared__ int sw, sbad, srows;
-    const int i = blockIdx.x, t = threadIdx.x, S = CD_N * Tg;
+    const int i = blockIdx.x, t = threadIdx.x, S = RW_N * Tg;
     const int nr = n_refs[i];
     int bad_img = (nr < 1 || nr > max_refs);
     const int nrc = bad_img ? 0 : nr;
     for (int j = 0; j < nrc; ++j) {
         int tf, words, bad;
-        const uint64_t key = cd_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+        const uint64_t key = rw_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
         const long o = ((long)i * max_refs + j) * S;
         if (t < S) {
             rkey[o + t] = key;
-            rval[o + t] = (double)tf;
-            all[j * S + t] = key;
+            rcnt[o + t] = tf;
+            if (CORPUS_DF) all[j * S + t] = key;
         }
-        if (t == 0) rlen[(long)i * max_refs + j] = words > 1 ? words - 1 : 0;
+        if (t == 0) rwords[(long)i * max_refs + j] = words;
         bad_img |= bad;
     }
     if (t == 0) img_bad[i] = bad_img;
-    if (!dkeys || bad_img) return;   // bad_img is block-uniform
+    if (!CORPUS_DF || bad_img) return;   // bad_img is block-uniform
     if (t == 0) srows = 0;
     __syncthreads();
     int mine = 0;
-    for (int r = t; r < n_rows; r += CD_THREADS) mine += (row_img[r] == i);
+    for (int r = t; r < n_rows; r += RW_THREADS) mine += (row_img[r] == i);
     if (mine) atomicAdd(&srows, mine);
     __syncthreads();
     const int rows = srows;
     if (rows == 0) return;
-    for (int x = t; x < nrc * S; x += CD_THREADS) {
+    for (int x = t; x < nrc * S; x += RW_THREADS) {
         const uint64_t key = all[x];
         if (!key) continue;
         const int j = x / S, s = x - j * S, n = s / Tg;
@@ -184,41 +196,59 @@ __global__ __launch_bounds__(CD_THREADS) void cd_refs_k(const int64_t* __restric
     }
 }
 
-// ---- reference vectors: one thread per (image, ref, n) -------------------------------------------------
+// The value one reference holds for `key`, an n-gram of order n + 1 of the caller's caption (0 when key is 0 or absent).
+// Block-wide: stages the reference's 4*Tg keys and values into rk / rv (RW_THREADS entries of LDS each), then every thread
+// scans the n-segment for its own key.  All threads must call it, and pass a barrier before the next call.
+template <typename V>
+__device__ __forceinline__ V rw_lookup(const uint64_t* __restrict__ ref_key, const V* __restrict__ ref_val, int Tg, uint64_t key,
+                                       int n, uint64_t* rk, V* rv) {
+    const int t = threadIdx.x;
+    if (t < RW_N * Tg) {
+        rk[t] = ref_key[t];
+        rv[t] = ref_val[t];
+    }
+    __syncthreads();
+    if (key)
+        for (int q = n * Tg; q < n * Tg + Tg; ++q)
+            if (rk[q] == key) return rv[q];
+    return 0;
+}
+
+// ---- CIDEr-D reference vectors: one thread per (image, ref, n) -------------------------------------------
 __global__ void cd_ref_vec_k(const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad, int n_img, int max_refs,
-                             int Tg, const uint64_t* __restrict__ rkey, double* __restrict__ rval, double* __restrict__ rnorm,
-                             CdDf df, double ref_docs) {
+                             int Tg, const uint64_t* __restrict__ rkey, const int32_t* __restrict__ rcnt,
+                             double* __restrict__ rval, double* __restrict__ rnorm, CdDf df, double ref_docs) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= (long)n_img * max_refs * CD_N) return;
-    const int n = (int)(g % CD_N);
-    const long ij = g / CD_N;
+    if (g >= (long)n_img * max_refs * RW_N) return;
+    const int n = (int)(g % RW_N);
+    const long ij = g / RW_N;
     const int i = (int)(ij / max_refs), j = (int)(ij % max_refs);
     if (img_bad[i] || j >= n_refs[i]) return;
     const double ref_len = log(ref_docs);
-    const long o = ij * CD_N * Tg + (long)n * Tg;
+    const long o = ij * RW_N * Tg + (long)n * Tg;
     double nrm = 0.0;
     for (int p = 0; p < Tg; ++p) {
         const uint64_t key = rkey[o + p];
         if (!key) continue;
-        const double v = rval[o + p] * (ref_len - cd_logdf(df, key));
-        rval[o + p] = v;
+        const double v = (double)rcnt[o + p] * (ref_len - cd_logdf(df, key));
+        rval[o + p] = v;   // only under a key: cd_hyp_k reads a value only where the key matches
         nrm += v * v;
     }
     rnorm[g] = sqrt(nrm);
 }
 
-// ---- hypotheses: one workgroup per score row -----------------------------------------------------------
-__global__ __launch_bounds__(CD_THREADS) void cd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
+// ---- CIDEr-D hypotheses: one workgroup per score row ---------------------------------------------------
+__global__ __launch_bounds__(RW_THREADS) void cd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
                                                        int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
                                                        int max_refs, int Tg, const uint64_t* __restrict__ rkey,
                                                        const double* __restrict__ rval, const double* __restrict__ rnorm,
-                                                       const int32_t* __restrict__ rlen, int vocab, CdDf df, double ref_docs,
+                                                       const int32_t* __restrict__ rwords, int vocab, CdDf df, double ref_docs,
                                                        double sigma, double* __restrict__ scores) {
-    __shared__ uint64_t skey[CD_THREADS], hk[CD_THREADS], rk[CD_THREADS];
-    __shared__ double hv[CD_THREADS], rv[CD_THREADS], contrib[CD_THREADS];
-    __shared__ double hnorm[CD_N], acc[CD_N];
+    __shared__ uint64_t skey[RW_THREADS], hk[RW_THREADS], rk[RW_THREADS];
+    __shared__ double hv[RW_THREADS], rv[RW_THREADS], contrib[RW_THREADS];
+    __shared__ double hnorm[RW_N], acc[RW_N];
     __shared__ int sw, sbad;
-    const int r = blockIdx.x, t = threadIdx.x, S = CD_N * T, Sg = CD_N * Tg;
+    const int r = blockIdx.x, t = threadIdx.x, Sg = RW_N * Tg;
     const int i = row_img[r];
     if (i < 0 || i >= n_img || img_bad[i]) {   // block-uniform
         if (t == 0) scores[r] = __builtin_nan("");
@@ -226,7 +256,7 @@ __global__ __launch_bounds__(CD_THREADS) void cd_hyp_k(const int64_t* __restrict
     }
     const int nr = n_refs[i];
     int tf, words, bad;
-    const uint64_t key = cd_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    const uint64_t key = rw_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
     if (bad) {
         if (t == 0) scores[r] = __builtin_nan("");
         return;
@@ -236,56 +266,46 @@ __global__ __launch_bounds__(CD_THREADS) void cd_hyp_k(const int64_t* __restrict
     hv[t] = key ? (double)tf * (ref_len - cd_logdf(df, key)) : 0.0;
     __syncthreads();
     double a = 0.0;
-    if (t < CD_N) {   // the reference's order: n-grams of one n in first-occurrence order
+    if (t < RW_N) {   // the reference's order: n-grams of one n in first-occurrence order
         double s = 0.0;
         for (int p = 0; p < T; ++p)
             if (hk[t * T + p]) s += hv[t * T + p] * hv[t * T + p];
         hnorm[t] = sqrt(s);
     }
     const int hlen = words > 1 ? words - 1 : 0;
-    const int n = t / (T > 0 ? T : 1);
+    const int n = t / T;
     for (int j = 0; j < nr; ++j) {
         const long ij = (long)i * max_refs + j;
-        if (t < Sg) {
-            rk[t] = rkey[ij * Sg + t];
-            rv[t] = rval[ij * Sg + t];
-        }
-        __syncthreads();
+        const double vr = rw_lookup(rkey + ij * Sg, rval + ij * Sg, Tg, key, n, rk, rv);
         if (key) {
-            double vr = 0.0;
-            for (int q = n * Tg; q < n * Tg + Tg; ++q)
-                if (rk[q] == key) {
-                    vr = rv[q];
-                    break;
-                }
             const double vh = hv[t];
             contrib[t] = (vr < vh ? vr : vh) * vr;
         }
         __syncthreads();
-        if (t < CD_N) {
+        if (t < RW_N) {
             double s = 0.0;
             for (int p = 0; p < T; ++p)
                 if (hk[t * T + p]) s += contrib[t * T + p];
-            const double nh = hnorm[t], nrf = rnorm[ij * CD_N + t];
+            const double nh = hnorm[t], nrf = rnorm[ij * RW_N + t];
             if (nh != 0.0 && nrf != 0.0) s /= nh * nrf;
-            const double delta = (double)(hlen - rlen[ij]);
+            const int rw = rwords[ij];
+            const double delta = (double)(hlen - (rw > 1 ? rw - 1 : 0));
             s *= exp(-(delta * delta) / (2.0 * sigma * sigma));
             a += s;
         }
         __syncthreads();
     }
-    if (t < CD_N) acc[t] = a;
+    if (t < RW_N) acc[t] = a;
     __syncthreads();
     if (t == 0) {
         double m = (((0.0 + acc[0]) + acc[1]) + acc[2]) + acc[3];
-        m /= (double)CD_N;
+        m /= (double)RW_N;
         m /= (double)nr;
         scores[r] = m * 10.0;
     }
-    (void)S;
 }
 
-// ---- table mode: build ------------------------------------------------------------------------------------
+// ---- CIDEr-D table mode: build ------------------------------------------------------------------------
 __global__ void cd_table_clear_k(uint64_t* __restrict__ keys, double* __restrict__ logdf, long slots) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (long)gridDim.x * blockDim.x) {
         keys[i] = 0;
@@ -297,11 +317,11 @@ __global__ void cd_table_insert_k(const int32_t* __restrict__ ids, const double*
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_entries) return;
     int len = 0;
-    while (len < CD_N && ids[e * CD_N + len] >= 0) ++len;
+    while (len < RW_N && ids[e * RW_N + len] >= 0) ++len;
     if (len == 0) return;
     uint64_t key = (uint64_t)len << 60;
-    for (int k = 0; k < CD_N; ++k) {
-        const int id = ids[e * CD_N + k];
+    for (int k = 0; k < RW_N; ++k) {
+        const int id = ids[e * RW_N + k];
         if (k < len) {
             if (id > vocab) return;   // can never match a caption of this vocabulary
             key |= (uint64_t)id << (15 * k);
@@ -313,84 +333,42 @@ __global__ void cd_table_insert_k(const int32_t* __restrict__ ids, const double*
     if (h >= 0) logdf[h] = log(fmax(1.0, counts[e]));
 }
 
-__global__ void cd_scst_k(const double* __restrict__ scores, int B, int T, double weight, int use_baseline, float* __restrict__ out,
-                          double* __restrict__ out64) {
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= (long)B * T) return;
-    const int b = (int)(g / T);
-    const double c = use_baseline ? scores[b] - scores[B + b] : scores[b];
-    // compute_reward: bleu4 * 0 + cider * weight + spice * 0 (the zero terms turn a -0 into +0)
-    const double v = (0.0 + c * weight) + 0.0;
-    if (out) out[g] = (float)v;
-    if (out64) out64[g] = v;
-}
-
-// ---- BLEU-D (cider/pyciderevalcap/bleuD, BleuD(4) with option 'closest') ---------------------------------------
-// Same captions, keys and limits as CIDEr-D.  Launches of one call: refs (cook every reference: first-occurrence keys, raw
-// term counts, word count), hyp (one workgroup per score row: clip every distinct n-gram of the row against the maximum
-// count over the image's references, reduce correct[4], pick the closest reference length, write the row's four scores and
-// its integer components) and, when asked for, corpus (the same formula over the sums of the components).  Everything before
-// the formula is integer counting, the formula is fp64 in one thread: bitwise reproducible, no atomics on global memory.
+// ---- BLEU-D ---------------------------------------------------------------------------------------------------
 #define BD_COMPS 10   // testlen, reflen, guess[4], correct[4]
 
 __device__ void bd_formula(const double* correct, const double* guess, double testlen, double reflen, double* bleu) {
     const double small = 1e-9, tiny = 1e-15;
     double p = 1.0;
-    for (int k = 0; k < CD_N; ++k) {
+    for (int k = 0; k < RW_N; ++k) {
         p *= (correct[k] + tiny) / (guess[k] + small);
         bleu[k] = pow(p, 1.0 / (double)(k + 1));
     }
     const double ratio = (testlen + tiny) / (reflen + small);
     if (ratio < 1.0) {
         const double bp = exp(1.0 - 1.0 / ratio);
-        for (int k = 0; k < CD_N; ++k) bleu[k] *= bp;
+        for (int k = 0; k < RW_N; ++k) bleu[k] *= bp;
     }
-}
-
-// one workgroup per image: per (image, ref) slot rkey[4*Tg] (first occurrences), rcnt[4*Tg] (term counts), rlen (words)
-__global__ __launch_bounds__(CD_THREADS) void bd_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
-                                                        int max_refs, int Tg, int vocab, uint64_t* __restrict__ rkey,
-                                                        int32_t* __restrict__ rcnt, int32_t* __restrict__ rlen,
-                                                        int32_t* __restrict__ img_bad) {
-    __shared__ uint64_t skey[CD_THREADS];
-    __shared__ int sw, sbad;
-    const int i = blockIdx.x, t = threadIdx.x, S = CD_N * Tg;
-    const int nr = n_refs[i];
-    int bad_img = (nr < 1 || nr > max_refs);
-    const int nrc = bad_img ? 0 : nr;
-    for (int j = 0; j < nrc; ++j) {
-        int tf, words, bad;
-        const uint64_t key = cd_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
-        const long o = ((long)i * max_refs + j) * S;
-        if (t < S) {
-            rkey[o + t] = key;
-            rcnt[o + t] = tf;
-        }
-        if (t == 0) rlen[(long)i * max_refs + j] = words;
-        bad_img |= bad;
-    }
-    if (t == 0) img_bad[i] = bad_img;
 }
 
 // one workgroup per score row.  comps: n_rows x BD_COMPS (testlen = -1 marks a row that scores NaN); ucomps: NULL or the
 // caller's copy of it (zeros for a NaN row).
-__global__ __launch_bounds__(CD_THREADS) void bd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
+__global__ __launch_bounds__(RW_THREADS) void bd_hyp_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
                                                        int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
                                                        int max_refs, int Tg, const uint64_t* __restrict__ rkey,
-                                                       const int32_t* __restrict__ rcnt, const int32_t* __restrict__ rlen, int vocab,
+                                                       const int32_t* __restrict__ rcnt, const int32_t* __restrict__ rwords, int vocab,
                                                        double* __restrict__ scores, int32_t* __restrict__ comps,
                                                        int32_t* __restrict__ ucomps) {
-    __shared__ uint64_t skey[CD_THREADS], rk[CD_THREADS];
-    __shared__ int rc[CD_THREADS], clip[CD_THREADS];
-    __shared__ int correct[CD_N];
+    __shared__ uint64_t skey[RW_THREADS], rk[RW_THREADS];
+    __shared__ int rc[RW_THREADS], clip[RW_THREADS];
+    __shared__ int correct[RW_N];
     __shared__ int sw, sbad;
-    const int r = blockIdx.x, t = threadIdx.x, Sg = CD_N * Tg;
+    const int r = blockIdx.x, t = threadIdx.x, Sg = RW_N * Tg;
     const int i = row_img[r];
     int tf = 0, words = 0, bad = (i < 0 || i >= n_img || img_bad[i]);   // block-uniform
     uint64_t key = 0;
-    if (!bad) key = cd_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    if (!bad) key = rw_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
     if (bad) {
-        if (t < CD_N) scores[(long)r * CD_N + t] = __builtin_nan("");
+        if (t < RW_N) scores[(long)r * RW_N + t] = __builtin_nan("");
         if (t < BD_COMPS) {
             comps[(long)r * BD_COMPS + t] = t == 0 ? -1 : 0;
             if (ucomps) ucomps[(long)r * BD_COMPS + t] = 0;
@@ -402,32 +380,21 @@ __global__ __launch_bounds__(CD_THREADS) void bd_hyp_k(const int64_t* __restrict
     int maxc = 0;
     for (int j = 0; j < nr; ++j) {
         const long ij = (long)i * max_refs + j;
-        if (t < Sg) {
-            rk[t] = rkey[ij * Sg + t];
-            rc[t] = rcnt[ij * Sg + t];
-        }
-        __syncthreads();
-        if (key) {
-            for (int q = n * Tg; q < n * Tg + Tg; ++q)
-                if (rk[q] == key) {
-                    maxc = max(maxc, rc[q]);
-                    break;
-                }
-        }
+        maxc = max(maxc, rw_lookup(rkey + ij * Sg, rcnt + ij * Sg, Tg, key, n, rk, rc));
         __syncthreads();
     }
     clip[t] = key ? min(tf, maxc) : 0;
     __syncthreads();
-    if (t < CD_N) {
+    if (t < RW_N) {
         int s = 0;
         for (int p = 0; p < T; ++p) s += clip[t * T + p];
         correct[t] = s;
     }
     __syncthreads();
     if (t == 0) {
-        int reflen = rlen[(long)i * max_refs], best = abs(reflen - words);   // min((|l - testlen|, l)): a tie takes the shorter
+        int reflen = rwords[(long)i * max_refs], best = abs(reflen - words);   // min((|l - testlen|, l)): a tie takes the shorter
         for (int j = 1; j < nr; ++j) {
-            const int l = rlen[(long)i * max_refs + j], d = abs(l - words);
+            const int l = rwords[(long)i * max_refs + j], d = abs(l - words);
             if (d < best || (d == best && l < reflen)) {
                 best = d;
                 reflen = l;
@@ -436,15 +403,15 @@ __global__ __launch_bounds__(CD_THREADS) void bd_hyp_k(const int64_t* __restrict
         int c[BD_COMPS];
         c[0] = words;
         c[1] = reflen;
-        double cor[CD_N], gue[CD_N], bleu[CD_N];
-        for (int k = 0; k < CD_N; ++k) {
+        double cor[RW_N], gue[RW_N], bleu[RW_N];
+        for (int k = 0; k < RW_N; ++k) {
             c[2 + k] = words - k > 0 ? words - k : 0;
-            c[2 + CD_N + k] = correct[k];
+            c[2 + RW_N + k] = correct[k];
             gue[k] = (double)c[2 + k];
             cor[k] = (double)correct[k];
         }
         bd_formula(cor, gue, (double)words, (double)reflen, bleu);
-        for (int k = 0; k < CD_N; ++k) scores[(long)r * CD_N + k] = bleu[k];
+        for (int k = 0; k < RW_N; ++k) scores[(long)r * RW_N + k] = bleu[k];
         for (int k = 0; k < BD_COMPS; ++k) {
             comps[(long)r * BD_COMPS + k] = c[k];
             if (ucomps) ucomps[(long)r * BD_COMPS + k] = c[k];
@@ -453,17 +420,17 @@ __global__ __launch_bounds__(CD_THREADS) void bd_hyp_k(const int64_t* __restrict
 }
 
 // one workgroup: the corpus-level four from the integer sums of the rows' components (NaN rows left out)
-__global__ __launch_bounds__(CD_THREADS) void bd_corpus_k(const int32_t* __restrict__ comps, int n_rows, double* __restrict__ corpus) {
-    __shared__ long long part[CD_THREADS];
+__global__ __launch_bounds__(RW_THREADS) void bd_corpus_k(const int32_t* __restrict__ comps, int n_rows, double* __restrict__ corpus) {
+    __shared__ long long part[RW_THREADS];
     __shared__ long long tot[BD_COMPS];
     const int t = threadIdx.x;
     for (int k = 0; k < BD_COMPS; ++k) {
         long long s = 0;
-        for (int r = t; r < n_rows; r += CD_THREADS)
+        for (int r = t; r < n_rows; r += RW_THREADS)
             if (comps[(long)r * BD_COMPS] >= 0) s += comps[(long)r * BD_COMPS + k];
         part[t] = s;
         __syncthreads();
-        for (int w = CD_THREADS / 2; w > 0; w >>= 1) {
+        for (int w = RW_THREADS / 2; w > 0; w >>= 1) {
             if (t < w) part[t] += part[t + w];
             __syncthreads();
         }
@@ -471,27 +438,28 @@ __global__ __launch_bounds__(CD_THREADS) void bd_corpus_k(const int32_t* __restr
         __syncthreads();
     }
     if (t == 0) {
-        double cor[CD_N], gue[CD_N], bleu[CD_N];
-        for (int k = 0; k < CD_N; ++k) {
+        double cor[RW_N], gue[RW_N], bleu[RW_N];
+        for (int k = 0; k < RW_N; ++k) {
             gue[k] = (double)tot[2 + k];
-            cor[k] = (double)tot[2 + CD_N + k];
+            cor[k] = (double)tot[2 + RW_N + k];
         }
         bd_formula(cor, gue, (double)tot[0], (double)tot[1], bleu);
-        for (int k = 0; k < CD_N; ++k) corpus[k] = bleu[k];
+        for (int k = 0; k < RW_N; ++k) corpus[k] = bleu[k];
     }
 }
 
-// compute_reward's mix: ((bleu4 * w_b) + (cider * w_c)) + spice * 0, each product and sum rounded on its own
-__global__ void bd_mix_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu, double bleu4_weight,
-                         int B, int T, int use_baseline, float* __restrict__ out, double* __restrict__ out64) {
+// ---- the reward: compute_reward's mix ((bleu4 * w_b) + (cider * w_c)) + spice * 0, each product and sum rounded on its own;
+// a NULL scorer is the 0 * weight the reference adds (which also turns a -0 into +0)
+__global__ void rw_reward_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu,
+                            double bleu4_weight, int B, int T, int use_baseline, float* __restrict__ out, double* __restrict__ out64) {
 #pragma clang fp contract(off)
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long)B * T) return;
     const int b = (int)(g / T);
     double sb = 0.0, sc = 0.0;
     if (bleu) {
-        sb = bleu[(long)b * CD_N + 3];
-        if (use_baseline) sb = sb - bleu[(long)(B + b) * CD_N + 3];
+        sb = bleu[(long)b * RW_N + 3];
+        if (use_baseline) sb = sb - bleu[(long)(B + b) * RW_N + 3];
     }
     if (cider) {
         sc = cider[b];
@@ -509,43 +477,67 @@ const size_t kAlign = 256;
 size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
 long corpus_slots(int n_img, int max_refs, int T_gt) {
-    const long distinct = (long)n_img * max_refs * CD_N * T_gt;   // an upper bound of the distinct reference n-grams
+    const long distinct = (long)n_img * max_refs * RW_N * T_gt;   // an upper bound of the distinct reference n-grams
     long s = 1024;
     while (s < 2 * distinct) s <<= 1;
     return s;
 }
 
 bool dims_ok(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
-    return n_rows >= 1 && n_img >= 1 && T_res >= 1 && T_res <= CD_MAX_T && T_gt >= 1 && T_gt <= CD_MAX_T && max_refs >= 1 &&
-           max_refs <= CD_MAX_REFS;
+    return n_rows >= 1 && n_img >= 1 && T_res >= 1 && T_res <= RW_MAX_T && T_gt >= 1 && T_gt <= RW_MAX_T && max_refs >= 1 &&
+           max_refs <= RW_MAX_REFS;
 }
 
+// The workspace of one call: the cooked references (what rw_refs_k writes), then what the scorer adds.
+enum Scorer { CIDER_TABLE, CIDER_CORPUS, BLEU };
 struct Layout {
-    size_t dkeys, dcnt, rkey, rval, rnorm, rlen, bad, total;
+    size_t rkey, rcnt, rwords, bad;      // shared
+    size_t dkeys, dcnt, rval, rnorm;     // CIDEr-D (the df table in corpus mode only)
+    size_t comps;                        // BLEU-D
+    size_t total;
     long dslots;
 };
-Layout layout(int n_rows, int T_res, int n_img, int max_refs, int T_gt, int corpus) {
-    (void)n_rows;
-    (void)T_res;
+Layout layout(Scorer scorer, int n_rows, int n_img, int max_refs, int T_gt) {
     Layout L{};
     const size_t nref = (size_t)n_img * max_refs;
     size_t o = 0;
-    L.dslots = corpus ? corpus_slots(n_img, max_refs, T_gt) : 0;
-    L.dkeys = o; o = up(o + (size_t)L.dslots * 8);
-    L.dcnt = o;  o = up(o + (size_t)L.dslots * 4);
-    L.rkey = o;  o = up(o + nref * CD_N * T_gt * 8);
-    L.rval = o;  o = up(o + nref * CD_N * T_gt * 8);
-    L.rnorm = o; o = up(o + nref * CD_N * 8);
-    L.rlen = o;  o = up(o + nref * 4);
-    L.bad = o;   o = up(o + (size_t)n_img * 4);
+    L.rkey = o;   o = up(o + nref * RW_N * T_gt * 8);
+    L.rcnt = o;   o = up(o + nref * RW_N * T_gt * 4);
+    L.rwords = o; o = up(o + nref * 4);
+    L.bad = o;    o = up(o + (size_t)n_img * 4);
+    if (scorer == BLEU) {
+        L.comps = o; o = up(o + (size_t)n_rows * BD_COMPS * 4);
+    } else {
+        L.dslots = scorer == CIDER_CORPUS ? corpus_slots(n_img, max_refs, T_gt) : 0;
+        L.dkeys = o; o = up(o + (size_t)L.dslots * 8);
+        L.dcnt = o;  o = up(o + (size_t)L.dslots * 4);
+        L.rval = o;  o = up(o + nref * RW_N * T_gt * 8);
+        L.rnorm = o; o = up(o + nref * RW_N * 8);
+    }
     L.total = o;
     return L;
+}
+
+// The checks rfn_ciderd_score and rfn_bleud_score share, in their precedence; fills *L when it returns RFN_OK.
+// extra_shape_ok: the caller's own shape conditions.
+int check_score_args(Scorer scorer, const void* res, int n_rows, int T_res, const void* row_img, const void* gts, const void* n_refs,
+                     int n_img, int max_refs, int T_gt, int vocab, bool extra_shape_ok, const void* scores, const void* ws,
+                     size_t ws_bytes, Layout* L) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > RW_MAX_ID || !extra_shape_ok) return RFN_ERR_SHAPE;
+    if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
+    *L = layout(scorer, n_rows, n_img, max_refs, T_gt);
+    return ws_bytes < L->total ? RFN_ERR_WORKSPACE : RFN_OK;
 }
 }  // namespace
 
 extern "C" size_t rfn_ciderd_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt, int corpus) {
     if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
-    return layout(n_rows, T_res, n_img, max_refs, T_gt, corpus).total;
+    return layout(corpus ? CIDER_CORPUS : CIDER_TABLE, n_rows, n_img, max_refs, T_gt).total;
+}
+
+extern "C" size_t rfn_bleud_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
+    return layout(BLEU, n_rows, n_img, max_refs, T_gt).total;
 }
 
 extern "C" size_t rfn_ciderd_table_bytes(int64_t slots) {
@@ -555,7 +547,7 @@ extern "C" size_t rfn_ciderd_table_bytes(int64_t slots) {
 
 extern "C" int rfn_ciderd_table_build(const int32_t* ngram_ids, const double* counts, int64_t n_entries, int vocab, void* table,
                                       int64_t slots, void* stream) {
-    if (n_entries < 0 || slots < 2 || (slots & (slots - 1)) || n_entries > slots / 2 || vocab < 0 || vocab > CD_MAX_ID)
+    if (n_entries < 0 || slots < 2 || (slots & (slots - 1)) || n_entries > slots / 2 || vocab < 0 || vocab > RW_MAX_ID)
         return RFN_ERR_SHAPE;
     if (!table || (n_entries > 0 && (!ngram_ids || !counts)) || !rfn_aligned16(table)) return RFN_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -574,106 +566,70 @@ extern "C" int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const
                                 const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots,
                                 double ref_docs, int vocab, double sigma, double* scores, void* ws, size_t ws_bytes,
                                 void* stream) {
-    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > CD_MAX_ID) return RFN_ERR_SHAPE;
-    const int corpus = table == nullptr;
-    if (!corpus && (slots < 2 || (slots & (slots - 1)) || !(ref_docs > 0.0))) return RFN_ERR_SHAPE;
-    if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
-    const Layout L = layout(n_rows, T_res, n_img, max_refs, T_gt, corpus);
-    if (ws_bytes < L.total) return RFN_ERR_WORKSPACE;
+    const bool corpus = table == nullptr;
+    const bool table_ok = corpus || (slots >= 2 && !(slots & (slots - 1)) && ref_docs > 0.0);
+    Layout L;
+    const int rc = check_score_args(corpus ? CIDER_CORPUS : CIDER_TABLE, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs,
+                                    T_gt, vocab, table_ok, scores, ws, ws_bytes, &L);
+    if (rc != RFN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
-    uint64_t* dkeys = corpus ? (uint64_t*)(w + L.dkeys) : nullptr;
-    uint32_t* dcnt = corpus ? (uint32_t*)(w + L.dcnt) : nullptr;
     uint64_t* rkey = (uint64_t*)(w + L.rkey);
+    int32_t* rcnt = (int32_t*)(w + L.rcnt);
+    int32_t* rwords = (int32_t*)(w + L.rwords);
+    int32_t* bad = (int32_t*)(w + L.bad);
     double* rval = (double*)(w + L.rval);
     double* rnorm = (double*)(w + L.rnorm);
-    int32_t* rlen = (int32_t*)(w + L.rlen);
-    int32_t* bad = (int32_t*)(w + L.bad);
     CdDf df;
     if (corpus) {
-        df.keys = dkeys;
-        df.cnt = dcnt;
-        df.logdf = nullptr;
-        df.slots = L.dslots;
+        uint64_t* dkeys = (uint64_t*)(w + L.dkeys);
+        uint32_t* dcnt = (uint32_t*)(w + L.dcnt);
+        df = CdDf{dkeys, dcnt, nullptr, L.dslots};
         ref_docs = (double)n_rows;   // compute_reward: ref_len = log(len(crefs)), one entry per score row
         cd_clear_k<<<(int)std::min<long>(rfn_cdiv(L.dslots, 256), 4096), 256, 0, st>>>(dkeys, dcnt, L.dslots);
         RFN_CHECK_LAUNCH();
+        const size_t lds = (size_t)max_refs * RW_N * T_gt * 8;   // <= 64 KiB
+        if (lds > 48 * 1024)
+            hipFuncSetAttribute((const void*)rw_refs_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, row_img, n_rows,
+                                                        dkeys, dcnt, L.dslots);
     } else {
-        df.keys = (const uint64_t*)table;
-        df.cnt = nullptr;
-        df.logdf = (const double*)((const uint64_t*)table + slots);
-        df.slots = slots;
+        df = CdDf{(const uint64_t*)table, nullptr, (const double*)((const uint64_t*)table + slots), slots};
+        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, nullptr, 0, nullptr,
+                                                       nullptr, 0);
     }
-    const size_t lds = (size_t)max_refs * CD_N * T_gt * 8;   // <= 64 KiB
-    if (lds > 48 * 1024)
-        hipFuncSetAttribute((const void*)cd_refs_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    cd_refs_k<<<n_img, CD_THREADS, lds, st>>>(gts, n_refs, max_refs, T_gt, row_img, n_rows, vocab, rkey, rval, rlen, bad, dkeys,
-                                              dcnt, L.dslots);
     RFN_CHECK_LAUNCH();
-    const long nvec = (long)n_img * max_refs * CD_N;
-    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rval, rnorm, df, ref_docs);
+    const long nvec = (long)n_img * max_refs * RW_N;
+    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rcnt, rval, rnorm, df, ref_docs);
     RFN_CHECK_LAUNCH();
-    cd_hyp_k<<<n_rows, CD_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rval, rnorm, rlen, vocab,
+    cd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rval, rnorm, rwords, vocab,
                                             df, ref_docs, sigma, scores);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
 
-extern "C" int rfn_scst_reward(const double* scores, int B, int T, double weight, int use_baseline, float* out, double* out64,
-                               void* stream) {
-    if (B < 1 || T < 1) return RFN_ERR_SHAPE;
-    if (!scores || (!out && !out64)) return RFN_ERR_ARG;
-    const long n = (long)B * T;
-    cd_scst_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(scores, B, T, weight, use_baseline, out, out64);
-    RFN_CHECK_LAUNCH();
-    return RFN_OK;
-}
-
-// ---- BLEU-D host side ------------------------------------------------------------------------------------
-namespace {
-struct BleuLayout {
-    size_t rkey, rcnt, rlen, bad, comps, total;
-};
-BleuLayout bleu_layout(int n_rows, int n_img, int max_refs, int T_gt) {
-    BleuLayout L{};
-    const size_t nref = (size_t)n_img * max_refs;
-    size_t o = 0;
-    L.rkey = o;  o = up(o + nref * CD_N * T_gt * 8);
-    L.rcnt = o;  o = up(o + nref * CD_N * T_gt * 4);
-    L.rlen = o;  o = up(o + nref * 4);
-    L.bad = o;   o = up(o + (size_t)n_img * 4);
-    L.comps = o; o = up(o + (size_t)n_rows * BD_COMPS * 4);
-    L.total = o;
-    return L;
-}
-}  // namespace
-
-extern "C" size_t rfn_bleud_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
-    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
-    return bleu_layout(n_rows, n_img, max_refs, T_gt).total;
-}
-
 extern "C" int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
                                const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, double* scores, int32_t* comps,
                                double* corpus, void* ws, size_t ws_bytes, void* stream) {
-    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > CD_MAX_ID) return RFN_ERR_SHAPE;
-    if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
-    const BleuLayout L = bleu_layout(n_rows, n_img, max_refs, T_gt);
-    if (ws_bytes < L.total) return RFN_ERR_WORKSPACE;
+    Layout L;
+    const int rc = check_score_args(BLEU, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, vocab, true, scores, ws,
+                                    ws_bytes, &L);
+    if (rc != RFN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
     uint64_t* rkey = (uint64_t*)(w + L.rkey);
     int32_t* rcnt = (int32_t*)(w + L.rcnt);
-    int32_t* rlen = (int32_t*)(w + L.rlen);
+    int32_t* rwords = (int32_t*)(w + L.rwords);
     int32_t* bad = (int32_t*)(w + L.bad);
     int32_t* wcomps = (int32_t*)(w + L.comps);
-    bd_refs_k<<<n_img, CD_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rlen, bad);
+    rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, nullptr, 0, nullptr,
+                                                   nullptr, 0);
     RFN_CHECK_LAUNCH();
-    bd_hyp_k<<<n_rows, CD_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rcnt, rlen, vocab, scores,
+    bd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rcnt, rwords, vocab, scores,
                                             wcomps, comps);
     RFN_CHECK_LAUNCH();
     if (corpus) {
-        bd_corpus_k<<<1, CD_THREADS, 0, st>>>(wcomps, n_rows, corpus);
+        bd_corpus_k<<<1, RW_THREADS, 0, st>>>(wcomps, n_rows, corpus);
         RFN_CHECK_LAUNCH();
     }
     return RFN_OK;
@@ -684,7 +640,13 @@ extern "C" int rfn_scst_reward_mix(const double* cider, double cider_weight, con
     if (B < 1 || T < 1) return RFN_ERR_SHAPE;
     if ((!cider && !bleu) || (!out && !out64)) return RFN_ERR_ARG;
     const long n = (long)B * T;
-    bd_mix_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, T, use_baseline, out, out64);
+    rw_reward_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, T, use_baseline, out,
+                                                                   out64);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
+}
+
+extern "C" int rfn_scst_reward(const double* scores, int B, int T, double weight, int use_baseline, float* out, double* out64,
+                               void* stream) {
+    return rfn_scst_reward_mix(scores, weight, nullptr, 0.0, B, T, use_baseline, out, out64, stream);
 }

@@ -33,16 +33,46 @@ def _ref_docs_of(mode):
     raise ValueError('df mode %r names none of coco-all / coco-train / coco-val: its document count is unknown' % mode)
 
 
-class CiderD:
+class _IdScorer:
+    """What CiderD and BleuD share: the head of score_ids and the workspace."""
+    _NAME = None
+    _ws = None
+
+    def _inputs(self, res, row_img, gts, n_refs):
+        """score_ids' arguments on res's device, in the types the C entry reads -> dev, res, row_img, gts, n_refs and the
+        sizes (n_rows, T, n_img, R, Tg)."""
+        dev = res.device
+        if dev.type != 'cuda':
+            raise N.RfnError('res must live on the GPU: the reward has no CPU fallback')
+        res = res.to(torch.int64).contiguous()
+        gts = gts.to(dev, torch.int64).contiguous()
+        row_img = row_img.to(dev, torch.int32).contiguous()
+        n_refs = n_refs.to(dev, torch.int32).contiguous()
+        n_rows, T = res.shape
+        n_img, R, Tg = gts.shape
+        if row_img.numel() != n_rows or n_refs.numel() != n_img:
+            raise ValueError('row_img needs one entry per row and n_refs one per image')
+        return dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg)
+
+    def _workspace(self, dev, nbytes):
+        """nbytes: the C entry's workspace query for the call's sizes (0 outside the limits)."""
+        if nbytes == 0:
+            raise ValueError('%s limits: 1 <= T <= %d, 1 <= refs per image <= %d' % (self._NAME, MAX_T, MAX_REFS))
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        return self._ws
+
+
+class CiderD(_IdScorer):
     """CIDEr-D scorer.  df: 'corpus', a dict {tuple of id strings: df}, a pickle path, or a reference mode name such as
     'coco-train-idxs' (read from data/<name>.p like the reference).  df_mode names the document count of a table
     (defaults to the name / file name of df)."""
+    _NAME = 'CIDEr-D'
 
     def __init__(self, n=4, sigma=6.0, df='corpus', df_mode=None):
         if n != 4:
             raise NotImplementedError('only n = 4 (CiderD\'s default) is implemented')
         self._n, self._sigma = n, float(sigma)
-        self._ws = None
         self._tables = {}
         self._table_src = None
         if isinstance(df, str) and df == 'corpus':
@@ -92,32 +122,14 @@ class CiderD:
             self._tables[key] = table
         return self._tables[key]
 
-    def _workspace(self, dev, nbytes):
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self._ws
-
     # -- scoring ---------------------------------------------------------------------------------------------------
     def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None):
         """res (N, T) int64 ids, row_img (N,) image of each row, gts (n_img, R, Tg) int64 references padded to R,
         n_refs (n_img,) references per image; all on one GPU.  -> (N,) float64 scores on the device (NaN for a row whose
         caption or references hold an id outside [0, vocab])."""
-        dev = res.device
-        if dev.type != 'cuda':
-            raise N.RfnError('res must live on the GPU: the reward has no CPU fallback')
-        res = res.to(torch.int64).contiguous()
-        gts = gts.to(dev, torch.int64).contiguous()
-        row_img = row_img.to(dev, torch.int32).contiguous()
-        n_refs = n_refs.to(dev, torch.int32).contiguous()
-        n_rows, T = res.shape
-        n_img, R, Tg = gts.shape
-        if row_img.numel() != n_rows or n_refs.numel() != n_img:
-            raise ValueError('row_img needs one entry per row and n_refs one per image')
+        dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg) = self._inputs(res, row_img, gts, n_refs)
         table = self._table(dev)
-        nbytes = N.lib.rfn_ciderd_ws_bytes(n_rows, T, n_img, R, Tg, int(table is None))
-        if nbytes == 0:
-            raise ValueError('CIDEr-D limits: 1 <= T <= %d, 1 <= refs per image <= %d' % (MAX_T, MAX_REFS))
-        ws = self._workspace(dev, nbytes)
+        ws = self._workspace(dev, N.lib.rfn_ciderd_ws_bytes(n_rows, T, n_img, R, Tg, int(table is None)))
         if out is None:
             out = torch.empty(n_rows, dtype=torch.float64, device=dev)
         N.check(N.lib.rfn_ciderd_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(),
@@ -139,40 +151,22 @@ class CiderD:
         return 'CIDEr-D'
 
 
-class BleuD:
+class BleuD(_IdScorer):
     """BLEU-D scorer: the reference's BleuD(4), whose rows take the closest reference length."""
+    _NAME = 'BLEU-D'
 
     def __init__(self, n=4):
         if n != 4:
             raise NotImplementedError('only n = 4 (compute_reward\'s BleuD(4)) is implemented')
         self._n = n
-        self._ws = None
-
-    def _workspace(self, dev, nbytes):
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        return self._ws
 
     def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, comps=None, corpus=None):
         """Arguments as CiderD.score_ids.  -> (N, 4) float64 BLEU-1..4 per row on the device (NaN in all four for a row whose
         caption or references hold an id outside [0, vocab]).  comps: optional (N, 10) int32 device tensor that receives
         testlen, reflen, guess[4], correct[4] of every row; corpus: optional (4,) float64 device tensor that receives the
         corpus-level scores (one more small launch)."""
-        dev = res.device
-        if dev.type != 'cuda':
-            raise N.RfnError('res must live on the GPU: the reward has no CPU fallback')
-        res = res.to(torch.int64).contiguous()
-        gts = gts.to(dev, torch.int64).contiguous()
-        row_img = row_img.to(dev, torch.int32).contiguous()
-        n_refs = n_refs.to(dev, torch.int32).contiguous()
-        n_rows, T = res.shape
-        n_img, R, Tg = gts.shape
-        if row_img.numel() != n_rows or n_refs.numel() != n_img:
-            raise ValueError('row_img needs one entry per row and n_refs one per image')
-        nbytes = N.lib.rfn_bleud_ws_bytes(n_rows, T, n_img, R, Tg)
-        if nbytes == 0:
-            raise ValueError('BLEU-D limits: 1 <= T <= %d, 1 <= refs per image <= %d' % (MAX_T, MAX_REFS))
-        ws = self._workspace(dev, nbytes)
+        dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg) = self._inputs(res, row_img, gts, n_refs)
+        ws = self._workspace(dev, N.lib.rfn_bleud_ws_bytes(n_rows, T, n_img, R, Tg))
         if out is None:
             out = torch.empty(n_rows, 4, dtype=torch.float64, device=dev)
         for t, name, shape, dtype in ((out, 'out', (n_rows, 4), torch.float64), (comps, 'comps', (n_rows, 10), torch.int32),
@@ -290,15 +284,11 @@ def scst_reward(scorer, gen_result, greedy_res, gts, n_refs, seq_per_img, cider_
     res = torch.cat([gen_result.to(torch.int64), greedy_res.to(dev, torch.int64)], 0)
     row_img = _scst_row_img(B, seq_per_img, dev)
     scores = None if scorer is None else scorer.score_ids(res, row_img, gts, n_refs)
+    bleu = None if bleu_scorer is None else bleu_scorer.score_ids(res, row_img, gts, n_refs)
     out = torch.empty(B, T, dtype=torch.float32, device=dev)
-    if bleu_scorer is None:
-        N.check(N.lib.rfn_scst_reward(scores.data_ptr(), B, T, C.c_double(cider_weight), int(bool(use_baseline)),
-                                      out.data_ptr(), N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward')
-        return out
-    bleu = bleu_scorer.score_ids(res, row_img, gts, n_refs)
-    N.check(N.lib.rfn_scst_reward_mix(N.ptr(scores), C.c_double(cider_weight), bleu.data_ptr(), C.c_double(bleu4_weight), B, T,
-                                      int(bool(use_baseline)), out.data_ptr(), N.ptr(out64), N.stream_ptr()),
-            'rfn_scst_reward_mix')
+    N.check(N.lib.rfn_scst_reward_mix(N.ptr(scores), C.c_double(cider_weight), N.ptr(bleu),
+                                      C.c_double(0.0 if bleu is None else bleu4_weight), B, T, int(bool(use_baseline)),
+                                      out.data_ptr(), N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward_mix')
     return out
 
 

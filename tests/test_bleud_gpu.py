@@ -9,8 +9,8 @@ import torch
 
 import bleud_cpu as BCPU
 import ciderd_cpu as CPU
+from reward_cases import device_inputs, drop_in_data, fuzz_case, small_model, string_dicts
 from test_bleud_cpu import TIERS, golden
-from test_ciderd_gpu import small_model
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +22,6 @@ def close(got, want, what):
     rel = np.abs(got - want) / np.abs(want)
     print('%s: max relative error %.3g over %d values (smallest |want| %.3g)' % (what, rel.max(), rel.size, np.abs(want).min()))
     np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
-
-
-def device_inputs(g, dev):
-    B, spi = int(g['B']), int(g['seq_per_img'])
-    return (B, spi, torch.from_numpy(g['res']).to(dev), torch.from_numpy(CPU.scst_rows(B, spi)).to(dev),
-            torch.from_numpy(g['gts']).to(dev), torch.from_numpy(g['n_refs']).to(dev))
 
 
 @pytest.mark.parametrize('name', TIERS)
@@ -89,12 +83,8 @@ def test_reference_interface_compute_score(dev):
     from recurrent_fusion_network_amd import rewards as RW
     for name in ('spi5', 'near_spi5'):
         g = golden(name)
-        B, spi = int(g['B']), int(g['seq_per_img'])
-
-        def s(row):
-            return ' '.join(str(int(x)) for x in CPU.caption(row))
-        res = [{'image_id': r, 'caption': [s(g['res'][r])]} for r in range(2 * B)]
-        gts = {r: [s(g['gts'][(r % B) // spi][j]) for j in range(int(g['n_refs'][(r % B) // spi]))] for r in range(2 * B)}
+        B = int(g['B'])
+        gts, res = string_dicts(g)
         corpus, rows = RW.BleuD(4).compute_score(gts, res)
         assert isinstance(corpus, list) and len(corpus) == 4 and isinstance(rows, list) and len(rows) == 4
         assert all(isinstance(r, list) and len(r) == 2 * B for r in rows)
@@ -108,27 +98,8 @@ def test_reference_interface_compute_score(dev):
 @pytest.mark.parametrize('seed', range(24))
 def test_fuzz_against_cpu_restatement(seed, dev):
     from recurrent_fusion_network_amd import rewards as RW
-    rng = np.random.default_rng(2000 + seed)
-    T, Tg = int(rng.integers(1, 65)), int(rng.integers(1, 65))
-    vocab = int(rng.choice([5, 50, 9487, 32767]))
-    n_img = int(rng.integers(1, 9))
-    spi = int(rng.integers(1, 5))
-    max_refs = int(rng.integers(1, 33))
-    n_refs = rng.integers(1, max_refs + 1, n_img).astype(np.int32)
-    n_refs[0] = max_refs
-    pools = [rng.integers(0, vocab + 1, int(rng.integers(2, 12))) for _ in range(n_img)]   # small: repeats and matches occur
-
-    def rows(n, width, pool):
-        out = rng.choice(pool, (n, width)).astype(np.int64)
-        cut = rng.random(n) < 0.6       # the others keep whatever ids the pool gives (with or without a 0)
-        out[cut, rng.integers(0, width, int(cut.sum()))] = 0
-        return out
-    gts = np.zeros((n_img, max_refs, Tg), dtype=np.int64)
-    for i in range(n_img):
-        gts[i, :n_refs[i]] = rows(int(n_refs[i]), Tg, pools[i])
-    B = n_img * spi
-    res = np.concatenate([rows(1, T, pools[(r % B) // spi]) for r in range(2 * B)])
-    row_img = CPU.scst_rows(B, spi)
+    f = fuzz_case(2000, seed)
+    T, Tg, vocab, max_refs, B, res, row_img, gts, n_refs = f.T, f.Tg, f.vocab, f.max_refs, f.B, f.res, f.row_img, f.gts, f.n_refs
     want, want_comps, want_corpus = BCPU.score_rows(res, row_img, gts, n_refs)
     comps = torch.empty(2 * B, 10, dtype=torch.int32, device=dev)
     corpus = torch.empty(4, dtype=torch.float64, device=dev)
@@ -206,11 +177,7 @@ def test_out_of_range_id_scores_nan_only_on_its_row(dev):
 def test_get_rewards_drop_in_and_full_self_critical_step(dev):
     from recurrent_fusion_network_amd import rewards as RW
     R, cfg, model, fc, att, top = small_model(dev)
-    rng = np.random.default_rng(3)
-    B, spi = 8, 2
-    data = {'gts': [rng.integers(1, 40, (int(k), cfg.seq_length + 2)) for k in (5, 3, 7, 1)]}
-    for a in data['gts']:
-        a[:, -2:] = 0
+    data, B, spi = drop_in_data(cfg)
     opt = types.SimpleNamespace(bleu4_weight=0.5, spice_weight=0, cider_weight=1.0, use_baseline=1)
     model.eval()
     with torch.no_grad():

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import ciderd_cpu as CPU
+from reward_cases import device_inputs, drop_in_data, fuzz_case, small_model, string_dicts
 from test_ciderd_cpu import TIERS, golden
 
 pytestmark = pytest.mark.gpu
@@ -29,11 +30,9 @@ def close(got, want):
 def test_golden_tiers_scores_and_rewards(name, dev):
     from recurrent_fusion_network_amd import rewards as RW
     g = golden(name)
-    B, spi = int(g['B']), int(g['seq_per_img'])
+    B, spi, res, row_img, gts, n_refs = device_inputs(g, dev)
     sc = scorer_for(g, name)
-    res = torch.from_numpy(g['res']).to(dev)
-    gts, n_refs = torch.from_numpy(g['gts']).to(dev), torch.from_numpy(g['n_refs']).to(dev)
-    s = sc.score_ids(res, torch.from_numpy(CPU.scst_rows(B, spi)), gts, n_refs, vocab=int(g['vocab']))
+    s = sc.score_ids(res, row_img, gts, n_refs, vocab=int(g['vocab']))
     close(s.cpu().numpy(), g['scores'])
     out64 = torch.empty(B, res.shape[1], dtype=torch.float64, device=dev)
     r32 = RW.scst_reward(sc, res[:B], res[B:], gts, n_refs, spi, out64=out64)
@@ -48,12 +47,7 @@ def test_reference_interface_compute_score(dev):
     """CiderD.compute_score on compute_reward's string dicts equals the reference's scores."""
     from recurrent_fusion_network_amd import rewards as RW
     g = golden('spi5')
-    B, spi = int(g['B']), int(g['seq_per_img'])
-
-    def s(row):
-        return ' '.join(str(int(x)) for x in CPU.caption(row))
-    res = [{'image_id': r, 'caption': [s(g['res'][r])]} for r in range(2 * B)]
-    gts = {r: [s(g['gts'][(r % B) // spi][j]) for j in range(int(g['n_refs'][(r % B) // spi]))] for r in range(2 * B)}
+    gts, res = string_dicts(g)
     mean, scores = RW.CiderD().compute_score(gts, res)
     close(scores, g['scores'])
     assert abs(mean - np.mean(g['scores'])) <= 1e-10 * abs(np.mean(g['scores']))
@@ -64,27 +58,8 @@ def test_reference_interface_compute_score(dev):
 @pytest.mark.parametrize('seed', range(24))
 def test_fuzz_against_cpu_restatement(seed, dev):
     from recurrent_fusion_network_amd import rewards as RW
-    rng = np.random.default_rng(1000 + seed)
-    T, Tg = int(rng.integers(1, 65)), int(rng.integers(1, 65))
-    vocab = int(rng.choice([5, 50, 9487, 32767]))
-    n_img = int(rng.integers(1, 9))
-    spi = int(rng.integers(1, 5))
-    max_refs = int(rng.integers(1, 33))
-    n_refs = rng.integers(1, max_refs + 1, n_img).astype(np.int32)
-    n_refs[0] = max_refs
-    pools = [rng.integers(0, vocab + 1, int(rng.integers(2, 12))) for _ in range(n_img)]
-
-    def rows(n, width, pool):
-        out = rng.choice(pool, (n, width)).astype(np.int64)
-        cut = rng.random(n) < 0.6       # the others keep whatever ids the pool gives (with or without a 0)
-        out[cut, rng.integers(0, width, int(cut.sum()))] = 0
-        return out
-    gts = np.zeros((n_img, max_refs, Tg), dtype=np.int64)
-    for i in range(n_img):
-        gts[i, :n_refs[i]] = rows(int(n_refs[i]), Tg, pools[i])
-    B = n_img * spi
-    res = np.concatenate([rows(1, T, pools[(r % B) // spi]) for r in range(2 * B)])
-    row_img = CPU.scst_rows(B, spi)
+    f = fuzz_case(1000, seed)
+    vocab, n_img, res, row_img, gts, n_refs = f.vocab, f.n_img, f.res, f.row_img, f.gts, f.n_refs
     want = CPU.score_rows(res, row_img, gts, n_refs)
     got = RW.CiderD().score_ids(torch.from_numpy(res).to(dev), torch.from_numpy(row_img), torch.from_numpy(gts),
                                 torch.from_numpy(n_refs), vocab=vocab)
@@ -105,13 +80,11 @@ def test_fuzz_against_cpu_restatement(seed, dev):
 def test_bitwise_repeatable_and_graph_capturable(dev):
     from recurrent_fusion_network_amd import rewards as RW
     g = golden('spi5')
-    B, spi = int(g['B']), int(g['seq_per_img'])
-    res = torch.from_numpy(g['res']).to(dev)
-    gts, n_refs = torch.from_numpy(g['gts']).to(dev), torch.from_numpy(g['n_refs']).to(dev)
+    B, spi, res, row_img, gts, n_refs = device_inputs(g, dev)
     sc = RW.CiderD()
     a = RW.scst_reward(sc, res[:B], res[B:], gts, n_refs, spi).clone()
-    s1 = sc.score_ids(res, torch.from_numpy(CPU.scst_rows(B, spi)).to(dev), gts, n_refs).clone()
-    s2 = sc.score_ids(res, torch.from_numpy(CPU.scst_rows(B, spi)).to(dev), gts, n_refs).clone()
+    s1 = sc.score_ids(res, row_img, gts, n_refs).clone()
+    s2 = sc.score_ids(res, row_img, gts, n_refs).clone()
     assert torch.equal(s1, s2)
     gen, greedy = res[:B].clone(), res[B:].clone()
     side = torch.cuda.Stream()
@@ -156,28 +129,10 @@ def test_out_of_range_id_scores_nan_only_on_its_row(dev):
             assert s[r] == base[r], r
 
 
-def small_model(dev):
-    import recurrent_fusion_network_amd as R
-    from oracle import rfn_oracle as O
-    info = [dict(att_num=49, att_feat_size=96, fc_feat_size=64), dict(att_num=20, att_feat_size=72, fc_feat_size=72)]
-    cfg = O.make_cfg(info, vocab_size=200, rnn_size=64, input_encoding_size=64, att_hid_size=64, num_review_steps_0=4,
-                     num_review_steps=4, top_words_count=40, seq_length=8)
-    model = R.RecurrentFusionModel(cfg)
-    model.load_state_dict(O.seeded_params(cfg, 123))
-    fc, att, labels, masks, top = O.synthetic_batch(cfg, 8, seed=7)
-    d = lambda ts: [t.to(dev) for t in ts]  # noqa: E731
-    return R, cfg, model.to(dev), d(fc), d(att), top.to(dev)
-
-
 def test_get_rewards_drop_in_and_full_self_critical_step(dev):
     from recurrent_fusion_network_amd import rewards as RW
     R, cfg, model, fc, att, top = small_model(dev)
-    rng = np.random.default_rng(3)
-    B, spi = 8, 2
-    # variable caption counts per image, as dataloader.py collects them
-    data = {'gts': [rng.integers(1, 40, (int(k), cfg.seq_length + 2)) for k in (5, 3, 7, 1)]}
-    for a in data['gts']:
-        a[:, -2:] = 0
+    data, B, spi = drop_in_data(cfg)
     opt = types.SimpleNamespace(bleu4_weight=0, spice_weight=0, cider_weight=1.0, use_baseline=1)
     model.eval()
     with torch.no_grad():
