@@ -533,3 +533,44 @@ def train_step_loss_and_grads(cfg, P: Dict[str, Tensor], fc, att, labels, masks,
     loss.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in Pg.items()}
     return loss.detach(), grads
+
+
+def rl_step_loss_and_grads(cfg, P: Dict[str, Tensor], fc, att, fed_ids: Tensor, reward: Tensor, top_words, entropy_reg: float,
+                           reason_weight: float = 1.0, old_logprobs: Tensor = None, drop=None, dtype=None):
+    """The self-critical step minus the optimiser (train_rl.py:160-191) on tokens that were already drawn: the sampled
+    pass of ``sample(sample_max=0)`` (misc/RecurrentFusionModel.py:616-653), the reward criterion, backward.
+
+    ``fed_ids`` (B, S): column 0 is BOS, column t the UNMASKED token fed at step t (:637).  ``seq``, ``seqLogprobs`` and the
+    early exit follow from them exactly as in ``sample_greedy``: a row is finished after its first 0 (:641-644), the pass
+    stops at the first step with no unfinished row (:645), ``seqLogprobs`` is not masked (:649) and ``logprobs_all`` holds
+    one step more than ``seq``.  The decode itself is ``forward`` on the steps that ran -- a teacher-forced pass on the
+    fed tokens is the sampled pass -- so ``drop`` (``make_drop``) replays a training-mode sample.  ``reward`` is (B, T) with
+    T the length of ``seq``, or one value per row.  ``dtype=torch.float64`` casts weights and inputs.
+    Returns (loss, grads, seq, seqLogprobs, logprobs_all)."""
+    if dtype is not None:
+        P = {k: v.to(dtype) for k, v in P.items()}
+        fc, att = [f.to(dtype) for f in fc], [a.to(dtype) for a in att]
+    B, S = fed_ids.shape
+    tok = fed_ids[:, 1:]
+    unfinished = torch.cumprod((tok > 0).long(), 1)                                # :641-644
+    alive = unfinished.sum(0).tolist()
+    t_stop = next((t for t in range(1, S) if alive[t - 1] == 0), S)                # :645
+    n_seq = t_stop - 1
+    if n_seq < 1:
+        raise ValueError('every row drew 0 first: the reference fails in torch.cat([]) here (:655)')
+    Pg = {k: v.detach().clone().requires_grad_(True) for k, v in P.items()}
+    # no column 1 .. t_stop-1 is all zero (that step would have been the exit), so forward() runs exactly t_stop steps
+    lp_all, reason = forward(cfg, Pg, fc, att, fed_ids[:, :t_stop], drop=drop)
+    assert lp_all.size(1) == t_stop
+    seq = tok[:, :n_seq] * unfinished[:, :n_seq]                                   # :647-648
+    seq_lp = lp_all[:, :n_seq].gather(2, tok[:, :n_seq].unsqueeze(2)).squeeze(2)   # :632, :649
+    reward = reward.to(lp_all.dtype).reshape(B, -1)
+    if reward.size(1) == 1:
+        reward = reward.expand(B, n_seq)
+    if reward.size(1) != n_seq:
+        raise ValueError('reward has %d columns, the sampled sequence %d' % (reward.size(1), n_seq))
+    old = None if old_logprobs is None else old_logprobs.to(lp_all.dtype)
+    loss = rl_criterion(cfg, seq_lp, seq, reward, lp_all, entropy_reg, reason, top_words, reason_weight, old)
+    loss.backward()
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in Pg.items()}
+    return loss.detach(), grads, seq, seq_lp.detach(), lp_all.detach()
