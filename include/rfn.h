@@ -853,6 +853,37 @@ int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* ro
 int rfn_scst_reward_mix(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int T,
                         int use_baseline, float* out, double* out64, void* stream);
 
+/* ---- validation captions (eval_utils.language_eval: coco-caption/pycocoevalcap Bleu(4), Rouge(), Cider()) -------------------
+ * eval_utils.decode_sequence stops BEFORE the first 0, so a validation caption carries no end token.  The _ex forms of the two
+ * score calls take flags: with RFN_CAPTION_END_EXCLUDED a hypothesis or reference is the ids strictly before its first 0 (all
+ * T when there is none) and may be empty; without it they are rfn_ciderd_score / rfn_bleud_score bit for bit.  An empty
+ * hypothesis scores like pycocoevalcap's (BLEU 0 through its brevity penalty, CIDEr 0, ROUGE-L 0); an image with an empty
+ * reference (which the loader never produces) is treated like one with an out-of-range id: its rows score NaN.  Unknown flag
+ * bits: RFN_ERR_ARG.  Cider() is rfn_ciderd_score_ex in corpus mode with one score row per image (df per image, ref_len =
+ * log(n_img)); Bleu(4)'s corpus four are the `corpus` output. */
+#define RFN_CAPTION_END_EXCLUDED 1u
+int rfn_ciderd_score_ex(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                        const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots, double ref_docs,
+                        int vocab, double sigma, unsigned flags, double* scores, void* ws, size_t ws_bytes, void* stream);
+int rfn_bleud_score_ex(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                       const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, unsigned flags, double* scores,
+                       int32_t* comps, double* corpus, void* ws, size_t ws_bytes, void* stream);
+/* ROUGE-L (rouge/rouge.py): lcs[r, j] = the length of the longest common subsequence of row r's caption and reference j of its
+ * image (integer, one 64-bit bit-vector recurrence per pair); p = max_j lcs / len(caption), q = max_j lcs / len(reference j);
+ * scores[r] = (1 + beta^2) p q / (q + beta^2 p) when both are non-zero, else 0 (beta: 1.2 in the reference; must be > 0).
+ * Captions, rows, references, limits, flags and the NaN rule as above (both caption conventions).  One launch, one fp64 formula
+ * per row, no atomics: bitwise reproducible; no allocation, no synchronisation (capturable in a graph).
+ * scores: n_rows doubles; lcs: NULL or n_rows x max_refs int32 (0 behind an image's references and on a NaN row); ws:
+ * rfn_rougel_ws_bytes (0 outside the limits, else one 256-byte block: the single launch keeps nothing in it), 16-B aligned. */
+size_t rfn_rougel_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt);
+int rfn_rougel_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                     const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, unsigned flags, double beta, double* scores,
+                     int32_t* lcs, void* ws, size_t ws_bytes, void* stream);
+/* The corpus mean of a score column: *mean = the mean of scores[0], scores[stride], ... (n values) that are not NaN (NaN when
+ * none is left), *n_skipped (NULL or one int64) = how many were.  One workgroup, fp64 in a fixed order (strided partial sums,
+ * then a binary tree): bitwise reproducible, no atomics.  n, stride >= 1 (RFN_ERR_SHAPE otherwise). */
+int rfn_score_mean(const double* scores, int64_t n, int64_t stride, double* mean, int64_t* n_skipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ PATH_OPT_SHARED_SMALL_TILES = 64  # rfn.h RFN_PATH_OPT_SHARED_SMALL_TILES (A/B h
 PATH_OPT_DEC_UNHOISTED = 128      # rfn.h RFN_PATH_OPT_DEC_UNHOISTED (A/B hook: the three-launch decoder cell of rounds 3-5)
 PATH_OPT_SEED_DEV = 256           # rfn.h RFN_PATH_OPT_SEED_DEV: the `seed` argument is the device address of the dropout key
 CELL_VARIANT_DEEP = 256
+CAPTION_END_EXCLUDED = 1          # rfn.h RFN_CAPTION_END_EXCLUDED: a caption ends before its first 0 (validation), not after it
 GEMM_OPT_LDS_LEAN = 1
 GEMM_OPT_NO_DMA = 2
 GEMM_OPT_BF16X3 = 4
@@ -193,6 +194,11 @@ def _load():
         'rfn_bleud_ws_bytes': (SZ, [I, I, I, I, I]),
         'rfn_bleud_score': (C.c_int, [P, I, I, P, P, P, I, I, I, I, P, P, P, P, SZ, P]),
         'rfn_scst_reward_mix': (C.c_int, [P, C.c_double, P, C.c_double, I, I, I, P, P, P]),
+        'rfn_ciderd_score_ex': (C.c_int, [P, I, I, P, P, P, I, I, I, P, L, C.c_double, I, C.c_double, C.c_uint, P, P, SZ, P]),
+        'rfn_bleud_score_ex': (C.c_int, [P, I, I, P, P, P, I, I, I, I, C.c_uint, P, P, P, P, SZ, P]),
+        'rfn_rougel_ws_bytes': (SZ, [I, I, I, I, I]),
+        'rfn_rougel_score': (C.c_int, [P, I, I, P, P, P, I, I, I, I, C.c_uint, C.c_double, P, P, P, SZ, P]),
+        'rfn_score_mean': (C.c_int, [P, L, L, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

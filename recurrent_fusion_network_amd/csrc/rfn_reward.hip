@@ -7,7 +7,9 @@
 // 60-62, so no valid key is 0 and equal keys are equal n-grams (no hash collision can change a result).  rw_cook turns
 // a caption into first-occurrence keys, term counts and a word count; rw_refs_k stores that for every reference (one
 // workgroup per image); a hypothesis kernel cooks its score row (one workgroup per row) and walks the references of
-// its image through LDS with rw_lookup.  rw_reward_k forms the reward from the scores.
+// its image through LDS with rw_lookup.  rw_reward_k forms the reward from the scores.  The _ex entry points take flags:
+// with RFN_CAPTION_END_EXCLUDED a caption is the ids strictly before the first 0 (eval_utils.decode_sequence: what validation
+// scores), which rw_cook honours for every scorer; an image with an empty reference is then bad (its rows score NaN).
 //
 // CIDEr-D (cd_): document frequencies live in an open-addressing, linear-probe table:
 //   - corpus mode: the workspace table is cleared and filled every call; one integer atomicAdd per unique
@@ -83,8 +85,9 @@ __device__ __forceinline__ double cd_logdf(const CdDf& df, uint64_t key) {
 // Cook one caption of T ids (block-wide; blockDim.x = RW_THREADS).  Thread t < 4T owns n-gram slot (n = t / T,
 // p = t % T); it returns the key when its slot holds the FIRST occurrence of an n-gram in the caption (0 otherwise) and
 // the n-gram's term count in *tf.  *words: the caption's word count; the return of *bad: an id outside [0, vocab].
+// excl: the caption ends before its first 0 (and may be empty) instead of after it.
 // skey: RW_THREADS keys of LDS; sw / sbad: LDS ints.  All threads must call it.
-__device__ uint64_t rw_cook(const int64_t* __restrict__ ids, int T, int vocab, uint64_t* skey, int* sw, int* sbad,
+__device__ uint64_t rw_cook(const int64_t* __restrict__ ids, int T, int vocab, int excl, uint64_t* skey, int* sw, int* sbad,
                             int* tf, int* words, int* bad) {
     const int t = threadIdx.x;
     if (t == 0) {
@@ -95,7 +98,7 @@ __device__ uint64_t rw_cook(const int64_t* __restrict__ ids, int T, int vocab, u
     int64_t id = -1;
     if (t < T) {
         id = ids[t];
-        if (id == 0) atomicMin(sw, t + 1);
+        if (id == 0) atomicMin(sw, excl ? t : t + 1);
     }
     __syncthreads();
     const int W = *sw;
@@ -143,10 +146,11 @@ __global__ void cd_clear_k(uint64_t* __restrict__ keys, uint32_t* __restrict__ c
 // ---- references: one workgroup per image ----------------------------------------------------------------
 // Writes, per (image, ref) slot: rkey[4*Tg] (first occurrences), rcnt[4*Tg] (term counts), rwords (the word count); per
 // image img_bad.  CORPUS_DF (CIDEr-D's corpus mode) then adds the image's row count to the df of every n-gram its
-// references hold (once per image); only that instantiation uses dynamic LDS: max_refs * 4 * Tg keys.
+// references hold (once per image); only that instantiation uses dynamic LDS: max_refs * 4 * Tg keys.  excl: rw_cook's; an
+// empty reference then makes the image bad.
 template <bool CORPUS_DF>
 __global__ __launch_bounds__(RW_THREADS) void rw_refs_k(const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
-                                                        int max_refs, int Tg, int vocab, uint64_t* __restrict__ rkey,
+                                                        int max_refs, int Tg, int vocab, int excl, uint64_t* __restrict__ rkey,
                                                         int32_t* __restrict__ rcnt, int32_t* __restrict__ rwords,
                                                         int32_t* __restrict__ img_bad, const int32_t* __restrict__ row_img,
                                                         int n_rows, uint64_t* dkeys, uint32_t* dcnt, long dslots) {
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(RW_THREADS) void rw_refs_k(const int64_t* __restric
     const int nrc = bad_img ? 0 : nr;
     for (int j = 0; j < nrc; ++j) {
         int tf, words, bad;
-        const uint64_t key = rw_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+        const uint64_t key = rw_cook(gts + ((long)i * max_refs + j) * Tg, Tg, vocab, excl, skey, &sw, &sbad, &tf, &words, &bad);
         const long o = ((long)i * max_refs + j) * S;
         if (t < S) {
             rkey[o + t] = key;
@@ -167,7 +171,7 @@ __global__ __launch_bounds__(RW_THREADS) void rw_refs_k(const int64_t* __restric
             if (CORPUS_DF) all[j * S + t] = key;
         }
         if (t == 0) rwords[(long)i * max_refs + j] = words;
-        bad_img |= bad;
+        bad_img |= bad | (words == 0);   // words == 0: under excl only
     }
     if (t == 0) img_bad[i] = bad_img;
     if (!CORPUS_DF || bad_img) return;   // bad_img is block-uniform
@@ -242,8 +246,8 @@ __global__ __launch_bounds__(RW_THREADS) void cd_hyp_k(const int64_t* __restrict
                                                        int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
                                                        int max_refs, int Tg, const uint64_t* __restrict__ rkey,
                                                        const double* __restrict__ rval, const double* __restrict__ rnorm,
-                                                       const int32_t* __restrict__ rwords, int vocab, CdDf df, double ref_docs,
-                                                       double sigma, double* __restrict__ scores) {
+                                                       const int32_t* __restrict__ rwords, int vocab, int excl, CdDf df,
+                                                       double ref_docs, double sigma, double* __restrict__ scores) {
     __shared__ uint64_t skey[RW_THREADS], hk[RW_THREADS], rk[RW_THREADS];
     __shared__ double hv[RW_THREADS], rv[RW_THREADS], contrib[RW_THREADS];
     __shared__ double hnorm[RW_N], acc[RW_N];
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(RW_THREADS) void cd_hyp_k(const int64_t* __restrict
     }
     const int nr = n_refs[i];
     int tf, words, bad;
-    const uint64_t key = rw_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    const uint64_t key = rw_cook(res + (long)r * T, T, vocab, excl, skey, &sw, &sbad, &tf, &words, &bad);
     if (bad) {
         if (t == 0) scores[r] = __builtin_nan("");
         return;
@@ -356,7 +360,7 @@ __global__ __launch_bounds__(RW_THREADS) void bd_hyp_k(const int64_t* __restrict
                                                        int n_img, const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad,
                                                        int max_refs, int Tg, const uint64_t* __restrict__ rkey,
                                                        const int32_t* __restrict__ rcnt, const int32_t* __restrict__ rwords, int vocab,
-                                                       double* __restrict__ scores, int32_t* __restrict__ comps,
+                                                       int excl, double* __restrict__ scores, int32_t* __restrict__ comps,
                                                        int32_t* __restrict__ ucomps) {
     __shared__ uint64_t skey[RW_THREADS], rk[RW_THREADS];
     __shared__ int rc[RW_THREADS], clip[RW_THREADS];
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(RW_THREADS) void bd_hyp_k(const int64_t* __restrict
     const int i = row_img[r];
     int tf = 0, words = 0, bad = (i < 0 || i >= n_img || img_bad[i]);   // block-uniform
     uint64_t key = 0;
-    if (!bad) key = rw_cook(res + (long)r * T, T, vocab, skey, &sw, &sbad, &tf, &words, &bad);
+    if (!bad) key = rw_cook(res + (long)r * T, T, vocab, excl, skey, &sw, &sbad, &tf, &words, &bad);
     if (bad) {
         if (t < RW_N) scores[(long)r * RW_N + t] = __builtin_nan("");
         if (t < BD_COMPS) {
@@ -448,6 +452,117 @@ __global__ __launch_bounds__(RW_THREADS) void bd_corpus_k(const int32_t* __restr
     }
 }
 
+// ---- ROUGE-L (coco-caption/pycocoevalcap/rouge) ---------------------------------------------------------------------------
+// One workgroup per score row, one launch.  Wave w takes the references j = w, w + 4, ... of the row's image: lane q holds the
+// reference's id q, so a ballot of (id == hyp[p]) is the 64-bit match mask of hypothesis word p and the LCS length is the
+// bit-vector recurrence V = (V + (V & M)) | (V - (V & M)) over the hypothesis words (Hyyro 2004; V starts all ones, the LCS is the
+// number of zero bits).  The masks are wave-uniform, so the recurrence runs on the scalar unit.  Integer throughout; thread 0 then
+// forms the row's one fp64 formula from max(lcs) / len(hyp) and max over references of lcs / len(ref).
+__global__ __launch_bounds__(RW_THREADS) void rl_score_k(const int64_t* __restrict__ res, int T, const int32_t* __restrict__ row_img,
+                                                         int n_img, const int64_t* __restrict__ gts, const int32_t* __restrict__ n_refs,
+                                                         int max_refs, int Tg, int vocab, int excl, double beta,
+                                                         double* __restrict__ scores, int32_t* __restrict__ lcs_out /* or NULL */) {
+    __shared__ int hyp[RW_MAX_T];
+    __shared__ int slcs[RW_MAX_REFS], slen[RW_MAX_REFS];
+    __shared__ int shl, sbad;
+    const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i = row_img[r];
+    int nr = 0;
+    bool bad = (i < 0 || i >= n_img);   // block-uniform
+    if (!bad) {
+        nr = n_refs[i];
+        bad = (nr < 1 || nr > max_refs);
+    }
+    if (lcs_out && t < max_refs) lcs_out[(long)r * max_refs + t] = 0;
+    if (bad) {
+        if (t == 0) scores[r] = __builtin_nan("");
+        return;
+    }
+    if (t == 0) sbad = 0;
+    __syncthreads();
+    if (wave == 0) {   // the hypothesis: its length and its range check
+        const int64_t id = lane < T ? res[(long)r * T + lane] : -1;
+        const unsigned long long zero = __ballot(lane < T && id == 0);
+        int hl = T;
+        if (zero) hl = __ffsll(zero) - 1 + (excl ? 0 : 1);
+        if (lane < hl && (id < 0 || id > vocab)) sbad = 1;
+        hyp[lane] = (int)id;
+        if (lane == 0) shl = hl;
+    }
+    __syncthreads();
+    const int hl = shl;
+    for (int j = wave; j < nr; j += RW_THREADS / 64) {
+        const int64_t id = lane < Tg ? gts[((long)i * max_refs + j) * Tg + lane] : -1;
+        const unsigned long long zero = __ballot(lane < Tg && id == 0);
+        int rl = Tg;
+        if (zero) rl = __ffsll(zero) - 1 + (excl ? 0 : 1);
+        if ((lane < rl && (id < 0 || id > vocab)) || rl == 0) sbad = 1;   // an empty reference (excl only) is bad too
+        const int tok = (int)id;
+        unsigned long long V = ~0ull;
+        for (int p = 0; p < hl; ++p) {
+            const unsigned long long U = V & __ballot(lane < rl && tok == hyp[p]);
+            V = (V + U) | (V - U);
+        }
+        if (lane == 0) {
+            slcs[j] = __popcll(~V);
+            slen[j] = rl;
+        }
+    }
+    __syncthreads();
+    if (sbad) {   // block-uniform
+        if (t == 0) scores[r] = __builtin_nan("");
+        return;
+    }
+    if (lcs_out && t < nr) lcs_out[(long)r * max_refs + t] = slcs[t];
+    if (t == 0) {
+        double score = 0.0;
+        if (hl > 0) {   // an empty hypothesis is the reference's one empty token, which matches nothing
+            double pmax = 0.0, rmax = 0.0;
+            for (int j = 0; j < nr; ++j) {
+                pmax = fmax(pmax, (double)slcs[j] / (double)hl);
+                rmax = fmax(rmax, (double)slcs[j] / (double)slen[j]);
+            }
+            const double b2 = beta * beta;
+            if (pmax != 0.0 && rmax != 0.0) score = ((1.0 + b2) * pmax * rmax) / (rmax + b2 * pmax);
+        }
+        scores[r] = score;
+    }
+}
+
+// ---- the corpus mean of a score column: one workgroup, fp64 in a fixed order (thread t sums x[t], x[t + 256], ..., then a
+// binary tree over LDS), NaN rows skipped and counted.  No atomics: bitwise reproducible.
+__global__ __launch_bounds__(RW_THREADS) void rw_mean_k(const double* __restrict__ x, long n, long stride, double* __restrict__ mean,
+                                                        int64_t* __restrict__ skipped) {
+#pragma clang fp contract(off)
+    __shared__ double part[RW_THREADS];
+    __shared__ long long nan_part[RW_THREADS];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    long long k = 0;
+    for (long r = t; r < n; r += RW_THREADS) {
+        const double v = x[r * stride];
+        if (v != v)
+            ++k;
+        else
+            s += v;
+    }
+    part[t] = s;
+    nan_part[t] = k;
+    __syncthreads();
+    for (int w = RW_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            part[t] += part[t + w];
+            nan_part[t] += nan_part[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const long kept = n - (long)nan_part[0];
+        *mean = kept > 0 ? part[0] / (double)kept : __builtin_nan("");
+        if (skipped) *skipped = (int64_t)nan_part[0];
+    }
+}
+
 // ---- the reward: compute_reward's mix ((bleu4 * w_b) + (cider * w_c)) + spice * 0, each product and sum rounded on its own;
 // a NULL scorer is the 0 * weight the reference adds (which also turns a -0 into +0)
 __global__ void rw_reward_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu,
@@ -489,7 +604,7 @@ bool dims_ok(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
 }
 
 // The workspace of one call: the cooked references (what rw_refs_k writes), then what the scorer adds.
-enum Scorer { CIDER_TABLE, CIDER_CORPUS, BLEU };
+enum Scorer { CIDER_TABLE, CIDER_CORPUS, BLEU, ROUGE };
 struct Layout {
     size_t rkey, rcnt, rwords, bad;      // shared
     size_t dkeys, dcnt, rval, rnorm;     // CIDEr-D (the df table in corpus mode only)
@@ -501,6 +616,10 @@ Layout layout(Scorer scorer, int n_rows, int n_img, int max_refs, int T_gt) {
     Layout L{};
     const size_t nref = (size_t)n_img * max_refs;
     size_t o = 0;
+    if (scorer == ROUGE) {   // one launch that cooks nothing and stores nothing between kernels: a token block
+        L.total = kAlign;
+        return L;
+    }
     L.rkey = o;   o = up(o + nref * RW_N * T_gt * 8);
     L.rcnt = o;   o = up(o + nref * RW_N * T_gt * 4);
     L.rwords = o; o = up(o + nref * 4);
@@ -518,12 +637,13 @@ Layout layout(Scorer scorer, int n_rows, int n_img, int max_refs, int T_gt) {
     return L;
 }
 
-// The checks rfn_ciderd_score and rfn_bleud_score share, in their precedence; fills *L when it returns RFN_OK.
+// The checks the score calls share, in their precedence; fills *L when it returns RFN_OK.
 // extra_shape_ok: the caller's own shape conditions.
 int check_score_args(Scorer scorer, const void* res, int n_rows, int T_res, const void* row_img, const void* gts, const void* n_refs,
-                     int n_img, int max_refs, int T_gt, int vocab, bool extra_shape_ok, const void* scores, const void* ws,
-                     size_t ws_bytes, Layout* L) {
+                     int n_img, int max_refs, int T_gt, int vocab, unsigned flags, bool extra_shape_ok, const void* scores,
+                     const void* ws, size_t ws_bytes, Layout* L) {
     if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt) || vocab < 0 || vocab > RW_MAX_ID || !extra_shape_ok) return RFN_ERR_SHAPE;
+    if (flags & ~RFN_CAPTION_END_EXCLUDED) return RFN_ERR_ARG;
     if (!res || !row_img || !gts || !n_refs || !scores || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
     *L = layout(scorer, n_rows, n_img, max_refs, T_gt);
     return ws_bytes < L->total ? RFN_ERR_WORKSPACE : RFN_OK;
@@ -562,15 +682,16 @@ extern "C" int rfn_ciderd_table_build(const int32_t* ngram_ids, const double* co
     return RFN_OK;
 }
 
-extern "C" int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
-                                const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots,
-                                double ref_docs, int vocab, double sigma, double* scores, void* ws, size_t ws_bytes,
-                                void* stream) {
+extern "C" int rfn_ciderd_score_ex(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                                   const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots,
+                                   double ref_docs, int vocab, double sigma, unsigned flags, double* scores, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    const int excl = (flags & RFN_CAPTION_END_EXCLUDED) != 0;
     const bool corpus = table == nullptr;
     const bool table_ok = corpus || (slots >= 2 && !(slots & (slots - 1)) && ref_docs > 0.0);
     Layout L;
     const int rc = check_score_args(corpus ? CIDER_CORPUS : CIDER_TABLE, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs,
-                                    T_gt, vocab, table_ok, scores, ws, ws_bytes, &L);
+                                    T_gt, vocab, flags, table_ok, scores, ws, ws_bytes, &L);
     if (rc != RFN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
@@ -591,29 +712,38 @@ extern "C" int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const
         const size_t lds = (size_t)max_refs * RW_N * T_gt * 8;   // <= 64 KiB
         if (lds > 48 * 1024)
             hipFuncSetAttribute((const void*)rw_refs_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, row_img, n_rows,
-                                                        dkeys, dcnt, L.dslots);
+        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(gts, n_refs, max_refs, T_gt, vocab, excl, rkey, rcnt, rwords, bad, row_img,
+                                                        n_rows, dkeys, dcnt, L.dslots);
     } else {
         df = CdDf{(const uint64_t*)table, nullptr, (const double*)((const uint64_t*)table + slots), slots};
-        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, nullptr, 0, nullptr,
-                                                       nullptr, 0);
+        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, excl, rkey, rcnt, rwords, bad, nullptr, 0,
+                                                       nullptr, nullptr, 0);
     }
     RFN_CHECK_LAUNCH();
     const long nvec = (long)n_img * max_refs * RW_N;
     cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rcnt, rval, rnorm, df, ref_docs);
     RFN_CHECK_LAUNCH();
     cd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rval, rnorm, rwords, vocab,
-                                            df, ref_docs, sigma, scores);
+                                            excl, df, ref_docs, sigma, scores);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
 
-extern "C" int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
-                               const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, double* scores, int32_t* comps,
-                               double* corpus, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int rfn_ciderd_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                                const int32_t* n_refs, int n_img, int max_refs, int T_gt, const void* table, int64_t slots,
+                                double ref_docs, int vocab, double sigma, double* scores, void* ws, size_t ws_bytes,
+                                void* stream) {
+    return rfn_ciderd_score_ex(res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, table, slots, ref_docs, vocab, sigma,
+                               0u, scores, ws, ws_bytes, stream);
+}
+
+extern "C" int rfn_bleud_score_ex(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                                  const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, unsigned flags, double* scores,
+                                  int32_t* comps, double* corpus, void* ws, size_t ws_bytes, void* stream) {
+    const int excl = (flags & RFN_CAPTION_END_EXCLUDED) != 0;
     Layout L;
-    const int rc = check_score_args(BLEU, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, vocab, true, scores, ws,
-                                    ws_bytes, &L);
+    const int rc = check_score_args(BLEU, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, vocab, flags, true, scores,
+                                    ws, ws_bytes, &L);
     if (rc != RFN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
@@ -622,16 +752,49 @@ extern "C" int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const 
     int32_t* rwords = (int32_t*)(w + L.rwords);
     int32_t* bad = (int32_t*)(w + L.bad);
     int32_t* wcomps = (int32_t*)(w + L.comps);
-    rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, rkey, rcnt, rwords, bad, nullptr, 0, nullptr,
-                                                   nullptr, 0);
+    rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(gts, n_refs, max_refs, T_gt, vocab, excl, rkey, rcnt, rwords, bad, nullptr, 0,
+                                                   nullptr, nullptr, 0);
     RFN_CHECK_LAUNCH();
-    bd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rcnt, rwords, vocab, scores,
-                                            wcomps, comps);
+    bd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rcnt, rwords, vocab, excl,
+                                            scores, wcomps, comps);
     RFN_CHECK_LAUNCH();
     if (corpus) {
         bd_corpus_k<<<1, RW_THREADS, 0, st>>>(wcomps, n_rows, corpus);
         RFN_CHECK_LAUNCH();
     }
+    return RFN_OK;
+}
+
+extern "C" int rfn_bleud_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                               const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, double* scores, int32_t* comps,
+                               double* corpus, void* ws, size_t ws_bytes, void* stream) {
+    return rfn_bleud_score_ex(res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, vocab, 0u, scores, comps, corpus, ws,
+                              ws_bytes, stream);
+}
+
+extern "C" size_t rfn_rougel_ws_bytes(int n_rows, int T_res, int n_img, int max_refs, int T_gt) {
+    if (!dims_ok(n_rows, T_res, n_img, max_refs, T_gt)) return 0;
+    return layout(ROUGE, n_rows, n_img, max_refs, T_gt).total;
+}
+
+extern "C" int rfn_rougel_score(const int64_t* res, int n_rows, int T_res, const int32_t* row_img, const int64_t* gts,
+                                const int32_t* n_refs, int n_img, int max_refs, int T_gt, int vocab, unsigned flags, double beta,
+                                double* scores, int32_t* lcs, void* ws, size_t ws_bytes, void* stream) {
+    Layout L;
+    const int rc = check_score_args(ROUGE, res, n_rows, T_res, row_img, gts, n_refs, n_img, max_refs, T_gt, vocab, flags,
+                                    beta > 0.0, scores, ws, ws_bytes, &L);
+    if (rc != RFN_OK) return rc;
+    rl_score_k<<<n_rows, RW_THREADS, 0, (hipStream_t)stream>>>(res, T_res, row_img, n_img, gts, n_refs, max_refs, T_gt, vocab,
+                                                               (flags & RFN_CAPTION_END_EXCLUDED) != 0, beta, scores, lcs);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+extern "C" int rfn_score_mean(const double* scores, int64_t n, int64_t stride, double* mean, int64_t* n_skipped, void* stream) {
+    if (n < 1 || stride < 1) return RFN_ERR_SHAPE;
+    if (!scores || !mean) return RFN_ERR_ARG;
+    rw_mean_k<<<1, RW_THREADS, 0, (hipStream_t)stream>>>(scores, (long)n, (long)stride, mean, n_skipped);
+    RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
 

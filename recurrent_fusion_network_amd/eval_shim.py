@@ -6,7 +6,10 @@ row, dataloader.py:251-252); :159-195 then keeps ONE row per image (`arange(batc
 `sum(seqLogprobs * (seq > 0))`.  Everything around it (vocabulary decoding, COCO json, Java metrics) is host-side
 bookkeeping outside the accelerated path.
 
-Plumbing only: the arithmetic is `model.forward` / `model.sample` / the criterion (HIP kernels).
+`eval_split` is that loop around `eval_step`, with the part of `language_eval` that is plain arithmetic (Bleu, ROUGE_L, CIDEr)
+scored on the device by evalcap.LanguageEval.
+
+Plumbing only: the arithmetic is `model.forward` / `model.sample` / the criterion / the scorers (HIP kernels).
 """
 import torch
 
@@ -35,3 +38,31 @@ def eval_step(model, crit, fc_feats, att_feats, labels, masks, top_words, seq_pe
         seq, seq_lp = out[0], out[1]
         sentence = torch.sum(seq_lp * (seq > 0).to(seq_lp.dtype), 1)
     return dict(loss=loss, seq=seq, seqLogprobs=seq_lp, log_probs_sentence=sentence, sample=out)
+
+
+def eval_split(model, crit, batches, seq_per_img, vocab, beam_size=1, sample_max=1, reason_weight=1.0, metrics=None,
+               language_eval=None):
+    """eval_utils.eval_split's loop with language_eval's Bleu / ROUGE_L / CIDEr computed on the device.
+
+    batches: an iterable of dicts with the loader's 'fc_feats', 'att_feats' (lists of caption-row tensors), 'labels', 'masks',
+    'top_words' on the model's device and 'gts' (per image, an (n_refs_i, T) id array; or a padded array with 'n_refs').  The
+    module is put in eval mode for the loop and left in the mode it was found in.  -> (mean loss over the batches, metrics dict
+    of evalcap.LanguageEval.compute()).  The losses stay on the device until the loop has ended; language_eval: a LanguageEval to
+    feed instead of a new one (its per_image() and skipped are then the caller's to read)."""
+    from .evalcap import METRICS, LanguageEval
+    lang = language_eval if language_eval is not None else LanguageEval(vocab, METRICS if metrics is None else metrics)
+    was_training = model.training
+    model.eval()
+    losses = []
+    try:
+        for data in batches:
+            out = eval_step(model, crit, data['fc_feats'], data['att_feats'], data['labels'], data['masks'], data['top_words'],
+                            seq_per_img, reason_weight, beam_size, sample_max)
+            losses.append(out['loss'].detach().reshape(1).to(torch.float64))
+            lang.add(out['seq'], data['gts'], data.get('n_refs'))
+    finally:
+        model.train(was_training)
+    if not losses:
+        raise ValueError('eval_split needs at least one batch')
+    scores = lang.compute()
+    return float(torch.cat(losses).mean()), scores

@@ -10,6 +10,10 @@ reference would.
 BleuD reproduces cider/pyciderevalcap/bleuD's BleuD(4) (closest reference length) on the same id rows: four scores per row, the
 row's integer components and the corpus-level four.  compute_reward's bleu4 * bleu4_weight + cider * cider_weight is mixed on
 the device (scst_reward with bleu_scorer=).  SPICE-D (a Java server behind a socket) is not ported.
+
+RougeL reproduces coco-caption/pycocoevalcap's Rouge() (ROUGE-L, beta = 1.2) on the same id rows.  Every score_ids takes
+end_token=: True (the default) is the reward's caption, False the validation caption of eval_utils.decode_sequence, the ids
+strictly before the first 0 (evalcap.LanguageEval scores a whole split that way).
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ def _ref_docs_of(mode):
 
 
 class _IdScorer:
-    """What CiderD and BleuD share: the head of score_ids and the workspace."""
+    """What the scorers share: the head of score_ids and the workspace."""
     _NAME = None
     _ws = None
 
@@ -61,6 +65,10 @@ class _IdScorer:
         if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         return self._ws
+
+    @staticmethod
+    def _flags(end_token):
+        return 0 if end_token else N.CAPTION_END_EXCLUDED
 
 
 class CiderD(_IdScorer):
@@ -123,20 +131,21 @@ class CiderD(_IdScorer):
         return self._tables[key]
 
     # -- scoring ---------------------------------------------------------------------------------------------------
-    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None):
+    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, end_token=True):
         """res (N, T) int64 ids, row_img (N,) image of each row, gts (n_img, R, Tg) int64 references padded to R,
         n_refs (n_img,) references per image; all on one GPU.  -> (N,) float64 scores on the device (NaN for a row whose
-        caption or references hold an id outside [0, vocab])."""
+        caption or references hold an id outside [0, vocab]).  end_token=False: a caption is the ids before its first 0, not up
+        to and including it (then an image with an empty reference scores NaN too)."""
         dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg) = self._inputs(res, row_img, gts, n_refs)
         table = self._table(dev)
         ws = self._workspace(dev, N.lib.rfn_ciderd_ws_bytes(n_rows, T, n_img, R, Tg, int(table is None)))
         if out is None:
             out = torch.empty(n_rows, dtype=torch.float64, device=dev)
-        N.check(N.lib.rfn_ciderd_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(),
-                                       n_img, R, Tg, None if table is None else table.data_ptr(),
-                                       0 if table is None else self._slots, C.c_double(self.ref_docs or 0.0), vocab,
-                                       C.c_double(self._sigma), out.data_ptr(), ws.data_ptr(), ws.numel(), N.stream_ptr()),
-                'rfn_ciderd_score')
+        N.check(N.lib.rfn_ciderd_score_ex(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(),
+                                          n_img, R, Tg, None if table is None else table.data_ptr(),
+                                          0 if table is None else self._slots, C.c_double(self.ref_docs or 0.0), vocab,
+                                          C.c_double(self._sigma), self._flags(end_token), out.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), N.stream_ptr()), 'rfn_ciderd_score_ex')
         return out
 
     def compute_score(self, gts, res):
@@ -160,11 +169,11 @@ class BleuD(_IdScorer):
             raise NotImplementedError('only n = 4 (compute_reward\'s BleuD(4)) is implemented')
         self._n = n
 
-    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, comps=None, corpus=None):
+    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, comps=None, corpus=None, end_token=True):
         """Arguments as CiderD.score_ids.  -> (N, 4) float64 BLEU-1..4 per row on the device (NaN in all four for a row whose
         caption or references hold an id outside [0, vocab]).  comps: optional (N, 10) int32 device tensor that receives
         testlen, reflen, guess[4], correct[4] of every row; corpus: optional (4,) float64 device tensor that receives the
-        corpus-level scores (one more small launch)."""
+        corpus-level scores (one more small launch).  end_token: as CiderD.score_ids."""
         dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg) = self._inputs(res, row_img, gts, n_refs)
         ws = self._workspace(dev, N.lib.rfn_bleud_ws_bytes(n_rows, T, n_img, R, Tg))
         if out is None:
@@ -173,9 +182,9 @@ class BleuD(_IdScorer):
                                       (corpus, 'corpus', (4,), torch.float64)):
             if t is not None and (t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
                 raise ValueError('%s must be a contiguous %s %s tensor on %s' % (name, shape, dtype, dev))
-        N.check(N.lib.rfn_bleud_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(), n_img, R,
-                                      Tg, vocab, out.data_ptr(), N.ptr(comps), N.ptr(corpus), ws.data_ptr(), ws.numel(),
-                                      N.stream_ptr()), 'rfn_bleud_score')
+        N.check(N.lib.rfn_bleud_score_ex(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(), n_img,
+                                         R, Tg, vocab, self._flags(end_token), out.data_ptr(), N.ptr(comps), N.ptr(corpus),
+                                         ws.data_ptr(), ws.numel(), N.stream_ptr()), 'rfn_bleud_score_ex')
         return out
 
     def compute_score(self, gts, res):
@@ -189,6 +198,61 @@ class BleuD(_IdScorer):
 
     def method(self):
         return 'Bleu'
+
+
+class RougeL(_IdScorer):
+    """ROUGE-L scorer: pycocoevalcap's Rouge() (the F-measure of the longest common subsequence, beta = 1.2)."""
+    _NAME = 'ROUGE-L'
+
+    def __init__(self, beta=1.2):
+        if not beta > 0:
+            raise ValueError('beta must be positive')
+        self.beta = float(beta)
+
+    def score_ids(self, res, row_img, gts, n_refs, vocab=MAX_ID, out=None, lcs=None, end_token=True):
+        """Arguments as CiderD.score_ids.  -> (N,) float64 ROUGE-L per row on the device (NaN for a row whose caption or
+        references hold an id outside [0, vocab]; 0 for an empty caption).  lcs: optional (N, R) int32 device tensor that
+        receives the LCS length of the row against every reference of its image (0 behind them)."""
+        dev, res, row_img, gts, n_refs, (n_rows, T, n_img, R, Tg) = self._inputs(res, row_img, gts, n_refs)
+        ws = self._workspace(dev, N.lib.rfn_rougel_ws_bytes(n_rows, T, n_img, R, Tg))
+        if out is None:
+            out = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        for t, name, shape, dtype in ((out, 'out', (n_rows,), torch.float64), (lcs, 'lcs', (n_rows, R), torch.int32)):
+            if t is not None and (t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError('%s must be a contiguous %s %s tensor on %s' % (name, shape, dtype, dev))
+        N.check(N.lib.rfn_rougel_score(res.data_ptr(), n_rows, T, row_img.data_ptr(), gts.data_ptr(), n_refs.data_ptr(), n_img, R,
+                                       Tg, vocab, self._flags(end_token), C.c_double(self.beta), out.data_ptr(), N.ptr(lcs),
+                                       ws.data_ptr(), ws.numel(), N.stream_ptr()), 'rfn_rougel_score')
+        return out
+
+    def compute_score(self, gts, res, end_token=False):
+        """The reference's interface: gts {image_id: [caption, ...]}, res {image_id: [caption]} (or CiderD.compute_score's list),
+        captions being space-separated id strings.  end_token=False (the default): validation captions as
+        eval_utils.decode_sequence writes them, without a 0 (a 0 token raises ValueError; an empty string is an empty caption);
+        end_token=True: the reward's captions as array_to_str writes them.  -> (mean, np.ndarray of per-image scores, in res's
+        order)."""
+        if isinstance(res, dict):
+            res = [{'image_id': k, 'caption': v} for k, v in res.items()]
+        res_a, row_img, gts_a, n_refs, vocab = _id_arrays(gts, res, end_token=end_token)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        s = self.score_ids(torch.from_numpy(res_a).to(dev), row_img, torch.from_numpy(gts_a), n_refs, vocab=vocab,
+                           end_token=end_token)
+        return mean_score(s)[0].item(), s.cpu().numpy()
+
+    def method(self):
+        return 'Rouge'
+
+
+def mean_score(scores, out=None):
+    """The mean of a (N,) or (N, k) float64 device tensor's first column over the rows that are not NaN, in a fixed order
+    (bitwise repeatable) -> (mean, skipped): one-element float64 and int64 device tensors.  No synchronisation."""
+    if scores.dtype != torch.float64 or scores.dim() not in (1, 2) or not scores.is_contiguous() or scores.device.type != 'cuda':
+        raise ValueError('scores must be a contiguous float64 (N,) or (N, k) tensor on the GPU')
+    mean = torch.empty(1, dtype=torch.float64, device=scores.device) if out is None else out
+    skipped = torch.empty(1, dtype=torch.int64, device=scores.device)
+    N.check(N.lib.rfn_score_mean(scores.data_ptr(), scores.shape[0], 1 if scores.dim() == 1 else scores.shape[1],
+                                 mean.data_ptr(), skipped.data_ptr(), N.stream_ptr()), 'rfn_score_mean')
+    return mean, skipped
 
 
 def _int_word(w):
@@ -215,9 +279,19 @@ def _row(words, T):
                      'first 0, or exactly T ids without one)' % (' '.join(map(str, words)), T))
 
 
-def _id_arrays(gts, res):
+def _plain_row(words, T):
+    """One id row whose validation caption (the ids before the first 0) is `words`."""
+    if 0 in words:
+        raise ValueError('caption %r holds the end token 0: a validation caption stops before it (end_token=True scores the '
+                         'reward\'s captions)' % ' '.join(map(str, words)))
+    return words + [0] * (T - len(words))
+
+
+def _id_arrays(gts, res, end_token=True):
     """compute_score's dicts (gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}]) as id arrays:
-    res (N, T) int64, row_img (N,) int32 tensor, gts (n_img, R, Tg) int64, n_refs (n_img,) int32 tensor, vocab."""
+    res (N, T) int64, row_img (N,) int32 tensor, gts (n_img, R, Tg) int64, n_refs (n_img,) int32 tensor, vocab.
+    end_token=False: captions without a 0 (possibly empty), padded with 0."""
+    row = _row if end_token else _plain_row
     images, img_of = [], {}
     rows = []
     for entry in res:
@@ -232,14 +306,14 @@ def _id_arrays(gts, res):
             img_of[iid] = len(images)
             images.append([_words(s) for s in refs])
         rows.append((_words(hyp[0]), img_of[iid]))
-    T = max(len(w) for w, _ in rows)
-    Tg = max(len(w) for refs in images for w in refs)
-    res_a = np.array([_row(w, T) for w, _ in rows], dtype=np.int64)
+    T = max(1, max(len(w) for w, _ in rows))
+    Tg = max(1, max(len(w) for refs in images for w in refs))
+    res_a = np.array([row(w, T) for w, _ in rows], dtype=np.int64)
     R = max(len(refs) for refs in images)
     gts_a = np.zeros((len(images), R, Tg), dtype=np.int64)
     for i, refs in enumerate(images):
         for j, w in enumerate(refs):
-            gts_a[i, j] = _row(w, Tg)
+            gts_a[i, j] = row(w, Tg)
     vocab = int(max(res_a.max(), gts_a.max(), 0))
     return (res_a, torch.tensor([i for _, i in rows], dtype=torch.int32), gts_a,
             torch.tensor([len(r) for r in images], dtype=torch.int32), min(vocab, MAX_ID))

@@ -7,7 +7,12 @@
   - --bleu: instead, the BLEU-D legs (profiles/bleud_reward.json): at the C5 shape (128 + 128 rows, 5 refs) and at the shape
     of the spi5 golden tier (640 + 640 rows, 128 images, 5-7 refs) the CIDEr-only call (corpus mode, the call timed above), the
     BLEU-only call and the mixed call, alternated in blocks of --block calls over --rounds rounds; min / median / max per leg.
-Usage: python tools/bench_reward.py [--steps 50] [--warmup 5] | --bleu [--block 2000] [--rounds 7]
+  - --rouge: instead, the ROUGE-L call alone (rewards.RougeL.score_ids, validation captions) at the C5 shape, at the spi5 shape
+    and at 5000 rows x 5 refs, in blocks as --bleu.
+  - --eval: instead, one whole-split evalcap.LanguageEval.compute() (Bleu, ROUGE_L, CIDEr; 5000 images x 5 references, T = 16, the
+    split tools/make_evalcap_golden.py --time scores with the reference's scorers) including its one host read, per call and per
+    metric.
+Usage: python tools/bench_reward.py [--steps 50] [--warmup 5] | --bleu [--block 2000] [--rounds 7] | --rouge | --eval
 """
 import argparse
 import json
@@ -80,6 +85,55 @@ def bleu_legs(args):
     print(json.dumps(out), flush=True)
 
 
+def spread(v):
+    v = sorted(v)
+    return {'min': round(v[0], 4), 'median': round(v[len(v) // 2], 4), 'max': round(v[-1], 4)}
+
+
+def rouge_legs(args):
+    from recurrent_fusion_network_amd import rewards as RW
+    dev = torch.device('cuda:0')
+    out = {'metric': 'ROUGE-L, ms per RougeL.score_ids call (validation captions, T = 16)', 'unit': 'ms',
+           'calls_per_block': args.block, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0)}
+    sc = RW.RougeL()
+    for tag, rows, spi, refs in (('c5_256', 256, 1, 5), ('spi5_1280', 1280, 5, 7), ('val_5000', 5000, 1, 5)):
+        gen, _, gts, n_refs = scoring_case(rows, spi, dev, rows, refs=refs)
+        row_img = torch.arange(rows, dtype=torch.int32, device=dev) // spi
+        scores = torch.empty(rows, dtype=torch.float64, device=dev)
+
+        def call():
+            sc.score_ids(gen, row_img, gts, n_refs, out=scores, end_token=False)
+        time_calls(call, args.block // 4, 20)
+        out[tag] = spread([time_calls(call, args.block, 0) for _ in range(args.rounds)])
+    print(json.dumps(out), flush=True)
+
+
+def eval_legs(args):
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import evalcap_cases as CASES
+    from recurrent_fusion_network_amd.evalcap import LanguageEval
+    dev = torch.device('cuda:0')
+    seq, gts, n_refs, vocab = CASES.val_split(77, 5000, 5, 5)
+    batches = [(torch.from_numpy(seq[lo:lo + 500]).to(dev), torch.from_numpy(gts[lo:lo + 500]).to(dev),
+                torch.from_numpy(n_refs[lo:lo + 500]).to(dev)) for lo in range(0, 5000, 500)]
+    out = {'metric': 'validation metrics, ms per whole-split LanguageEval.compute() (5000 images x 5 references, T = 16, fed as ten '
+                     'device batches; concatenation, the scorers, the corpus reductions and the one host read)', 'unit': 'ms',
+           'calls_per_block': args.steps, 'rounds': args.rounds, 'device': torch.cuda.get_device_name(0)}
+    for tag, metrics in (('all', ('Bleu', 'ROUGE_L', 'CIDEr')), ('bleu', ('Bleu',)), ('rouge', ('ROUGE_L',)), ('cider', ('CIDEr',))):
+        le = LanguageEval(vocab, metrics)
+        for b in batches:
+            le.add(*b)
+
+        def call():
+            le._result = None
+            return le.compute()
+        time_calls(call, args.warmup, 2)
+        out[tag] = spread([time_calls(call, args.steps, 0) for _ in range(args.rounds)])
+        if tag == 'all':
+            out['scores'] = {k: round(v, 6) for k, v in call().items()}
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -87,9 +141,15 @@ def main():
     ap.add_argument('--bleu', action='store_true', help='time the BLEU-D and mixed reward calls next to the CIDEr-D call')
     ap.add_argument('--block', type=int, default=2000)
     ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--rouge', action='store_true', help='time the ROUGE-L call')
+    ap.add_argument('--eval', action='store_true', help='time a whole-split LanguageEval.compute() at 5000 x 5')
     args = ap.parse_args()
     if args.bleu:
         return bleu_legs(args)
+    if args.rouge:
+        return rouge_legs(args)
+    if args.eval:
+        return eval_legs(args)
     import bench
     import recurrent_fusion_network_amd as R
     from recurrent_fusion_network_amd import rewards as RW
