@@ -615,6 +615,8 @@ int rfn_adam_step_multi_coef(int nbuckets, float* const* p, const float* const* 
 
 /* greedy pick of sample() (misc/RecurrentFusionModel.py:619-649) for one step t >= 1:
  * it = argmax_v logp[b,:] (first maximum), lp_out[b] = that value,
+ * with torch.max's order on degenerate rows: NaN ranks above every number, so a row holding NaN picks its first NaN
+ * (lp_out[b] = NaN), and a row of all -inf picks token 0; `it` is always in [0, V1).
  * unf_out[b] = (t==1 ? 1 : unf_prev[b]) & (it>0), seq_out[b] = it*unf_out[b],
  * next_ids[b] = it (UNMASKED: the reference embeds the raw argmax, :637).
  * Keeping one unf_out row per step lets the host apply the reference's early exit (:645) with a

@@ -1348,6 +1348,13 @@ extern "C" int rfn_multinomial_pick(const float* logp, int64_t ldl, int B, int V
 }
 
 // ---- greedy pick of sample() (misc/RecurrentFusionModel.py:619-649) -----------------------------------
+// Order of the arg-max, as torch.max has it: NaN ranks above every number, equals (two NaNs included) go to the lower index.
+// Every thread that owns an element starts from it, so a row of all -inf yields token 0 and a row with NaN its first NaN:
+// the picked id is always in [0, V1).  On rows of ordinary numbers the comparisons are the ones `>` / `==` made.
+__device__ __forceinline__ bool pick_gt(float x, float y) { return x > y || (x != x && y == y); }
+__device__ __forceinline__ bool pick_before(float x, int i, float y, int j) {
+    return pick_gt(x, y) || (!pick_gt(y, x) && i < j);
+}
 __global__ __launch_bounds__(256) void greedy_pick_k(const float* __restrict__ logp, long ldl, int V1, int t,
                                                      int64_t* __restrict__ next_ids, int64_t* __restrict__ seq_out,
                                                      long ld_seq, float* __restrict__ lp_out, long ld_lp,
@@ -1371,10 +1378,14 @@ __global__ __launch_bounds__(256) void greedy_pick_k(const float* __restrict__ l
         return;
     }
     float m = -INFINITY;
-    int mi = 0x7fffffff;
-    for (int v = threadIdx.x; v < V1; v += 256) {
+    int mi = 0x7fffffff;   // a thread past the row's end: loses to every real entry, -inf included
+    if (threadIdx.x < V1) {
+        m = x[threadIdx.x];
+        mi = threadIdx.x;
+    }
+    for (int v = threadIdx.x + 256; v < V1; v += 256) {
         const float xv = x[v];
-        if (xv > m) {  // strided ascending scan keeps the first maximum per thread
+        if (pick_gt(xv, m)) {  // strided ascending scan keeps the first maximum per thread
             m = xv;
             mi = v;
         }
@@ -1383,7 +1394,7 @@ __global__ __launch_bounds__(256) void greedy_pick_k(const float* __restrict__ l
     for (int o = 32; o > 0; o >>= 1) {
         const float om = __shfl_xor(m, o, 64);
         const int oi = __shfl_xor(mi, o, 64);
-        if (om > m || (om == m && oi < mi)) {
+        if (pick_before(om, oi, m, mi)) {
             m = om;
             mi = oi;
         }
@@ -1396,7 +1407,7 @@ __global__ __launch_bounds__(256) void greedy_pick_k(const float* __restrict__ l
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w)
-            if (vs[w] > m || (vs[w] == m && is[w] < mi)) {
+            if (pick_before(vs[w], is[w], m, mi)) {
                 m = vs[w];
                 mi = is[w];
             }
