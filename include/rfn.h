@@ -660,6 +660,47 @@ int rfn_beam_step_topk(const float* topv, const int32_t* topi, int V1, int W, in
  * sort lists them; the log-prob bits are those rfn_log_softmax_fwd writes, which are not materialised here. */
 int rfn_log_softmax_topk(const float* logits, int64_t ldl, int rows, int V1, int W, float* topv, int32_t* topi,
                          void* stream);
+/* ---- decoding constraints (off by default; the reference has none) ---------------------------------------------------------
+ * All of them edit a row's log-probs AFTER the log-softmax, by setting entries to -inf without renormalising: the log-prob
+ * recorded for a chosen token stays the model's own.  The history of a row is the tokens it has emitted so far (BOS
+ * excluded); step t >= 1 picks the t-th token, so the history then holds t - 1 tokens.  For a row that has not finished
+ * (history empty or its last token != 0; a finished row is left alone, its list is empty):
+ *   - banned[i] (0 < id < V1) is blocked at every step;
+ *   - block_ngram = n in [2, 4] (0 = off), t >= n: with g the last n - 1 tokens of the history, every token that followed an
+ *     earlier occurrence of g in the history is blocked, except token 0 (END);
+ *   - token 0 is blocked when the last token of the history is one of bad_endings (at t = S as at any other step: the search's
+ *     forced close at t = S is not a token choice and stays as it is).
+ * rfn_decode_blocklist writes the blocked ids of `rows` rows: blk (rows, RFN_DECODE_MAX_IDS + S) int32, row r holding blk_n[r]
+ * ids (banned first, then the n-gram continuations in history order, then 0) padded with -1; the list may hold duplicates.
+ * Token j of row r is hist[src * s_row + j * s_tok], src = order ? order[r] : r -- a (B, S) matrix (s_row = its row stride,
+ * s_tok = 1), or the beam arrays (S, NB, W) (s_row = 1, s_tok = NB * W): with order == NULL as rfn_beam_step leaves them
+ * (already forked, row r = beam r), with the step's order[] when they have NOT been forked yet (row r continues beam
+ * order[r]).  Limits (RFN_ERR_SHAPE): 1 <= t <= S <= 64, n_banned, n_bad <= RFN_DECODE_MAX_IDS.  Ids outside [0, V1) are
+ * dropped, so are banned ids <= 0. */
+#define RFN_DECODE_MAX_IDS 64
+int rfn_decode_blocklist(const int64_t* hist, int64_t s_row, int64_t s_tok, const int32_t* order, int rows, int S, int t,
+                         int block_ngram, const int32_t* banned, int n_banned, const int32_t* bad_endings, int n_bad, int V1,
+                         int32_t* blk, int32_t* blk_n, void* stream);
+/* logp[r, blk[r, i]] = -inf for i < blk_n[r], in place; everything else keeps its bits (ldl >= V1: the row stride). */
+int rfn_logp_mask_rows(float* logp, int64_t ldl, int rows, int V1, const int32_t* blk, int64_t ld_blk, const int32_t* blk_n,
+                       void* stream);
+/* rfn_log_softmax_topk of the masked rows: the log-sum-exp is taken over ALL V1 logits (an unblocked entry carries exactly the
+ * bits rfn_log_softmax_topk / rfn_log_softmax_fwd give it), blocked tokens rank as -inf -- the list a stable descending sort of
+ * the masked log-prob row gives, so a row with fewer than W unblocked tokens is filled with its lowest -inf ids in ascending
+ * order.  blk == NULL: rfn_log_softmax_topk, bit for bit.  V1 <= 393216 with a block list (one bit per token in LDS). */
+int rfn_log_softmax_topk_masked(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk, int64_t ld_blk,
+                                const int32_t* blk_n, float* topv, int32_t* topi, void* stream);
+/* What the loop entry points below take: the id lists live in device memory (uploaded once per call by the host), blk / blk_n
+ * are scratch of (rows, RFN_DECODE_MAX_IDS + S) and (rows) int32 for the rows of the loop (B, or NB * W). */
+typedef struct rfn_decode_constraints {
+    int32_t block_ngram;          /* 0 = off, else 2 .. 4 */
+    int32_t n_banned, n_bad;      /* <= RFN_DECODE_MAX_IDS each */
+    int32_t pad_;
+    const int32_t* banned;        /* device, may be NULL when n_banned = 0 */
+    const int32_t* bad_endings;   /* device, may be NULL when n_bad = 0 */
+    int32_t* blk;
+    int32_t* blk_n;
+} rfn_decode_constraints;
 /* dst[r,:] = src[order[r],:]  (src != dst) */
 int rfn_gather_rows(const float* src, float* dst, const int32_t* order, int rows, int R, void* stream);
 
@@ -801,6 +842,22 @@ int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const float* const* p
                   float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
                   float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
                   void* stream);
+
+/* The same loops under decoding constraints (above): per step one rfn_decode_blocklist, then rfn_logp_mask_rows before the pick
+ * (rfn_decoder_loop_ex: the masked entries of logp_all read -inf afterwards) or rfn_log_softmax_topk_masked in place of
+ * rfn_log_softmax_topk (rfn_beam_loop_ex).  A row left without any unblocked token picks token 0, as rfn_greedy_pick does on
+ * a row of -inf (a multinomial draw of such a row keeps the token the row fed last).  cons == NULL: the calls and the bits
+ * of rfn_decoder_loop / rfn_beam_loop, which forward here.  rfn_decoder_loop_ex needs steps - 1 <= 64 with constraints. */
+int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const float* const* params, const float* comb,
+                        const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                        float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                        int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                        const rfn_decode_constraints* cons, void* stream);
+int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const* params, const float* comb,
+                     const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp, int64_t* beam_seq,
+                     float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
+                     float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
+                     const rfn_decode_constraints* cons, void* stream);
 
 /* ---- self-critical reward: CIDEr-D of token-id captions (get_rewards.py:39-112, cider/pyciderevalcap/ciderD) ---------
  * CiderD(n=4, sigma) as compute_reward calls it (csrc/rfn_reward.hip).  A caption is the ids of its row up to and including

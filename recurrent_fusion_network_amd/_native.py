@@ -80,6 +80,15 @@ class CellOut(C.Structure):
                 ('lddcp', C.c_int64), ('acc_slabs', C.c_void_p), ('acc_parts', C.c_int32), ('acc_stride', C.c_int64)]
 
 
+class DecodeConstraints(C.Structure):
+    """rfn_decode_constraints (rfn.h)."""
+    _fields_ = [('block_ngram', C.c_int32), ('n_banned', C.c_int32), ('n_bad', C.c_int32), ('pad_', C.c_int32),
+                ('banned', C.c_void_p), ('bad_endings', C.c_void_p), ('blk', C.c_void_p), ('blk_n', C.c_void_p)]
+
+
+DECODE_MAX_IDS = 64
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise RfnError(
@@ -90,7 +99,7 @@ def _load():
         raise RfnError('librfn_hip.so ABI %d != binding ABI %d: rebuild' % (lib.rfn_abi_version(), ABI_VERSION))
     lib.rfn_error_string.restype = C.c_char_p
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
-    DP = C.POINTER(Dims)
+    DP, CP = C.POINTER(Dims), C.POINTER(DecodeConstraints)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -164,6 +173,9 @@ def _load():
         'rfn_gather_rows': (C.c_int, [P, P, P, I, I, P]),
         'rfn_beam_step_topk': (C.c_int, [P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
         'rfn_log_softmax_topk': (C.c_int, [P, L, I, I, I, P, P, P]),
+        'rfn_log_softmax_topk_masked': (C.c_int, [P, L, I, I, I, P, L, P, P, P, P]),
+        'rfn_decode_blocklist': (C.c_int, [P, L, L, P, I, I, I, I, P, I, P, I, I, P, P, P]),
+        'rfn_logp_mask_rows': (C.c_int, [P, L, I, I, P, L, P, P]),
         'rfn_prefix_ws_bytes': (SZ, [DP, I, I]),
         'rfn_prefix_fwd': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, SZ, I, U64, P]),
         'rfn_prefix_fwd_from_state': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, P]),
@@ -176,6 +188,8 @@ def _load():
         'rfn_decoder_bwd': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, P, P, P, P, P, SZ, U64, P]),
         'rfn_pick_record': (C.c_int, [P, L, I, I, I, P, P, P, L, P, L, P, P, P]),
         'rfn_decoder_loop': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, P]),
+        'rfn_decoder_loop_ex': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, P]),
+        'rfn_beam_loop_ex': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, P]),
         'rfn_decoder_fwd_sampled': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, P]),
         'rfn_beam_loop': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, P]),
         'rfn_decoder_step_ws_bytes': (SZ, [DP, I]),

@@ -362,17 +362,52 @@ extern "C" int rfn_log_softmax_fwd(const float* logits, int64_t ldl, int rows, i
 // from the same log-prob bits rfn_log_softmax_fwd writes.  W <= 32.
 #define LSM_TOPW 32
 __device__ __forceinline__ bool lsm_before(float x, int i, float y, int j) { return x > y || (x == y && i < j); }
-template <bool VEC, int LW>
+// MASK (rfn_log_softmax_topk_masked): the row's block list (blk[r, :blk_n[r]], duplicates allowed) becomes a bit per token in
+// LDS; the log-sum-exp above it is still taken over ALL logits, and a blocked token then enters the selection as -inf, so the
+// list is the one a stable descending sort of the masked log-prob row gives (short rows are filled with the lowest -inf ids).
+template <bool VEC, int LW, bool MASK>
 __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restrict__ logits, long ldl, int V1, int W,
-                                                          float* __restrict__ topv, int* __restrict__ topi) {
+                                                          float* __restrict__ topv, int* __restrict__ topi,
+                                                          const int* __restrict__ blk, long ld_blk,
+                                                          const int* __restrict__ blk_n) {
     __shared__ float red[4];
     __shared__ float wv[4][LSM_TOPW];
     __shared__ int wi[4][LSM_TOPW];
+    extern __shared__ unsigned lsm_bits[];       // MASK: (V1 + 31) / 32 words
     const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* x = logits + r * ldl;
     lsm_f32x4 xr[LSM_R4];
     const float lse = log_softmax_row<VEC>(x, V1, xr, red);
     const int cols = min(W, V1);
+    if constexpr (MASK) {
+        for (int i = threadIdx.x; i < (V1 + 31) / 32; i += 256) lsm_bits[i] = 0u;
+        __syncthreads();
+        const int nb = blk_n[r];
+        for (int i = threadIdx.x; i < nb; i += 256) {
+            const int id = blk[r * ld_blk + i];
+            if (id >= 0 && id < V1) atomicOr(&lsm_bits[id >> 5], 1u << (id & 31));
+        }
+        __syncthreads();
+        if constexpr (VEC) {
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j) {
+                const int i = threadIdx.x + 256 * j;
+                if (i < (V1 >> 2)) {
+                    const unsigned b4 = lsm_bits[i >> 3] >> ((4 * i) & 31);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if ((b4 >> e) & 1u) xr[j][e] = -INFINITY;
+                }
+            }
+        }
+    }
+    // the logit of token v as the selection sees it (the non-VEC form re-reads the row)
+    auto xat = [&](int v) {
+        if constexpr (MASK) {
+            if ((lsm_bits[v >> 5] >> (v & 31)) & 1u) return -INFINITY;
+        }
+        return x[v];
+    };
     // Threshold first: the `cols`-th largest of the 256 threads' LOCAL maxima is a lower bound of the row's `cols`-th largest
     // log-prob (those maxima are distinct elements of the row), so only entries >= it can make the list -- a handful per
     // row instead of every entry going through a sorted insert.
@@ -381,7 +416,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
 #pragma unroll
         for (int j = 0; j < LSM_R4; ++j) lm = fmaxf(lm, fmaxf(fmaxf(xr[j][0], xr[j][1]), fmaxf(xr[j][2], xr[j][3])));
     } else {
-        for (int v = threadIdx.x; v < V1; v += 256) lm = fmaxf(lm, x[v]);
+        for (int v = threadIdx.x; v < V1; v += 256) lm = fmaxf(lm, xat(v));
     }
     lm -= lse;      // x - lse is monotone in x: the maximum of the log-probs is the log-prob of the maximum
     {
@@ -452,7 +487,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
             }
         }
     } else {
-        for (int v = threadIdx.x; v < V1; v += 256) offer(x[v] - lse, v);
+        for (int v = threadIdx.x; v < V1; v += 256) offer(xat(v) - lse, v);
     }
     for (int c = 0; c < cols; ++c) {             // wave merge: pop the best head `cols` times
         float best = tv[0];
@@ -500,19 +535,123 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
         }
     }
 }
-extern "C" int rfn_log_softmax_topk(const float* logits, int64_t ldl, int rows, int V1, int W, float* topv, int32_t* topi,
-                                    void* stream) {
+static int log_softmax_topk_launch(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk, int64_t ld_blk,
+                                   const int32_t* blk_n, float* topv, int32_t* topi, void* stream) {
     if (rows <= 0 || V1 <= 0 || W < 1 || W > LSM_TOPW) return RFN_ERR_SHAPE;
     if (!logits || !topv || !topi) return RFN_ERR_ARG;
+    if (blk && (!blk_n || ld_blk < 1)) return RFN_ERR_ARG;
+    const size_t bits = blk ? (size_t)((V1 + 31) / 32) * sizeof(unsigned) : 0;
+    if (bits > 48 * 1024) return RFN_ERR_SHAPE;     // one bit per token in LDS
     hipStream_t st = (hipStream_t)stream;
     const bool vec = lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0);
-#define LSM_LAUNCH(VECV, LWV)                                                                                              \
-    hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV>), dim3(rows), dim3(256), 0, st, logits, (long)ldl, V1, W, topv, topi)
+#define LSM_LAUNCH3(VECV, LWV, MASKV)                                                                                       \
+    hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, W, topv, \
+                       topi, blk, (long)ld_blk, blk_n)
+#define LSM_LAUNCH(VECV, LWV)                                                                                               \
+    do {                                                                                                                    \
+        if (blk) LSM_LAUNCH3(VECV, LWV, true);                                                                              \
+        else LSM_LAUNCH3(VECV, LWV, false);                                                                                 \
+    } while (0)
     if (W <= 4) { if (vec) LSM_LAUNCH(true, 4); else LSM_LAUNCH(false, 4); }
     else if (W <= 8) { if (vec) LSM_LAUNCH(true, 8); else LSM_LAUNCH(false, 8); }
     else if (W <= 16) { if (vec) LSM_LAUNCH(true, 16); else LSM_LAUNCH(false, 16); }
     else { if (vec) LSM_LAUNCH(true, 32); else LSM_LAUNCH(false, 32); }
 #undef LSM_LAUNCH
+#undef LSM_LAUNCH3
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+extern "C" int rfn_log_softmax_topk(const float* logits, int64_t ldl, int rows, int V1, int W, float* topv, int32_t* topi,
+                                    void* stream) {
+    return log_softmax_topk_launch(logits, ldl, rows, V1, W, nullptr, 0, nullptr, topv, topi, stream);
+}
+extern "C" int rfn_log_softmax_topk_masked(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk,
+                                           int64_t ld_blk, const int32_t* blk_n, float* topv, int32_t* topi, void* stream) {
+    return log_softmax_topk_launch(logits, ldl, rows, V1, W, blk, ld_blk, blk_n, topv, topi, stream);
+}
+
+// ---- decoding constraints: the blocked tokens of every row at step t, and their mask (rfn.h) ---------------------------------
+// One wave per row.  Lane j holds token j of the row's history (at most 63 tokens: t <= S <= 64); it matches the n-gram that
+// starts at j against the history's last n - 1 tokens through LDS, and a ballot packs the blocked continuations behind the
+// banned ids.  Ids outside [0, V1) are dropped here, so every consumer may index a row with what it reads.
+#define DEC_BLK_WAVES 4
+__global__ __launch_bounds__(64 * DEC_BLK_WAVES) void decode_blocklist_k(
+    const int64_t* __restrict__ hist, long s_row, long s_tok, const int* __restrict__ order, int rows, int S, int t, int n,
+    const int* __restrict__ banned, int n_banned, const int* __restrict__ bad, int n_bad, int V1, int* __restrict__ blk,
+    int* __restrict__ blk_n) {
+    __shared__ int hs[DEC_BLK_WAVES][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x * DEC_BLK_WAVES + wave;
+    const bool live = r < rows;
+    const int len = t - 1, width = RFN_DECODE_MAX_IDS + S;
+    int tok = -1;
+    if (live && lane < len) {
+        const long src = order ? order[r] : r;
+        tok = (int)hist[src * s_row + lane * s_tok];
+    }
+    hs[wave][lane] = tok;
+    __syncthreads();
+    if (!live) return;
+    int* out = blk + (long)r * width;
+    const int last = len > 0 ? hs[wave][len - 1] : -1;
+    int count = 0;
+    if (!(len > 0 && last == 0)) {               // a finished row is left alone
+        const int b = lane < n_banned ? banned[lane] : -1;
+        const bool bok = b > 0 && b < V1;
+        unsigned long long m = __ballot(bok);
+        if (bok) out[__popcll(m & ((1ull << lane) - 1ull))] = b;
+        count = __popcll(m);
+        bool hit = false;
+        int nxt = 0;
+        if (n >= 2 && t >= n && lane + n - 1 < len) {
+            hit = true;
+            for (int i = 0; i < n - 1; ++i) hit = hit && hs[wave][lane + i] == hs[wave][len - (n - 1) + i];
+            nxt = hs[wave][lane + n - 1];
+            hit = hit && nxt > 0 && nxt < V1;      // END is never blocked by a repeated n-gram
+        }
+        m = __ballot(hit);
+        if (hit) out[count + __popcll(m & ((1ull << lane) - 1ull))] = nxt;
+        count += __popcll(m);
+        const bool ends_badly = len > 0 && lane < n_bad && bad[lane] == last;
+        if (__ballot(ends_badly)) {
+            if (lane == 0) out[count] = 0;
+            ++count;
+        }
+    }
+    for (int i = count + lane; i < width; i += 64) out[i] = -1;
+    if (lane == 0) blk_n[r] = count;
+}
+extern "C" int rfn_decode_blocklist(const int64_t* hist, int64_t s_row, int64_t s_tok, const int32_t* order, int rows, int S, int t,
+                                    int block_ngram, const int32_t* banned, int n_banned, const int32_t* bad_endings, int n_bad,
+                                    int V1, int32_t* blk, int32_t* blk_n, void* stream) {
+    if (rows < 1 || S < 1 || S > 64 || t < 1 || t > S || V1 < 1) return RFN_ERR_SHAPE;
+    if (block_ngram != 0 && (block_ngram < 2 || block_ngram > 4)) return RFN_ERR_SHAPE;
+    if (n_banned < 0 || n_banned > RFN_DECODE_MAX_IDS || n_bad < 0 || n_bad > RFN_DECODE_MAX_IDS) return RFN_ERR_SHAPE;
+    if (!hist || !blk || !blk_n || (n_banned && !banned) || (n_bad && !bad_endings)) return RFN_ERR_ARG;
+    hipLaunchKernelGGL(decode_blocklist_k, dim3(rfn_cdiv(rows, DEC_BLK_WAVES)), dim3(64 * DEC_BLK_WAVES), 0, (hipStream_t)stream,
+                       hist, (long)s_row, (long)s_tok, order, rows, S, t, block_ngram, banned, n_banned, bad_endings, n_bad, V1, blk,
+                       blk_n);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+// logp[r, blk[r, i]] = -inf for i < blk_n[r]: one wave per row, plain stores (duplicates store the same value twice)
+__global__ __launch_bounds__(64 * DEC_BLK_WAVES) void logp_mask_rows_k(float* __restrict__ logp, long ldl, int rows, int V1,
+                                                                       const int* __restrict__ blk, long ld_blk,
+                                                                       const int* __restrict__ blk_n) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * DEC_BLK_WAVES + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const int nb = blk_n[r];
+    for (int i = lane; i < nb && i < ld_blk; i += 64) {
+        const int id = blk[r * ld_blk + i];
+        if (id >= 0 && id < V1) logp[r * ldl + id] = -INFINITY;
+    }
+}
+extern "C" int rfn_logp_mask_rows(float* logp, int64_t ldl, int rows, int V1, const int32_t* blk, int64_t ld_blk,
+                                  const int32_t* blk_n, void* stream) {
+    if (rows < 1 || V1 < 1 || ldl < V1 || ld_blk < 1) return RFN_ERR_SHAPE;
+    if (!logp || !blk || !blk_n) return RFN_ERR_ARG;
+    hipLaunchKernelGGL(logp_mask_rows_k, dim3(rfn_cdiv(rows, DEC_BLK_WAVES)), dim3(64 * DEC_BLK_WAVES), 0, (hipStream_t)stream, logp,
+                       (long)ldl, rows, V1, blk, (long)ld_blk, blk_n);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

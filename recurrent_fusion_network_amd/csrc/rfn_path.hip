@@ -2025,7 +2025,8 @@ extern "C" int rfn_decoder_prepare(const rfn_dims* d, int B, const float* const*
 static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                              const int64_t* ids, const float* xt, int64_t ld_xt, float* h, float* c, float* logits,
                              float* logp, int64_t ld_logp, void* ws, size_t ws_bytes, uint64_t seed_arg, int step,
-                             void* st, float* topv = nullptr, int32_t* topi = nullptr, int topw = 0, int row_div = 1) {
+                             void* st, float* topv = nullptr, int32_t* topi = nullptr, int topw = 0, int row_div = 1,
+                             const int32_t* blk = nullptr, int64_t ld_blk = 0, const int32_t* blk_n = nullptr) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
@@ -2057,7 +2058,8 @@ static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, 
             if (ld_logp < V1) return RFN_ERR_SHAPE;
             RFN_TRY(rfn_log_softmax_fwd(lg, V1, B, V1, B, ld_logp, 0, logp, st));
         }
-        if (topv) RFN_TRY(rfn_log_softmax_topk(lg, V1, B, V1, topw, topv, topi, st));   // beam search: W best per row, no full rows
+        // beam search: W best per row, no full rows (blk: of the rows masked by their block lists)
+        if (topv) RFN_TRY(rfn_log_softmax_topk_masked(lg, V1, B, V1, topw, blk, ld_blk, blk_n, topv, topi, st));
     }
     return RFN_OK;
 }
@@ -2087,22 +2089,37 @@ extern "C" int rfn_decoder_step_embedded(const rfn_dims* d, int B, const float* 
 // Every step is rfn_decoder_step (embedding K10, cell a5, logit + log-softmax K11) on the same buffers, so the result is
 // bit for bit what the step-by-step host loop gives -- only the host is gone from the loop.  `unf` keeps one row of
 // unfinished flags per step so that the caller applies the reference's early exit (:645) with ONE read-back afterwards.
-extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
-                                const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
-                                float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
-                                int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
-                                void* st) {
+static int check_constraints(const rfn_decode_constraints* cons, int S) {
+    if (!cons) return RFN_OK;
+    if (S < 1 || S > 64) return RFN_ERR_SHAPE;
+    if (cons->block_ngram != 0 && (cons->block_ngram < 2 || cons->block_ngram > 4)) return RFN_ERR_SHAPE;
+    if (cons->n_banned < 0 || cons->n_banned > RFN_DECODE_MAX_IDS || cons->n_bad < 0 || cons->n_bad > RFN_DECODE_MAX_IDS)
+        return RFN_ERR_SHAPE;
+    if (!cons->blk || !cons->blk_n || (cons->n_banned && !cons->banned) || (cons->n_bad && !cons->bad_endings)) return RFN_ERR_ARG;
+    return RFN_OK;
+}
+extern "C" int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
+                                   const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                                   float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                                   int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                                   const rfn_decode_constraints* cons, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed_checked;
     RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
     if (B < 1 || steps < 1 || (mode != 0 && mode != 1)) return RFN_ERR_SHAPE;
     if (!prm || !comb || !cproj || !h || !c || !logp_all || !seq || !seq_lp || !unf || !ids || !ws) return RFN_ERR_ARG;
     if (mode == 1 && !u) return RFN_ERR_ARG;
-    const int V1 = d->V1;
+    const int V1 = d->V1, S = steps - 1;
+    if (cons && S >= 1) RFN_TRY(check_constraints(cons, S));
     if (hipMemsetAsync(ids, 0, (size_t)B * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;   // BOS
     for (int t = 0; t < steps; ++t) {
         if (t >= 1) {
-            const float* prev = logp_all + (long)(t - 1) * ld_t;
+            float* prev = logp_all + (long)(t - 1) * ld_t;
+            if (cons) {   // the row's history is what the picks before this one recorded in seq
+                RFN_TRY(rfn_decode_blocklist(seq, ld_seq, 1, nullptr, B, S, t, cons->block_ngram, cons->banned, cons->n_banned,
+                                             cons->bad_endings, cons->n_bad, V1, cons->blk, cons->blk_n, st));
+                RFN_TRY(rfn_logp_mask_rows(prev, ld_b, B, V1, cons->blk, RFN_DECODE_MAX_IDS + S, cons->blk_n, st));
+            }
             if (mode == 1)   // the draw first: the greedy-pick kernel below then records ITS log-prob and finished flags
                 RFN_TRY(rfn_multinomial_pick(prev, ld_b, B, V1, inv_temperature, u + (long)(t - 1) * B, nullptr, 1.f, ids, 1, st));
             RFN_TRY(rfn_pick_record(prev, ld_b, B, V1, t, mode == 1 ? ids : nullptr, ids, seq + (t - 1), ld_seq, seq_lp + (t - 1),
@@ -2112,6 +2129,14 @@ extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float
                                  st));
     }
     return RFN_OK;
+}
+extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
+                                const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                                float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                                int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                                void* st) {
+    return rfn_decoder_loop_ex(d, B, steps, prm, comb, cproj, h, c, mode, inv_temperature, u, logp_all, ld_b, ld_t, seq, ld_seq,
+                               seq_lp, ld_lp, unf, ids, ws, ws_bytes, seed, nullptr, st);
 }
 
 // The step-wise training decoder with draws between the steps (scheduled sampling :260-270, multinomial sample() with
@@ -2141,11 +2166,11 @@ extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const fl
 // sample_beam's search (misc/RecurrentFusionModel.py:451-531) for all images at once, queued by one call: per step the
 // device-side bookkeeping (rfn_beam_step), the re-gather of the recurrent state rows and one decoder step on the
 // NB * W beam rows.  h / c are ping-ponged with h_alt / c_alt; on return the live state is in h / c again.
-extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
-                             const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
-                             int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
-                             int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
-                             void* ws, size_t ws_bytes, uint64_t seed, void* st) {
+extern "C" int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+                                const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
+                                int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
+                                int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
+                                void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons, void* st) {
     // `logp` holds, per beam row, its W best log-probs and their tokens (2 * W values): the search never looks at more
     // (:463-466), so the full (rows, V+1) log-prob matrix is neither written nor read back
     RFN_TRY(check_dims(d));
@@ -2155,6 +2180,8 @@ extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const floa
     if (!prm || !comb || !cproj || !h || !c || !h_alt || !c_alt || !logp || !ids || !order || !ws) return RFN_ERR_ARG;
     const int rows = NB * W, V1 = d->V1, R = d->R;
     if (W > 32) return RFN_ERR_SHAPE;
+    RFN_TRY(check_constraints(cons, S));
+    if (cons && !beam_seq) return RFN_ERR_ARG;
     float* topv = logp;
     int32_t* topi = (int32_t*)(logp + (size_t)rows * W);
     float *hc = h, *cc = c, *ha = h_alt, *ca = c_alt;
@@ -2169,11 +2196,23 @@ extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const floa
             float* x = hc; hc = ha; ha = x;
             x = cc; cc = ca; ca = x;
         }
+        if (cons)   // the lists for step t + 1, which reads this step's log-probs: rfn_beam_step has forked the beam arrays
+            RFN_TRY(rfn_decode_blocklist(beam_seq, 1, rows, nullptr, rows, S, t + 1, cons->block_ngram, cons->banned, cons->n_banned,
+                                         cons->bad_endings, cons->n_bad, V1, cons->blk, cons->blk_n, st));
         RFN_TRY(decoder_step_impl(d, rows, prm, comb, cproj, ids, nullptr, 0, hc, cc, nullptr, nullptr, 0, ws, ws_bytes, seed, t, st,
-                                  topv, topi, W, W));   // the W rows of an image share its thought vectors (comb / cproj: NB rows)
+                                  topv, topi, W, W,   // the W rows of an image share its thought vectors (comb / cproj: NB rows)
+                                  cons ? cons->blk : nullptr, RFN_DECODE_MAX_IDS + S, cons ? cons->blk_n : nullptr));
     }
     if (hc != h) {   // an odd number of swaps: bring the live state home
         RFN_TRY(mem_batch({{h, hc, (long)rows * R}, {c, cc, (long)rows * R}}, st));
     }
     return RFN_OK;
+}
+extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+                             const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
+                             int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
+                             int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
+                             void* ws, size_t ws_bytes, uint64_t seed, void* st) {
+    return rfn_beam_loop_ex(d, NB, W, S, prm, comb, cproj, h, c, h_alt, c_alt, logp, beam_seq, beam_lp, beam_sum, order, ids, done_seq,
+                            done_lp, done_p, done_n, active, max_done, ws, ws_bytes, seed, nullptr, st);
 }

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .fusion_model import _Stepper, _sorted_done_beams
+from .fusion_model import _Constraints, _length_penalty, _Stepper, _sorted_done_beams
 
 
 class EnsembleDecoder:
@@ -37,11 +37,14 @@ class EnsembleDecoder:
                 raise N.RfnError('ensemble members disagree on vocab_size / seq_length')
 
     @torch.no_grad()
-    def sample(self, fc_feats, att_feats):
+    def sample(self, fc_feats, att_feats, opt={}):
         """Greedy ensemble decode -> (seq (B,<=S), seqLogprobs, logprobs_all (B,<=S+1,V+1)) with the reference's
-        sample() conventions (finished rows masked to 0, early exit when every row has finished)."""
+        sample() conventions (finished rows masked to 0, early exit when every row has finished).  opt: the decoding
+        constraints of RecurrentFusionModel.sample ('block_ngram', 'banned_ids', 'bad_endings'), applied to the averaged
+        log-probs."""
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
+        cons = _Constraints.parse(opt, V1, S)
         steppers = []
         for m in self.models:
             comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
@@ -55,9 +58,14 @@ class EnsembleDecoder:
         seq_lp = torch.zeros(B, S, device=dev)
         unf = torch.zeros(S + 1, B, dtype=torch.int32, device=dev)
         it = torch.zeros(B, dtype=torch.long, device=dev)
+        if cons is not None:
+            cons.bind(B, dev)
         for t in range(S + 1):
             if t >= 1:
                 prev = logp_all[:, t - 1]
+                if cons is not None:
+                    cons.blocklist(seq, seq.stride(0), 1, t)
+                    cons.mask(prev)
                 N.check(N.lib.rfn_greedy_pick(prev.data_ptr(), prev.stride(0), B, V1, t, it.data_ptr(),
                                               seq[:, t - 1].data_ptr(), seq.stride(0), seq_lp[:, t - 1].data_ptr(),
                                               seq_lp.stride(0), unf[t - 1].data_ptr() if t > 1 else None,
@@ -89,6 +97,7 @@ class EnsembleDecoder:
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
         if W > 32 or S > 64 or W > V1:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
+        cons, alpha = _Constraints.parse(opt, V1, S), _length_penalty(opt)
         steppers = []
         for m in self.models:
             comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
@@ -111,6 +120,8 @@ class EnsembleDecoder:
         topi = torch.empty(rows, W, dtype=torch.int32, device=dev)
         logit_sum = torch.empty(rows, V1, device=dev)
         logit_m = torch.empty(rows, V1, device=dev)
+        if cons is not None:
+            cons.bind(rows, dev)
         for t in range(S + 1):
             if t >= 1:
                 N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, max_done, bs.data_ptr(),
@@ -128,8 +139,13 @@ class EnsembleDecoder:
             if self.group is not None:
                 dist.all_reduce(logit_sum, op=dist.ReduceOp.SUM, group=self.group)
             N.check(N.lib.rfn_div_2d(logit_sum.data_ptr(), V1, rows, V1, float(self.n_total), st))
-            N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
-                    'rfn_log_softmax_topk')
-        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done)
+            if cons is not None:     # the lists of step t + 1 from the beam arrays rfn_beam_step_topk has just forked
+                cons.blocklist(bs, 1, rows, t + 1)
+                cons.topk(logit_sum, W, topv, topi)
+            else:
+                N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
+                        'rfn_log_softmax_topk')
+        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done,
+                                                                             alpha)
         return seq, seq_lp, top_seq, top_prob
 

@@ -22,33 +22,34 @@ def unique_image_rows(n_rows, seq_per_img, device=None):
 
 
 def eval_step(model, crit, fc_feats, att_feats, labels, masks, top_words, seq_per_img, reason_weight=1.0,
-              beam_size=1, sample_max=1):
+              beam_size=1, sample_max=1, decode_opt=None):
     """-> dict(loss, seq, seqLogprobs, log_probs_sentence, sample): one iteration of eval_split's loop.
 
     fc_feats / att_feats: lists of caption-row tensors (each image repeated seq_per_img times), labels (rows, S+2),
     masks, top_words as the loader builds them.  `sample` is the full tuple model.sample returned (4 entries for
-    beam_size 1, 5 with beam search: eval_utils.py:198-200)."""
+    beam_size 1, 5 with beam search: eval_utils.py:198-200).  decode_opt: further keys for model.sample's opt -- the decoding
+    constraints 'block_ngram', 'banned_ids', 'bad_endings', 'length_penalty' (INTEGRATION.md)."""
     with torch.no_grad():
         log_prob, top_pred = model(fc_feats, att_feats, labels)
         loss = crit(log_prob, labels[:, 1:], masks[:, 1:], top_pred, top_words, reason_weight)
         rows = unique_image_rows(fc_feats[0].size(0), seq_per_img, fc_feats[0].device)
         fc_u = [f.index_select(0, rows) for f in fc_feats]
         att_u = [a.index_select(0, rows) for a in att_feats]
-        out = model.sample(fc_u, att_u, {'beam_size': beam_size, 'sample_max': sample_max})
+        out = model.sample(fc_u, att_u, dict(decode_opt or {}, beam_size=beam_size, sample_max=sample_max))
         seq, seq_lp = out[0], out[1]
         sentence = torch.sum(seq_lp * (seq > 0).to(seq_lp.dtype), 1)
     return dict(loss=loss, seq=seq, seqLogprobs=seq_lp, log_probs_sentence=sentence, sample=out)
 
 
 def eval_split(model, crit, batches, seq_per_img, vocab, beam_size=1, sample_max=1, reason_weight=1.0, metrics=None,
-               language_eval=None):
+               language_eval=None, decode_opt=None):
     """eval_utils.eval_split's loop with language_eval's Bleu / ROUGE_L / CIDEr computed on the device.
 
     batches: an iterable of dicts with the loader's 'fc_feats', 'att_feats' (lists of caption-row tensors), 'labels', 'masks',
     'top_words' on the model's device and 'gts' (per image, an (n_refs_i, T) id array; or a padded array with 'n_refs').  The
     module is put in eval mode for the loop and left in the mode it was found in.  -> (mean loss over the batches, metrics dict
     of evalcap.LanguageEval.compute()).  The losses stay on the device until the loop has ended; language_eval: a LanguageEval to
-    feed instead of a new one (its per_image() and skipped are then the caller's to read)."""
+    feed instead of a new one (its per_image() and skipped are then the caller's to read).  decode_opt: as eval_step."""
     from .evalcap import METRICS, LanguageEval
     lang = language_eval if language_eval is not None else LanguageEval(vocab, METRICS if metrics is None else metrics)
     was_training = model.training
@@ -57,7 +58,7 @@ def eval_split(model, crit, batches, seq_per_img, vocab, beam_size=1, sample_max
     try:
         for data in batches:
             out = eval_step(model, crit, data['fc_feats'], data['att_feats'], data['labels'], data['masks'], data['top_words'],
-                            seq_per_img, reason_weight, beam_size, sample_max)
+                            seq_per_img, reason_weight, beam_size, sample_max, decode_opt)
             losses.append(out['loss'].detach().reshape(1).to(torch.float64))
             lang.add(out['seq'], data['gts'], data.get('n_refs'))
     finally:

@@ -772,7 +772,12 @@ class RecurrentFusionModel(nn.Module):
         temperature = opt.get('temperature', 1.0)
         if beam_size > 1:
             return self.sample_beam(fc_feats, att_feats, opt)
+        cons = _Constraints.parse(opt, self.vocab_size + 1, self.seq_length)
+        if cons is not None and opt.get('force_ids', None) is not None:
+            raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         want_grad = torch.is_grad_enabled() and not sample_max
+        if cons is not None and want_grad:
+            raise N.RfnError('decoding constraints are not applied to the differentiated sampling pass: sample under no_grad')
         # dropout follows the module's mode, as the reference's nn.Dropout layers do (train_rl.py samples in train()
         # mode)
         train = bool(self.training)
@@ -783,7 +788,7 @@ class RecurrentFusionModel(nn.Module):
         dev = comb.device
         reason_pred = list(reason.unbind(0))
         force = opt.get('force_ids', None)
-        if not sample_max or force is not None:
+        if (not sample_max and cons is None) or force is not None:
             # multinomial (:623-631) or replayed ids.  ONE pass of the training decoder is both the pass that is sampled
             # and, under grad, the pass that is differentiated (train_rl.py:160-166): step-wise with a device-side
             # inverse-CDF draw between steps, or -- when the ids are given -- simply teacher-forced.
@@ -814,12 +819,21 @@ class RecurrentFusionModel(nn.Module):
             seq_lp = torch.zeros(B, S, device=dev)
             unf = torch.zeros(S + 1, B, dtype=torch.int32, device=dev)
             it = torch.empty(B, dtype=torch.long, device=dev)
-            N.check(N.lib.rfn_decoder_loop(C.byref(stepper.d), B, S + 1, stepper.table, stepper.comb.data_ptr(),
-                                           stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), 0, 1.0, None,
-                                           logp_all.data_ptr(), logp_all.stride(0), logp_all.stride(1), seq.data_ptr(),
-                                           seq.stride(0), seq_lp.data_ptr(), seq_lp.stride(0), unf.data_ptr(), it.data_ptr(),
-                                           stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed, N.stream_ptr()),
-                    'rfn_decoder_loop')
+            mode, inv_temp, u = 0, 1.0, None
+            if not sample_max:     # constrained multinomial: the same loop drawing with the uniforms the sampled pass would use
+                r = getattr(self, '_ss_uniforms', None)
+                if r is None:
+                    r = torch.rand(2, S + 1, B, device=dev)
+                elif tuple(r.shape) != (2, S + 1, B) or r.device != dev:
+                    raise N.RfnError('sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S + 1, B)))
+                mode, inv_temp, u = 1, 1.0 / float(temperature), r[0, 1:].contiguous()
+            N.check(N.lib.rfn_decoder_loop_ex(C.byref(stepper.d), B, S + 1, stepper.table, stepper.comb.data_ptr(),
+                                              stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
+                                              N.ptr(u), logp_all.data_ptr(), logp_all.stride(0), logp_all.stride(1),
+                                              seq.data_ptr(), seq.stride(0), seq_lp.data_ptr(), seq_lp.stride(0), unf.data_ptr(),
+                                              it.data_ptr(), stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                              C.byref(cons.bind(B, dev).struct) if cons is not None else None, N.stream_ptr()),
+                    'rfn_decoder_loop_ex')
             # the reference's early exit (:645): stop at the first t >= 1 with no unfinished row
             alive = unf[1:].sum(1).tolist()
         t_stop = next((t for t in range(1, S + 1) if alive[t - 1] == 0), S + 1)
@@ -839,6 +853,9 @@ class RecurrentFusionModel(nn.Module):
         if beam_size > 32 or S > 64:
             raise N.RfnError('beam search supports beam_size <= 32 and seq_length <= 64')
         W = beam_size
+        cons, alpha = _Constraints.parse(opt, V1, S), _length_penalty(opt)
+        if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
+            raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         with torch.no_grad():
             drop = bool(self.training)
             seed = _fresh_seed() if drop else 0
@@ -861,29 +878,113 @@ class RecurrentFusionModel(nn.Module):
             logp = torch.empty(2 * rows * W, device=dev)           # the rows' top-W lists (rfn_beam_loop)
             h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
             # the whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows)
-            N.check(N.lib.rfn_beam_loop(C.byref(stepper.d), B, W, S, stepper.table, stepper.comb.data_ptr(),
-                                        stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
-                                        c_alt.data_ptr(), logp.data_ptr(), bs.data_ptr(), bl.data_ptr(), bsum.data_ptr(),
-                                        order.data_ptr(), ids.data_ptr(), done_seq.data_ptr(), done_lp.data_ptr(),
-                                        done_p.data_ptr(), done_n.data_ptr(), active.data_ptr(), max_done,
-                                        stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed, N.stream_ptr()), 'rfn_beam_loop')
-            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done)
+            N.check(N.lib.rfn_beam_loop_ex(C.byref(stepper.d), B, W, S, stepper.table, stepper.comb.data_ptr(),
+                                           stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
+                                           c_alt.data_ptr(), logp.data_ptr(), bs.data_ptr(), bl.data_ptr(), bsum.data_ptr(),
+                                           order.data_ptr(), ids.data_ptr(), done_seq.data_ptr(), done_lp.data_ptr(),
+                                           done_p.data_ptr(), done_n.data_ptr(), active.data_ptr(), max_done,
+                                           stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                           C.byref(cons.bind(rows, dev).struct) if cons is not None else None, N.stream_ptr()),
+                    'rfn_beam_loop_ex')
+            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, alpha)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch
 
 
-def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done):
+class _Constraints:
+    """The decoding constraints of one call (rfn.h "decoding constraints"): opt['block_ngram'] (0 = off, 2 .. 4),
+    opt['banned_ids'] and opt['bad_endings'] (at most 64 ids each, token 0 never banned).  `parse` returns None when all of
+    them are off, so an unconstrained call issues exactly the launches it always did.  `bind` uploads the id lists (once per
+    call) and allocates the per-row block lists; `blocklist` / `mask` / `topk` are the three kernels for a host-side step
+    loop (the ensemble's), `struct` is what the device loops take."""
+
+    KEYS = ('block_ngram', 'banned_ids', 'bad_endings')
+
+    @staticmethod
+    def _ids(opt, key, V1):
+        v = opt.get(key, None)
+        if v is None:
+            return []
+        ids = sorted(set(int(x) for x in (v.tolist() if torch.is_tensor(v) else v)))
+        if len(ids) > N.DECODE_MAX_IDS:
+            raise ValueError('%s holds %d ids, at most %d are supported' % (key, len(ids), N.DECODE_MAX_IDS))
+        if ids and (ids[0] < 0 or ids[-1] >= V1):
+            raise ValueError('%s must hold token ids in [0, %d)' % (key, V1))
+        return ids
+
+    @classmethod
+    def parse(cls, opt, V1, S):
+        n = int(opt.get('block_ngram', 0) or 0)
+        if n != 0 and not 2 <= n <= 4:
+            raise ValueError('block_ngram must be 0 (off) or 2 .. 4, got %d' % n)
+        banned, bad = cls._ids(opt, 'banned_ids', V1), cls._ids(opt, 'bad_endings', V1)
+        if 0 in banned:
+            raise ValueError('token 0 (END) cannot be banned')
+        if not (n or banned or bad):
+            return None
+        if S > 64:
+            raise N.RfnError('decoding constraints support seq_length <= 64')
+        c = cls()
+        c.n, c.banned, c.bad, c.V1, c.S = n, banned, bad, V1, S
+        return c
+
+    def bind(self, rows, dev):
+        self.rows = rows
+        self.banned_d = torch.tensor(self.banned or [0], dtype=torch.int32, device=dev)
+        self.bad_d = torch.tensor(self.bad or [0], dtype=torch.int32, device=dev)
+        self.blk = torch.empty(rows, N.DECODE_MAX_IDS + self.S, dtype=torch.int32, device=dev)
+        self.blk_n = torch.empty(rows, dtype=torch.int32, device=dev)
+        self.struct = N.DecodeConstraints(self.n, len(self.banned), len(self.bad), 0, self.banned_d.data_ptr(),
+                                          self.bad_d.data_ptr(), self.blk.data_ptr(), self.blk_n.data_ptr())
+        return self
+
+    def blocklist(self, hist, s_row, s_tok, t):
+        """The rows' blocked ids at step t (which picks the t-th token) from their histories (rfn_decode_blocklist)."""
+        N.check(N.lib.rfn_decode_blocklist(hist.data_ptr(), s_row, s_tok, None, self.rows, self.S, t, self.n,
+                                           self.banned_d.data_ptr(), len(self.banned), self.bad_d.data_ptr(), len(self.bad),
+                                           self.V1, self.blk.data_ptr(), self.blk_n.data_ptr(), N.stream_ptr()),
+                'rfn_decode_blocklist')
+
+    def mask(self, logp):
+        N.check(N.lib.rfn_logp_mask_rows(logp.data_ptr(), logp.stride(0), self.rows, self.V1, self.blk.data_ptr(),
+                                         self.blk.stride(0), self.blk_n.data_ptr(), N.stream_ptr()), 'rfn_logp_mask_rows')
+
+    def topk(self, logits, W, topv, topi):
+        N.check(N.lib.rfn_log_softmax_topk_masked(logits.data_ptr(), logits.stride(0), self.rows, self.V1, W, self.blk.data_ptr(),
+                                                  self.blk.stride(0), self.blk_n.data_ptr(), topv.data_ptr(), topi.data_ptr(),
+                                                  N.stream_ptr()), 'rfn_log_softmax_topk_masked')
+
+
+def _length_penalty(opt):
+    alpha = float(opt.get('length_penalty', 0.0) or 0.0)
+    if alpha < 0.0 or alpha != alpha:
+        raise ValueError('length_penalty must be >= 0, got %r' % alpha)
+    return alpha
+
+
+def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0):
     """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
     once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
     per-image Python structures top_seq / top_prob / done_beams: thousands of small objects that need the done counts on
     the host, so they are lists that fill themselves on first access -- a loop that only consumes the returned captions
-    never waits for them)."""
+    never waits for them).
+
+    length_penalty = alpha > 0 ranks by p / len^alpha instead (len: the tokens up to and including the first 0, S without one);
+    ties keep construction order, and `p` / top_prob stay the raw sums.  len^alpha comes from a host table of S + 1 doubles
+    and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly."""
     dev, B = done_p.device, done_p.size(0)
-    key = torch.where(torch.arange(max_done, device=dev)[None, :] < done_n[:, None], -done_p,
-                      torch.full_like(done_p, float('inf')))
+    score = done_p
+    if length_penalty:
+        ended = done_seq == 0
+        first0 = ended.to(torch.int8).argmax(2) + 1                                  # first maximum = first 0
+        length = torch.where(ended.any(2), first0, torch.full_like(first0, S))
+        table = torch.tensor([1.0] + [float(n) ** float(length_penalty) for n in range(1, S + 1)], dtype=torch.float64)
+        score = done_p.double() / table.to(dev)[length]
+    key = torch.where(torch.arange(max_done, device=dev)[None, :] < done_n[:, None], -score,
+                      torch.full_like(score, float('inf')))
     rank = torch.sort(key, dim=1, stable=True).indices
     pick = rank[:, :, None].expand(-1, -1, S)
     s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)

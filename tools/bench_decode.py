@@ -50,6 +50,31 @@ def rl_step_reuse():
     finally:
         model.reuse_prefix = False
 
+def constraints_ab(out_path, rounds=5):
+    """--constraints: config 5 greedy and beam 5 with block_ngram = 3, one banned id and five bad endings against the
+    unconstrained calls (which issue the launches they always did), alternating between the two; medians of `rounds`."""
+    S = cfg.seq_length
+    cons = {'block_ngram': 3, 'banned_ids': [cfg.vocab_size], 'bad_endings': [1, 2, 3, 4, 5]}
+    model.eval()
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=9488, seq=%d, B=%d' % (S, B), 'constraints': cons, 'rounds': rounds}
+    for mode, base, extra in (('greedy', {'sample_max': 1}, 2 * S), ('beam5', {'beam_size': 5}, S)):
+        run = lambda o: timed(lambda: model.sample(fc, att, o), 3)[0] * 1e3  # noqa: E731
+        with torch.no_grad():
+            plain, masked = [], []
+            for _ in range(rounds):
+                plain.append(run(dict(base)))
+                masked.append(run(dict(base, **cons)))
+        res[mode] = {'ms_unconstrained': round(sorted(plain)[rounds // 2], 3), 'ms_constrained': round(sorted(masked)[rounds // 2], 3),
+                     'added_launches_per_call': extra}
+        print(json.dumps({mode: res[mode]}), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
+if '--constraints' in sys.argv:
+    constraints_ab(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'decode_constraints.json'))
+    sys.exit(0)
+
 for name, fn, reps in (('greedy sample', greedy, 5), ('beam=5 sample_beam', beam, 3), ('RL step (sample+baseline+loss+bwd+Adam)', rl_step, 3),
                        ('RL step, model.reuse_prefix (baseline sample reuses stages I/II)', rl_step_reuse, 3)):
     dt, out = timed(fn, reps)
