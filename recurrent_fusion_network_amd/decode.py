@@ -1,0 +1,367 @@
+"""Free-running decoding, shared by RecurrentFusionModel.sample / sample_beam / one_time_step and the EnsembleDecoder: the
+decoder state, the decoding constraints, the loops' buffers, the two device-loop calls and the done-beam ranking.  The model
+is an argument (its `_dims_for`, `_param_table`, `_params_of` and `_decoder_slots` are used); it is never imported here."""
+from __future__ import annotations
+
+import collections.abc
+import ctypes as C
+
+import torch
+
+from . import _native as N
+
+
+class _Stepper:
+    """Free-running decoder state for sample / beam / one_time_step: rfn_decoder_prepare + rfn_decoder_step."""
+
+    def __init__(self, model, comb, h, c, drop=False, seed=0):
+        """drop / seed: apply the decoder dropout masks of (seed, step index) -- the ones rfn_decoder_fwd applies at
+        the same steps -- so a free-running pass in training mode reproduces the teacher-forced pass bit for bit."""
+        self.model = model
+        self.d = model._dims_for(bool(drop))
+        self.seed, self.t = int(seed), 0
+        self.comb = comb.contiguous()
+        self.h, self.c = h.contiguous(), c.contiguous()
+        self.B = self.h.size(0)
+        dev = self.h.device
+        self.table = model._param_table(model._params_of(model._decoder_slots), model._decoder_slots)
+        # the loop-invariant products of the thought vectors: att_2_att_h(comb) and U = comb . z2h.weight^T (rfn.h)
+        self.Bc = self.comb.size(1)          # rows per thought vector: B, or the images of a beam search (B = Bc * beam)
+        self.cproj = torch.empty(N.lib.rfn_decoder_cproj_floats(C.byref(self.d), self.Bc), device=dev)
+        N.check(N.lib.rfn_decoder_prepare(C.byref(self.d), self.Bc, self.table, self.comb.data_ptr(),
+                                          self.cproj.data_ptr(), N.stream_ptr()), 'rfn_decoder_prepare')
+        self.ws_bytes = N.lib.rfn_decoder_step_ws_bytes(C.byref(self.d), self.B)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+
+    def step(self, ids, out=None, want='logp'):
+        """ids: int64 token ids (B,) -- or an already embedded float input (B, E), as the reference's one_time_step."""
+        V1 = self.d.V1
+        if self.Bc != self.B:
+            raise N.RfnError('a stepper whose rows share thought vectors (beam search) is driven by rfn_beam_loop only')
+        if out is None:
+            out = torch.empty(self.B, V1, device=self.h.device)
+        logits_ptr = out.data_ptr() if want == 'logits' else None
+        logp_ptr = out.data_ptr() if want == 'logp' else None
+        if ids.is_floating_point():
+            xt = N.require_cuda_f32(ids, 'xt')
+            if tuple(xt.shape) != (self.B, self.d.E):
+                raise N.RfnError('embedded xt must be (%d, %d), got %s' % (self.B, self.d.E, tuple(xt.shape)))
+            N.check(N.lib.rfn_decoder_step_embedded(C.byref(self.d), self.B, self.table, self.comb.data_ptr(),
+                                                    self.cproj.data_ptr(), xt.data_ptr(), xt.stride(0),
+                                                    self.h.data_ptr(), self.c.data_ptr(), logits_ptr, logp_ptr,
+                                                    out.stride(0), self.ws.data_ptr(), self.ws_bytes, self.seed,
+                                                    self.t, N.stream_ptr()),
+                    'rfn_decoder_step_embedded')
+            self.t += 1
+            return out
+        if ids.dtype != torch.long or not ids.is_contiguous():
+            ids = ids.long().contiguous()
+        N.check(N.lib.rfn_decoder_step(C.byref(self.d), self.B, self.table, self.comb.data_ptr(),
+                                       self.cproj.data_ptr(), ids.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
+                                       logits_ptr, logp_ptr, out.stride(0), self.ws.data_ptr(), self.ws_bytes,
+                                       self.seed, self.t, N.stream_ptr()), 'rfn_decoder_step')
+        self.t += 1
+        return out
+
+    def reorder(self, order):
+        """Row r continues from row order[r] (int32, device): rfn_gather_rows on h and c."""
+        if order.dtype != torch.int32 or not order.is_contiguous():
+            order = order.to(torch.int32).contiguous()
+        h2, c2 = torch.empty_like(self.h), torch.empty_like(self.c)
+        st = N.stream_ptr()
+        N.check(N.lib.rfn_gather_rows(self.h.data_ptr(), h2.data_ptr(), order.data_ptr(), self.B, self.d.R, st), 'rfn_gather_rows')
+        N.check(N.lib.rfn_gather_rows(self.c.data_ptr(), c2.data_ptr(), order.data_ptr(), self.B, self.d.R, st), 'rfn_gather_rows')
+        self.h, self.c = h2, c2
+
+
+def early_exit(alive, S):
+    """The reference's early exit (misc/RecurrentFusionModel.py:645): the first t >= 1 with no unfinished row, S + 1 without
+    one.  alive[t - 1]: the rows still unfinished after the t-th token (a host list)."""
+    return next((t for t in range(1, S + 1) if alive[t - 1] == 0), S + 1)
+
+
+class GreedyBuffers:
+    """What a greedy / sampled loop over B rows writes.  `it` is the token fed next: rfn_decoder_loop sets it itself, a
+    host-stepped loop feeds it at t = 0 and asks for `bos=True` (zeros)."""
+
+    def __init__(self, B, S, V1, dev, bos=False):
+        self.S = S
+        self.logp_all = torch.empty(B, S + 1, V1, device=dev)
+        self.seq = torch.zeros(B, S, dtype=torch.long, device=dev)
+        self.seq_lp = torch.zeros(B, S, device=dev)
+        self.unf = torch.zeros(S + 1, B, dtype=torch.int32, device=dev)
+        self.it = (torch.zeros if bos else torch.empty)(B, dtype=torch.long, device=dev)
+
+    def read_back(self):
+        """The call's one synchronisation: the unfinished counts come to the host -> (seq, seq_lp, logp_all) cut there."""
+        t_stop = early_exit(self.unf[1:].sum(1).tolist(), self.S)
+        return self.seq[:, :t_stop - 1], self.seq_lp[:, :t_stop - 1], self.logp_all[:, :t_stop].contiguous()
+
+
+def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons):
+    """The whole free-running loop (pick, embed, cell, logit, log-softmax) in one call.  mode 0: greedy; 1: draw with the
+    uniforms u (S, B) at inverse temperature inv_temp.  cons: a parsed _Constraints or None."""
+    b, B = bufs, stepper.B
+    N.check(N.lib.rfn_decoder_loop_ex(C.byref(stepper.d), B, b.S + 1, stepper.table, stepper.comb.data_ptr(),
+                                      stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
+                                      N.ptr(u), b.logp_all.data_ptr(), b.logp_all.stride(0), b.logp_all.stride(1),
+                                      b.seq.data_ptr(), b.seq.stride(0), b.seq_lp.data_ptr(), b.seq_lp.stride(0), b.unf.data_ptr(),
+                                      b.it.data_ptr(), stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                      C.byref(cons.bind(B, stepper.h.device).struct) if cons is not None else None,
+                                      N.stream_ptr()), 'rfn_decoder_loop_ex')
+
+
+class BeamBuffers:
+    """The state of a beam search over B images x W beams x S steps.  The rows' top-W lists are uninitialised storage, as
+    one float buffer (`top_flat`, rfn_beam_loop) or as values and indices (`top_lists`, a host-stepped search)."""
+
+    def __init__(self, B, W, S, dev):
+        self.B, self.W, self.S, self.dev = B, W, S, dev
+        self.rows, self.max_done = rows, max_done = B * W, W * S
+        self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
+        self.bl = torch.zeros(S, B, W, device=dev)
+        self.bsum = torch.zeros(B, W, device=dev)
+        self.order = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.ids = torch.zeros(rows, dtype=torch.long, device=dev)
+        self.done_seq = torch.zeros(B, max_done, S, dtype=torch.long, device=dev)
+        self.done_lp = torch.zeros(B, max_done, S, device=dev)
+        self.done_p = torch.zeros(B, max_done, device=dev)
+        self.done_n = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.active = torch.ones(B, dtype=torch.int32, device=dev)
+
+    def top_flat(self):
+        return torch.empty(2 * self.rows * self.W, device=self.dev)
+
+    def top_lists(self):
+        return torch.empty(self.rows, self.W, device=self.dev), torch.empty(self.rows, self.W, dtype=torch.int32, device=self.dev)
+
+
+def run_beam_loop(stepper, bufs, cons):
+    """The whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows)."""
+    b, logp = bufs, bufs.top_flat()
+    h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
+    N.check(N.lib.rfn_beam_loop_ex(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
+                                   stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
+                                   c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(),
+                                   b.order.data_ptr(), b.ids.data_ptr(), b.done_seq.data_ptr(), b.done_lp.data_ptr(),
+                                   b.done_p.data_ptr(), b.done_n.data_ptr(), b.active.data_ptr(), b.max_done,
+                                   stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                   C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None, N.stream_ptr()),
+            'rfn_beam_loop_ex')
+
+
+class _Constraints:
+    """The decoding constraints of one call (rfn.h "decoding constraints"): opt['block_ngram'] (0 = off, 2 .. 4),
+    opt['banned_ids'] and opt['bad_endings'] (at most 64 ids each, token 0 never banned).  `parse` returns None when all of
+    them are off, so an unconstrained call issues exactly the launches it always did.  `bind` uploads the id lists (once per
+    call) and allocates the per-row block lists; `blocklist` / `mask` / `topk` are the three kernels for a host-side step
+    loop (the ensemble's), `struct` is what the device loops take."""
+
+    KEYS = ('block_ngram', 'banned_ids', 'bad_endings')
+
+    @staticmethod
+    def _ids(opt, key, V1):
+        v = opt.get(key, None)
+        if v is None:
+            return []
+        ids = sorted(set(int(x) for x in (v.tolist() if torch.is_tensor(v) else v)))
+        if len(ids) > N.DECODE_MAX_IDS:
+            raise ValueError('%s holds %d ids, at most %d are supported' % (key, len(ids), N.DECODE_MAX_IDS))
+        if ids and (ids[0] < 0 or ids[-1] >= V1):
+            raise ValueError('%s must hold token ids in [0, %d)' % (key, V1))
+        return ids
+
+    @classmethod
+    def parse(cls, opt, V1, S):
+        n = int(opt.get('block_ngram', 0) or 0)
+        if n != 0 and not 2 <= n <= 4:
+            raise ValueError('block_ngram must be 0 (off) or 2 .. 4, got %d' % n)
+        banned, bad = cls._ids(opt, 'banned_ids', V1), cls._ids(opt, 'bad_endings', V1)
+        if 0 in banned:
+            raise ValueError('token 0 (END) cannot be banned')
+        if not (n or banned or bad):
+            return None
+        if S > 64:
+            raise N.RfnError('decoding constraints support seq_length <= 64')
+        c = cls()
+        c.n, c.banned, c.bad, c.V1, c.S = n, banned, bad, V1, S
+        return c
+
+    def bind(self, rows, dev):
+        self.rows = rows
+        self.banned_d = torch.tensor(self.banned or [0], dtype=torch.int32, device=dev)
+        self.bad_d = torch.tensor(self.bad or [0], dtype=torch.int32, device=dev)
+        self.blk = torch.empty(rows, N.DECODE_MAX_IDS + self.S, dtype=torch.int32, device=dev)
+        self.blk_n = torch.empty(rows, dtype=torch.int32, device=dev)
+        self.struct = N.DecodeConstraints(self.n, len(self.banned), len(self.bad), 0, self.banned_d.data_ptr(),
+                                          self.bad_d.data_ptr(), self.blk.data_ptr(), self.blk_n.data_ptr())
+        return self
+
+    def blocklist(self, hist, s_row, s_tok, t):
+        """The rows' blocked ids at step t (which picks the t-th token) from their histories (rfn_decode_blocklist)."""
+        N.check(N.lib.rfn_decode_blocklist(hist.data_ptr(), s_row, s_tok, None, self.rows, self.S, t, self.n,
+                                           self.banned_d.data_ptr(), len(self.banned), self.bad_d.data_ptr(), len(self.bad),
+                                           self.V1, self.blk.data_ptr(), self.blk_n.data_ptr(), N.stream_ptr()),
+                'rfn_decode_blocklist')
+
+    def mask(self, logp):
+        N.check(N.lib.rfn_logp_mask_rows(logp.data_ptr(), logp.stride(0), self.rows, self.V1, self.blk.data_ptr(),
+                                         self.blk.stride(0), self.blk_n.data_ptr(), N.stream_ptr()), 'rfn_logp_mask_rows')
+
+    def topk(self, logits, W, topv, topi):
+        N.check(N.lib.rfn_log_softmax_topk_masked(logits.data_ptr(), logits.stride(0), self.rows, self.V1, W, self.blk.data_ptr(),
+                                                  self.blk.stride(0), self.blk_n.data_ptr(), topv.data_ptr(), topi.data_ptr(),
+                                                  N.stream_ptr()), 'rfn_log_softmax_topk_masked')
+
+
+def _length_penalty(opt):
+    alpha = float(opt.get('length_penalty', 0.0) or 0.0)
+    if alpha < 0.0 or alpha != alpha:
+        raise ValueError('length_penalty must be >= 0, got %r' % alpha)
+    return alpha
+
+
+def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0):
+    """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
+    once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
+    GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
+    per-image Python structures top_seq / top_prob / done_beams: thousands of small objects that need the done counts on
+    the host, so they are lists that fill themselves on first access -- a loop that only consumes the returned captions
+    never waits for them).
+
+    length_penalty = alpha > 0 ranks by p / len^alpha instead (len: the tokens up to and including the first 0, S without one);
+    ties keep construction order, and `p` / top_prob stay the raw sums.  len^alpha comes from a host table of S + 1 doubles
+    and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly."""
+    dev, B = done_p.device, done_p.size(0)
+    score = done_p
+    if length_penalty:
+        ended = done_seq == 0
+        first0 = ended.to(torch.int8).argmax(2) + 1                                  # first maximum = first 0
+        length = torch.where(ended.any(2), first0, torch.full_like(first0, S))
+        table = torch.tensor([1.0] + [float(n) ** float(length_penalty) for n in range(1, S + 1)], dtype=torch.float64)
+        score = done_p.double() / table.to(dev)[length]
+    key = torch.where(torch.arange(max_done, device=dev)[None, :] < done_n[:, None], -score,
+                      torch.full_like(score, float('inf')))
+    rank = torch.sort(key, dim=1, stable=True).indices
+    pick = rank[:, :, None].expand(-1, -1, S)
+    s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
+    src = _BeamResults(s_all, l_all, p_all, done_n)
+    return (s_all[:, 0].contiguous(), l_all[:, 0].contiguous(), _LazyList(B, lambda: src.top_seq()),
+            _LazyList(B, lambda: src.top_prob()), _LazyList(B, lambda: src.done_beams()))
+
+
+class _BeamResults:
+    """Host copies of the sorted done beams, fetched once, on demand."""
+
+    def __init__(self, s_all, l_all, p_all, done_n):
+        self._dev = (s_all, l_all, p_all, done_n)
+        self._host = None
+
+    def host(self):
+        if self._host is None:
+            s_all, l_all, p_all, done_n = self._dev
+            self._host = (s_all.cpu(), l_all.cpu(), p_all.cpu().tolist(), done_n.cpu().tolist())
+        return self._host
+
+    def top_seq(self):
+        s_all, _, _, counts = self.host()
+        return [s_all[k, :n] for k, n in enumerate(counts)]
+
+    def top_prob(self):
+        _, _, probs, counts = self.host()
+        return [probs[k][:n] for k, n in enumerate(counts)]
+
+    def done_beams(self):
+        """misc/RecurrentFusionModel.py:529-531: per image the list of {'seq', 'logps', 'p'} dicts, best first."""
+        s_all, l_all, probs, counts = self.host()
+        return [[{'seq': a, 'logps': b_, 'p': c_} for a, b_, c_ in zip(s_all[k, :n].unbind(0), l_all[k, :n].unbind(0), probs[k][:n])]
+                for k, n in enumerate(counts)]
+
+
+class _LazyList(collections.abc.MutableSequence):
+    """A sequence of known length whose entries are produced (all at once) by `fill()` the first time anything but its
+    length is asked for.  Deliberately NOT a subclass of `list`: C fast paths that take a list subclass (`PySequence_Fast`,
+    `PyList_GET_ITEM`: json's C encoder, `str.join`, some torch / numpy converters) read the list's item array directly and
+    would see unfilled placeholders without any Python-level hook running.  As a plain `MutableSequence` every consumer goes
+    through `__getitem__` / `__iter__` / `__len__` (which fill first), and a consumer that insists on a real list fails
+    loudly (`json.dumps(x)` raises TypeError; `json.dumps(list(x))` / `x.materialize()` is the spelling).  Indexing,
+    slicing, iteration, comparison with lists, `+`, `in`, `reversed`, `sorted`, printing, copying, pickling (as a plain
+    list) and in-place edits behave like the list the reference returns (misc/RecurrentFusionModel.py:529-543)."""
+
+    __slots__ = ('_n', '_fill', '_items')
+    __hash__ = None
+
+    def __init__(self, n, fill):
+        self._n, self._fill, self._items = int(n), fill, None
+
+    def materialize(self):
+        """The plain `list` behind this object (filled now if it was not)."""
+        if self._items is None:
+            fill, self._fill = self._fill, None
+            items = list(fill())
+            if len(items) != self._n:
+                raise N.RfnError('lazy list promised %d entries, its producer made %d' % (self._n, len(items)))
+            self._items = items
+        return self._items
+
+    def __len__(self):
+        return self._n if self._items is None else len(self._items)
+
+    def __getitem__(self, i):
+        return self.materialize()[i]
+
+    def __setitem__(self, i, v):
+        self.materialize()[i] = v
+
+    def __delitem__(self, i):
+        del self.materialize()[i]
+
+    def insert(self, i, v):
+        self.materialize().insert(i, v)
+
+    def __iter__(self):
+        return iter(self.materialize())
+
+    def __repr__(self):
+        return repr(self.materialize())
+
+    def _other(self, other):
+        return other.materialize() if isinstance(other, _LazyList) else other
+
+    def __eq__(self, other):
+        return self.materialize() == self._other(other)
+
+    def __ne__(self, other):
+        return self.materialize() != self._other(other)
+
+    def __lt__(self, other):
+        return self.materialize() < self._other(other)
+
+    def __le__(self, other):
+        return self.materialize() <= self._other(other)
+
+    def __gt__(self, other):
+        return self.materialize() > self._other(other)
+
+    def __ge__(self, other):
+        return self.materialize() >= self._other(other)
+
+    def __add__(self, other):
+        return self.materialize() + list(self._other(other))
+
+    def __radd__(self, other):
+        return list(other) + self.materialize()
+
+    def __mul__(self, k):
+        return self.materialize() * k
+
+    __rmul__ = __mul__
+
+    def copy(self):
+        return list(self.materialize())
+
+    def sort(self, **kw):
+        self.materialize().sort(**kw)
+
+    def __reduce_ex__(self, protocol):
+        return (list, (list(self.materialize()),))

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .fusion_model import _Constraints, _length_penalty, _Stepper, _sorted_done_beams
+from .decode import BeamBuffers, GreedyBuffers, _Constraints, _length_penalty, _sorted_done_beams, _Stepper
 
 
 class EnsembleDecoder:
@@ -36,6 +36,19 @@ class EnsembleDecoder:
             if m.vocab_size != m0.vocab_size or m.seq_length != m0.seq_length:
                 raise N.RfnError('ensemble members disagree on vocab_size / seq_length')
 
+    def _averaged_step(self, steppers, ids, logit_sum, logit_m):
+        """One decoder step of every member on the SAME tokens (each embeds them with its own table): logit_sum becomes the
+        members' mean pre-softmax logits, over all ranks of the group."""
+        rows, V1 = logit_sum.shape
+        st = N.stream_ptr()
+        for j, sp in enumerate(steppers):
+            sp.step(ids, out=logit_sum if j == 0 else logit_m, want='logits')
+            if j:
+                N.check(N.lib.rfn_axpby_2d(1.0, logit_m.data_ptr(), V1, 1.0, logit_sum.data_ptr(), V1, rows, V1, st))
+        if self.group is not None:
+            dist.all_reduce(logit_sum, op=dist.ReduceOp.SUM, group=self.group)
+        N.check(N.lib.rfn_div_2d(logit_sum.data_ptr(), V1, rows, V1, float(self.n_total), st))
+
     @torch.no_grad()
     def sample(self, fc_feats, att_feats, opt={}):
         """Greedy ensemble decode -> (seq (B,<=S), seqLogprobs, logprobs_all (B,<=S+1,V+1)) with the reference's
@@ -53,11 +66,8 @@ class EnsembleDecoder:
         st = N.stream_ptr()
         logit_sum = torch.empty(B, V1, device=dev)
         logit_m = torch.empty(B, V1, device=dev)
-        logp_all = torch.empty(B, S + 1, V1, device=dev)
-        seq = torch.zeros(B, S, dtype=torch.long, device=dev)
-        seq_lp = torch.zeros(B, S, device=dev)
-        unf = torch.zeros(S + 1, B, dtype=torch.int32, device=dev)
-        it = torch.zeros(B, dtype=torch.long, device=dev)
+        bufs = GreedyBuffers(B, S, V1, dev, bos=True)      # `it` = the BOS token fed at t = 0
+        logp_all, seq, seq_lp, unf, it = bufs.logp_all, bufs.seq, bufs.seq_lp, bufs.unf, bufs.it
         if cons is not None:
             cons.bind(B, dev)
         for t in range(S + 1):
@@ -70,22 +80,10 @@ class EnsembleDecoder:
                                               seq[:, t - 1].data_ptr(), seq.stride(0), seq_lp[:, t - 1].data_ptr(),
                                               seq_lp.stride(0), unf[t - 1].data_ptr() if t > 1 else None,
                                               unf[t].data_ptr(), st), 'rfn_greedy_pick')
-            for j, sp in enumerate(steppers):          # every member embeds the SAME token with its own table
-                sp.step(it, out=logit_sum if j == 0 else logit_m, want='logits')
-                if j:
-                    N.check(N.lib.rfn_axpby_2d(1.0, logit_m.data_ptr(), V1, 1.0, logit_sum.data_ptr(), V1, B, V1, st))
-            if self.group is not None:
-                dist.all_reduce(logit_sum, op=dist.ReduceOp.SUM, group=self.group)
-            N.check(N.lib.rfn_div_2d(logit_sum.data_ptr(), V1, B, V1, float(self.n_total), st))
+            self._averaged_step(steppers, it, logit_sum, logit_m)
             out = logp_all[:, t]
             N.check(N.lib.rfn_log_softmax_fwd(logit_sum.data_ptr(), V1, B, V1, B, out.stride(0), 0, out.data_ptr(), st))
-        alive = unf[1:].sum(1).tolist()
-        t_stop = S + 1
-        for t in range(1, S + 1):
-            if alive[t - 1] == 0:
-                t_stop = t
-                break
-        return seq[:, :t_stop - 1], seq_lp[:, :t_stop - 1], logp_all[:, :t_stop].contiguous()
+        return bufs.read_back()        # nothing is read back before this: the call synchronises here, once
 
     @torch.no_grad()
     def sample_beam(self, fc_feats, att_feats, opt={}):
@@ -105,47 +103,31 @@ class EnsembleDecoder:
                                      h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous()))
         dev = steppers[0].h.device
         st = N.stream_ptr()
-        rows, max_done = B * W, W * S
-        bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
-        bl = torch.zeros(S, B, W, device=dev)
-        bsum = torch.zeros(B, W, device=dev)
-        order = torch.zeros(rows, dtype=torch.int32, device=dev)
-        ids = torch.zeros(rows, dtype=torch.long, device=dev)
-        done_seq = torch.zeros(B, max_done, S, dtype=torch.long, device=dev)
-        done_lp = torch.zeros(B, max_done, S, device=dev)
-        done_p = torch.zeros(B, max_done, device=dev)
-        done_n = torch.zeros(B, dtype=torch.int32, device=dev)
-        active = torch.ones(B, dtype=torch.int32, device=dev)
-        topv = torch.empty(rows, W, device=dev)
-        topi = torch.empty(rows, W, dtype=torch.int32, device=dev)
+        b = BeamBuffers(B, W, S, dev)
+        rows = b.rows
+        topv, topi = b.top_lists()
         logit_sum = torch.empty(rows, V1, device=dev)
         logit_m = torch.empty(rows, V1, device=dev)
         if cons is not None:
             cons.bind(rows, dev)
         for t in range(S + 1):
             if t >= 1:
-                N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, max_done, bs.data_ptr(),
-                                                 bl.data_ptr(), bsum.data_ptr(), order.data_ptr(), ids.data_ptr(),
-                                                 done_seq.data_ptr(), done_lp.data_ptr(), done_p.data_ptr(), done_n.data_ptr(),
-                                                 active.data_ptr(), st), 'rfn_beam_step_topk')
+                N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, b.max_done, b.bs.data_ptr(),
+                                                 b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
+                                                 b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(),
+                                                 b.done_n.data_ptr(), b.active.data_ptr(), st), 'rfn_beam_step_topk')
                 if t == S:
                     break                      # the reference runs one more decoder step whose output is never used
                 for sp in steppers:
-                    sp.reorder(order)
-            for j, sp in enumerate(steppers):
-                sp.step(ids, out=logit_sum if j == 0 else logit_m, want='logits')
-                if j:
-                    N.check(N.lib.rfn_axpby_2d(1.0, logit_m.data_ptr(), V1, 1.0, logit_sum.data_ptr(), V1, rows, V1, st))
-            if self.group is not None:
-                dist.all_reduce(logit_sum, op=dist.ReduceOp.SUM, group=self.group)
-            N.check(N.lib.rfn_div_2d(logit_sum.data_ptr(), V1, rows, V1, float(self.n_total), st))
+                    sp.reorder(b.order)
+            self._averaged_step(steppers, b.ids, logit_sum, logit_m)
             if cons is not None:     # the lists of step t + 1 from the beam arrays rfn_beam_step_topk has just forked
-                cons.blocklist(bs, 1, rows, t + 1)
+                cons.blocklist(b.bs, 1, rows, t + 1)
                 cons.topk(logit_sum, W, topv, topi)
             else:
                 N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
                         'rfn_log_softmax_topk')
-        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done,
-                                                                             alpha)
+        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b.done_seq, b.done_lp, b.done_p, b.done_n, S,
+                                                                             b.max_done, alpha)
         return seq, seq_lp, top_seq, top_prob
 

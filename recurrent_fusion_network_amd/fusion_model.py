@@ -12,7 +12,6 @@ parameter names (``review_steps_individual.{t}.lstm.{i}.att_model.att_2_att_h.we
 """
 from __future__ import annotations
 
-import collections.abc
 import ctypes as C
 import re
 import weakref
@@ -22,6 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _LazyList, _length_penalty, _sorted_done_beams, _Stepper,
+                     early_exit, run_beam_loop, run_greedy_loop)
 
 _INIT = 0.1
 
@@ -784,61 +785,55 @@ class RecurrentFusionModel(nn.Module):
         seed = self._step_seed(train)
         with torch.set_grad_enabled(want_grad):
             comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
-        B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
-        dev = comb.device
         reason_pred = list(reason.unbind(0))
         force = opt.get('force_ids', None)
         if (not sample_max and cons is None) or force is not None:
-            # multinomial (:623-631) or replayed ids.  ONE pass of the training decoder is both the pass that is sampled
-            # and, under grad, the pass that is differentiated (train_rl.py:160-166): step-wise with a device-side
-            # inverse-CDF draw between steps, or -- when the ids are given -- simply teacher-forced.
-            with torch.set_grad_enabled(want_grad):
-                if force is not None:
-                    raw = torch.zeros(B, S + 1, dtype=torch.long, device=dev)      # column t = token fed at step t
-                    raw[:, 1:] = force[:, :S].to(dev)
-                else:
-                    logp_full, raw = self._decode_sampled(comb, h, c, train, seed, S + 1, 1.0 / float(temperature))
-                tok = raw[:, 1:]
-                unf = torch.cumprod((tok > 0).long(), 1)                           # a row is finished after its first 0
-                seq = tok * unf
-                alive = unf.sum(0).tolist()                                        # one read-back: the early exit (:645)
-                t_stop = next((t for t in range(1, S + 1) if alive[t - 1] == 0), S + 1)
-                n_seq = t_stop - 1
-                if force is not None:
-                    logp = self._decode_teacher_forced(raw[:, :t_stop].contiguous(), comb, h, c, train, seed)
-                else:
-                    logp = logp_full[:, :t_stop]
-                seq_lp = logp[:, :n_seq].gather(2, tok[:, :n_seq].unsqueeze(2)).squeeze(2)
-            if getattr(self, '_trace_ss', False):
-                self._sample_ids = raw[:, :t_stop].clone()       # test hook: the tokens the pass fed
-            return seq[:, :n_seq], seq_lp, logp.contiguous(), reason_pred
-        with torch.no_grad():      # greedy: the whole free-running loop (pick, embed, cell, logit, log-softmax) in one call
-            stepper = _Stepper(self, comb.detach(), h.detach().clone(), c.detach().clone(), train, seed)
-            logp_all = torch.empty(B, S + 1, V1, device=dev)
-            seq = torch.zeros(B, S, dtype=torch.long, device=dev)
-            seq_lp = torch.zeros(B, S, device=dev)
-            unf = torch.zeros(S + 1, B, dtype=torch.int32, device=dev)
-            it = torch.empty(B, dtype=torch.long, device=dev)
-            mode, inv_temp, u = 0, 1.0, None
-            if not sample_max:     # constrained multinomial: the same loop drawing with the uniforms the sampled pass would use
-                r = getattr(self, '_ss_uniforms', None)
-                if r is None:
-                    r = torch.rand(2, S + 1, B, device=dev)
-                elif tuple(r.shape) != (2, S + 1, B) or r.device != dev:
-                    raise N.RfnError('sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S + 1, B)))
-                mode, inv_temp, u = 1, 1.0 / float(temperature), r[0, 1:].contiguous()
-            N.check(N.lib.rfn_decoder_loop_ex(C.byref(stepper.d), B, S + 1, stepper.table, stepper.comb.data_ptr(),
-                                              stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
-                                              N.ptr(u), logp_all.data_ptr(), logp_all.stride(0), logp_all.stride(1),
-                                              seq.data_ptr(), seq.stride(0), seq_lp.data_ptr(), seq_lp.stride(0), unf.data_ptr(),
-                                              it.data_ptr(), stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
-                                              C.byref(cons.bind(B, dev).struct) if cons is not None else None, N.stream_ptr()),
-                    'rfn_decoder_loop_ex')
-            # the reference's early exit (:645): stop at the first t >= 1 with no unfinished row
-            alive = unf[1:].sum(1).tolist()
-        t_stop = next((t for t in range(1, S + 1) if alive[t - 1] == 0), S + 1)
-        n_seq = t_stop - 1
-        return seq[:, :n_seq], seq_lp[:, :n_seq], logp_all[:, :t_stop].contiguous(), reason_pred
+            out = self._sample_replayed(comb, h, c, train, seed, want_grad, temperature, force)
+        else:
+            out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons)
+        return (*out, reason_pred)
+
+    def _sample_replayed(self, comb, h, c, train, seed, want_grad, temperature, force):
+        """Multinomial (:623-631) or replayed ids -> (seq, seq_lp, logp).  ONE pass of the training decoder is both the pass
+        that is sampled and, under grad, the pass that is differentiated (train_rl.py:160-166): step-wise with a device-side
+        inverse-CDF draw between steps, or -- when the ids are given -- simply teacher-forced."""
+        B, S, dev = h.size(0), self.seq_length, comb.device
+        with torch.set_grad_enabled(want_grad):
+            if force is not None:
+                raw = torch.zeros(B, S + 1, dtype=torch.long, device=dev)      # column t = token fed at step t
+                raw[:, 1:] = force[:, :S].to(dev)
+            else:
+                logp_full, raw = self._decode_sampled(comb, h, c, train, seed, S + 1, 1.0 / float(temperature))
+            tok = raw[:, 1:]
+            unf = torch.cumprod((tok > 0).long(), 1)                           # a row is finished after its first 0
+            seq = tok * unf
+            t_stop = early_exit(unf.sum(0).tolist(), S)                        # one read-back
+            n_seq = t_stop - 1
+            if force is not None:
+                logp = self._decode_teacher_forced(raw[:, :t_stop].contiguous(), comb, h, c, train, seed)
+            else:
+                logp = logp_full[:, :t_stop]
+            seq_lp = logp[:, :n_seq].gather(2, tok[:, :n_seq].unsqueeze(2)).squeeze(2)
+        if getattr(self, '_trace_ss', False):
+            self._sample_ids = raw[:, :t_stop].clone()       # test hook: the tokens the pass fed
+        return seq[:, :n_seq], seq_lp, logp.contiguous()
+
+    @torch.no_grad()
+    def _sample_device_loop(self, comb, h, c, train, seed, sample_max, temperature, cons):
+        """Greedy, or constrained multinomial: the whole free-running loop in one call -> (seq, seq_lp, logp)."""
+        B, S, dev = h.size(0), self.seq_length, comb.device
+        stepper = _Stepper(self, comb.detach(), h.detach().clone(), c.detach().clone(), train, seed)
+        bufs = GreedyBuffers(B, S, self.vocab_size + 1, dev)
+        mode, inv_temp, u = 0, 1.0, None
+        if not sample_max:     # the same loop drawing with the uniforms the sampled pass would use
+            r = getattr(self, '_ss_uniforms', None)
+            if r is None:
+                r = torch.rand(2, S + 1, B, device=dev)
+            elif tuple(r.shape) != (2, S + 1, B) or r.device != dev:
+                raise N.RfnError('sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S + 1, B)))
+            mode, inv_temp, u = 1, 1.0 / float(temperature), r[0, 1:].contiguous()
+        run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons)
+        return bufs.read_back()        # waits for the loop: the call's one read-back
 
     def sample_beam(self, fc_feats, att_feats, opt={}):
         """misc/RecurrentFusionModel.py:352-543, batched and device-resident.
@@ -864,316 +859,17 @@ class RecurrentFusionModel(nn.Module):
             # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
             stepper = _Stepper(self, comb_b, h_b.repeat_interleave(W, dim=0).contiguous(),
                                c_b.repeat_interleave(W, dim=0).contiguous(), drop, seed)
-            rows, max_done = B * W, W * S
-            bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
-            bl = torch.zeros(S, B, W, device=dev)
-            bsum = torch.zeros(B, W, device=dev)
-            order = torch.zeros(rows, dtype=torch.int32, device=dev)
-            ids = torch.zeros(rows, dtype=torch.long, device=dev)
-            done_seq = torch.zeros(B, max_done, S, dtype=torch.long, device=dev)
-            done_lp = torch.zeros(B, max_done, S, device=dev)
-            done_p = torch.zeros(B, max_done, device=dev)
-            done_n = torch.zeros(B, dtype=torch.int32, device=dev)
-            active = torch.ones(B, dtype=torch.int32, device=dev)
-            logp = torch.empty(2 * rows * W, device=dev)           # the rows' top-W lists (rfn_beam_loop)
-            h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
-            # the whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows)
-            N.check(N.lib.rfn_beam_loop_ex(C.byref(stepper.d), B, W, S, stepper.table, stepper.comb.data_ptr(),
-                                           stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
-                                           c_alt.data_ptr(), logp.data_ptr(), bs.data_ptr(), bl.data_ptr(), bsum.data_ptr(),
-                                           order.data_ptr(), ids.data_ptr(), done_seq.data_ptr(), done_lp.data_ptr(),
-                                           done_p.data_ptr(), done_n.data_ptr(), active.data_ptr(), max_done,
-                                           stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
-                                           C.byref(cons.bind(rows, dev).struct) if cons is not None else None, N.stream_ptr()),
-                    'rfn_beam_loop_ex')
-            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, alpha)
+            bufs = BeamBuffers(B, W, S, dev)
+            run_beam_loop(stepper, bufs, cons)
+            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
+                                                                            S, bufs.max_done, alpha)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch
 
 
-class _Constraints:
-    """The decoding constraints of one call (rfn.h "decoding constraints"): opt['block_ngram'] (0 = off, 2 .. 4),
-    opt['banned_ids'] and opt['bad_endings'] (at most 64 ids each, token 0 never banned).  `parse` returns None when all of
-    them are off, so an unconstrained call issues exactly the launches it always did.  `bind` uploads the id lists (once per
-    call) and allocates the per-row block lists; `blocklist` / `mask` / `topk` are the three kernels for a host-side step
-    loop (the ensemble's), `struct` is what the device loops take."""
-
-    KEYS = ('block_ngram', 'banned_ids', 'bad_endings')
-
-    @staticmethod
-    def _ids(opt, key, V1):
-        v = opt.get(key, None)
-        if v is None:
-            return []
-        ids = sorted(set(int(x) for x in (v.tolist() if torch.is_tensor(v) else v)))
-        if len(ids) > N.DECODE_MAX_IDS:
-            raise ValueError('%s holds %d ids, at most %d are supported' % (key, len(ids), N.DECODE_MAX_IDS))
-        if ids and (ids[0] < 0 or ids[-1] >= V1):
-            raise ValueError('%s must hold token ids in [0, %d)' % (key, V1))
-        return ids
-
-    @classmethod
-    def parse(cls, opt, V1, S):
-        n = int(opt.get('block_ngram', 0) or 0)
-        if n != 0 and not 2 <= n <= 4:
-            raise ValueError('block_ngram must be 0 (off) or 2 .. 4, got %d' % n)
-        banned, bad = cls._ids(opt, 'banned_ids', V1), cls._ids(opt, 'bad_endings', V1)
-        if 0 in banned:
-            raise ValueError('token 0 (END) cannot be banned')
-        if not (n or banned or bad):
-            return None
-        if S > 64:
-            raise N.RfnError('decoding constraints support seq_length <= 64')
-        c = cls()
-        c.n, c.banned, c.bad, c.V1, c.S = n, banned, bad, V1, S
-        return c
-
-    def bind(self, rows, dev):
-        self.rows = rows
-        self.banned_d = torch.tensor(self.banned or [0], dtype=torch.int32, device=dev)
-        self.bad_d = torch.tensor(self.bad or [0], dtype=torch.int32, device=dev)
-        self.blk = torch.empty(rows, N.DECODE_MAX_IDS + self.S, dtype=torch.int32, device=dev)
-        self.blk_n = torch.empty(rows, dtype=torch.int32, device=dev)
-        self.struct = N.DecodeConstraints(self.n, len(self.banned), len(self.bad), 0, self.banned_d.data_ptr(),
-                                          self.bad_d.data_ptr(), self.blk.data_ptr(), self.blk_n.data_ptr())
-        return self
-
-    def blocklist(self, hist, s_row, s_tok, t):
-        """The rows' blocked ids at step t (which picks the t-th token) from their histories (rfn_decode_blocklist)."""
-        N.check(N.lib.rfn_decode_blocklist(hist.data_ptr(), s_row, s_tok, None, self.rows, self.S, t, self.n,
-                                           self.banned_d.data_ptr(), len(self.banned), self.bad_d.data_ptr(), len(self.bad),
-                                           self.V1, self.blk.data_ptr(), self.blk_n.data_ptr(), N.stream_ptr()),
-                'rfn_decode_blocklist')
-
-    def mask(self, logp):
-        N.check(N.lib.rfn_logp_mask_rows(logp.data_ptr(), logp.stride(0), self.rows, self.V1, self.blk.data_ptr(),
-                                         self.blk.stride(0), self.blk_n.data_ptr(), N.stream_ptr()), 'rfn_logp_mask_rows')
-
-    def topk(self, logits, W, topv, topi):
-        N.check(N.lib.rfn_log_softmax_topk_masked(logits.data_ptr(), logits.stride(0), self.rows, self.V1, W, self.blk.data_ptr(),
-                                                  self.blk.stride(0), self.blk_n.data_ptr(), topv.data_ptr(), topi.data_ptr(),
-                                                  N.stream_ptr()), 'rfn_log_softmax_topk_masked')
-
-
-def _length_penalty(opt):
-    alpha = float(opt.get('length_penalty', 0.0) or 0.0)
-    if alpha < 0.0 or alpha != alpha:
-        raise ValueError('length_penalty must be >= 0, got %r' % alpha)
-    return alpha
-
-
-def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0):
-    """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
-    once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
-    GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
-    per-image Python structures top_seq / top_prob / done_beams: thousands of small objects that need the done counts on
-    the host, so they are lists that fill themselves on first access -- a loop that only consumes the returned captions
-    never waits for them).
-
-    length_penalty = alpha > 0 ranks by p / len^alpha instead (len: the tokens up to and including the first 0, S without one);
-    ties keep construction order, and `p` / top_prob stay the raw sums.  len^alpha comes from a host table of S + 1 doubles
-    and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly."""
-    dev, B = done_p.device, done_p.size(0)
-    score = done_p
-    if length_penalty:
-        ended = done_seq == 0
-        first0 = ended.to(torch.int8).argmax(2) + 1                                  # first maximum = first 0
-        length = torch.where(ended.any(2), first0, torch.full_like(first0, S))
-        table = torch.tensor([1.0] + [float(n) ** float(length_penalty) for n in range(1, S + 1)], dtype=torch.float64)
-        score = done_p.double() / table.to(dev)[length]
-    key = torch.where(torch.arange(max_done, device=dev)[None, :] < done_n[:, None], -score,
-                      torch.full_like(score, float('inf')))
-    rank = torch.sort(key, dim=1, stable=True).indices
-    pick = rank[:, :, None].expand(-1, -1, S)
-    s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
-    src = _BeamResults(s_all, l_all, p_all, done_n)
-    return (s_all[:, 0].contiguous(), l_all[:, 0].contiguous(), _LazyList(B, lambda: src.top_seq()),
-            _LazyList(B, lambda: src.top_prob()), _LazyList(B, lambda: src.done_beams()))
-
-
-class _BeamResults:
-    """Host copies of the sorted done beams, fetched once, on demand."""
-
-    def __init__(self, s_all, l_all, p_all, done_n):
-        self._dev = (s_all, l_all, p_all, done_n)
-        self._host = None
-
-    def host(self):
-        if self._host is None:
-            s_all, l_all, p_all, done_n = self._dev
-            self._host = (s_all.cpu(), l_all.cpu(), p_all.cpu().tolist(), done_n.cpu().tolist())
-        return self._host
-
-    def top_seq(self):
-        s_all, _, _, counts = self.host()
-        return [s_all[k, :n] for k, n in enumerate(counts)]
-
-    def top_prob(self):
-        _, _, probs, counts = self.host()
-        return [probs[k][:n] for k, n in enumerate(counts)]
-
-    def done_beams(self):
-        """misc/RecurrentFusionModel.py:529-531: per image the list of {'seq', 'logps', 'p'} dicts, best first."""
-        s_all, l_all, probs, counts = self.host()
-        return [[{'seq': a, 'logps': b_, 'p': c_} for a, b_, c_ in zip(s_all[k, :n].unbind(0), l_all[k, :n].unbind(0), probs[k][:n])]
-                for k, n in enumerate(counts)]
-
-
-class _LazyList(collections.abc.MutableSequence):
-    """A sequence of known length whose entries are produced (all at once) by `fill()` the first time anything but its
-    length is asked for.  Deliberately NOT a subclass of `list`: C fast paths that take a list subclass (`PySequence_Fast`,
-    `PyList_GET_ITEM`: json's C encoder, `str.join`, some torch / numpy converters) read the list's item array directly and
-    would see unfilled placeholders without any Python-level hook running.  As a plain `MutableSequence` every consumer goes
-    through `__getitem__` / `__iter__` / `__len__` (which fill first), and a consumer that insists on a real list fails
-    loudly (`json.dumps(x)` raises TypeError; `json.dumps(list(x))` / `x.materialize()` is the spelling).  Indexing,
-    slicing, iteration, comparison with lists, `+`, `in`, `reversed`, `sorted`, printing, copying, pickling (as a plain
-    list) and in-place edits behave like the list the reference returns (misc/RecurrentFusionModel.py:529-543)."""
-
-    __slots__ = ('_n', '_fill', '_items')
-    __hash__ = None
-
-    def __init__(self, n, fill):
-        self._n, self._fill, self._items = int(n), fill, None
-
-    def materialize(self):
-        """The plain `list` behind this object (filled now if it was not)."""
-        if self._items is None:
-            fill, self._fill = self._fill, None
-            items = list(fill())
-            if len(items) != self._n:
-                raise N.RfnError('lazy list promised %d entries, its producer made %d' % (self._n, len(items)))
-            self._items = items
-        return self._items
-
-    def __len__(self):
-        return self._n if self._items is None else len(self._items)
-
-    def __getitem__(self, i):
-        return self.materialize()[i]
-
-    def __setitem__(self, i, v):
-        self.materialize()[i] = v
-
-    def __delitem__(self, i):
-        del self.materialize()[i]
-
-    def insert(self, i, v):
-        self.materialize().insert(i, v)
-
-    def __iter__(self):
-        return iter(self.materialize())
-
-    def __repr__(self):
-        return repr(self.materialize())
-
-    def _other(self, other):
-        return other.materialize() if isinstance(other, _LazyList) else other
-
-    def __eq__(self, other):
-        return self.materialize() == self._other(other)
-
-    def __ne__(self, other):
-        return self.materialize() != self._other(other)
-
-    def __lt__(self, other):
-        return self.materialize() < self._other(other)
-
-    def __le__(self, other):
-        return self.materialize() <= self._other(other)
-
-    def __gt__(self, other):
-        return self.materialize() > self._other(other)
-
-    def __ge__(self, other):
-        return self.materialize() >= self._other(other)
-
-    def __add__(self, other):
-        return self.materialize() + list(self._other(other))
-
-    def __radd__(self, other):
-        return list(other) + self.materialize()
-
-    def __mul__(self, k):
-        return self.materialize() * k
-
-    __rmul__ = __mul__
-
-    def copy(self):
-        return list(self.materialize())
-
-    def sort(self, **kw):
-        self.materialize().sort(**kw)
-
-    def __reduce_ex__(self, protocol):
-        return (list, (list(self.materialize()),))
-
-
 def _join_before_state_dict(module, prefix, keep_vars):
     hook = getattr(module, 'param_wait_hook', None)
     if hook is not None:
         hook(None)
-
-
-class _Stepper:
-    """Free-running decoder state for sample / beam / one_time_step: rfn_decoder_prepare + rfn_decoder_step."""
-
-    def __init__(self, model, comb, h, c, drop=False, seed=0):
-        """drop / seed: apply the decoder dropout masks of (seed, step index) -- the ones rfn_decoder_fwd applies at
-        the same steps -- so a free-running pass in training mode reproduces the teacher-forced pass bit for bit."""
-        self.model = model
-        self.d = model._dims_for(bool(drop))
-        self.seed, self.t = int(seed), 0
-        self.comb = comb.contiguous()
-        self.h, self.c = h.contiguous(), c.contiguous()
-        self.B = self.h.size(0)
-        dev = self.h.device
-        self.table = model._param_table(model._params_of(model._decoder_slots), model._decoder_slots)
-        # the loop-invariant products of the thought vectors: att_2_att_h(comb) and U = comb . z2h.weight^T (rfn.h)
-        self.Bc = self.comb.size(1)          # rows per thought vector: B, or the images of a beam search (B = Bc * beam)
-        self.cproj = torch.empty(N.lib.rfn_decoder_cproj_floats(C.byref(self.d), self.Bc), device=dev)
-        N.check(N.lib.rfn_decoder_prepare(C.byref(self.d), self.Bc, self.table, self.comb.data_ptr(),
-                                          self.cproj.data_ptr(), N.stream_ptr()), 'rfn_decoder_prepare')
-        self.ws_bytes = N.lib.rfn_decoder_step_ws_bytes(C.byref(self.d), self.B)
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-
-    def step(self, ids, out=None, want='logp'):
-        """ids: int64 token ids (B,) -- or an already embedded float input (B, E), as the reference's one_time_step."""
-        V1 = self.d.V1
-        if self.Bc != self.B:
-            raise N.RfnError('a stepper whose rows share thought vectors (beam search) is driven by rfn_beam_loop only')
-        if out is None:
-            out = torch.empty(self.B, V1, device=self.h.device)
-        logits_ptr = out.data_ptr() if want == 'logits' else None
-        logp_ptr = out.data_ptr() if want == 'logp' else None
-        if ids.is_floating_point():
-            xt = N.require_cuda_f32(ids, 'xt')
-            if tuple(xt.shape) != (self.B, self.d.E):
-                raise N.RfnError('embedded xt must be (%d, %d), got %s' % (self.B, self.d.E, tuple(xt.shape)))
-            N.check(N.lib.rfn_decoder_step_embedded(C.byref(self.d), self.B, self.table, self.comb.data_ptr(),
-                                                    self.cproj.data_ptr(), xt.data_ptr(), xt.stride(0),
-                                                    self.h.data_ptr(), self.c.data_ptr(), logits_ptr, logp_ptr,
-                                                    out.stride(0), self.ws.data_ptr(), self.ws_bytes, self.seed,
-                                                    self.t, N.stream_ptr()),
-                    'rfn_decoder_step_embedded')
-            self.t += 1
-            return out
-        if ids.dtype != torch.long or not ids.is_contiguous():
-            ids = ids.long().contiguous()
-        N.check(N.lib.rfn_decoder_step(C.byref(self.d), self.B, self.table, self.comb.data_ptr(),
-                                       self.cproj.data_ptr(), ids.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
-                                       logits_ptr, logp_ptr, out.stride(0), self.ws.data_ptr(), self.ws_bytes,
-                                       self.seed, self.t, N.stream_ptr()), 'rfn_decoder_step')
-        self.t += 1
-        return out
-
-    def reorder(self, order):
-        """Row r continues from row order[r] (int32, device): rfn_gather_rows on h and c."""
-        if order.dtype != torch.int32 or not order.is_contiguous():
-            order = order.to(torch.int32).contiguous()
-        h2, c2 = torch.empty_like(self.h), torch.empty_like(self.c)
-        st = N.stream_ptr()
-        N.check(N.lib.rfn_gather_rows(self.h.data_ptr(), h2.data_ptr(), order.data_ptr(), self.B, self.d.R, st), 'rfn_gather_rows')
-        N.check(N.lib.rfn_gather_rows(self.c.data_ptr(), c2.data_ptr(), order.data_ptr(), self.B, self.d.R, st), 'rfn_gather_rows')
-        self.h, self.c = h2, c2

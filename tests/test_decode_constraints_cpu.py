@@ -80,7 +80,7 @@ def test_length_penalty_order_against_a_hand_sorted_list():
 
 
 def test_option_parsing_refuses_what_the_kernels_cannot_take():
-    from recurrent_fusion_network_amd.fusion_model import _Constraints, _length_penalty
+    from recurrent_fusion_network_amd.decode import _Constraints, _length_penalty
     V1, S = 51, 5
     assert _Constraints.parse({}, V1, S) is None
     assert _Constraints.parse({'block_ngram': 0, 'banned_ids': [], 'bad_endings': None}, V1, S) is None

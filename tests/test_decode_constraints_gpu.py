@@ -224,7 +224,7 @@ def beams_of(done_beams):
 
 
 def _members(models, fc, att, repeat=1):
-    from recurrent_fusion_network_amd.fusion_model import _Stepper
+    from recurrent_fusion_network_amd.decode import _Stepper
     out = []
     for m in models:
         comb, h, c, _ = m._prefix(fc, att, False, 0)
@@ -285,7 +285,7 @@ def host_sample(models, fc, att, cons, u=None, inv_temp=1.0):
 @torch.no_grad()
 def host_beam(models, fc, att, W, cons, alpha=0.0):
     """sample_beam stepped from the host with rfn_beam_step in its full-row form on the masked log-prob rows."""
-    from recurrent_fusion_network_amd.fusion_model import _sorted_done_beams
+    from recurrent_fusion_network_amd.decode import _sorted_done_beams
     N = nat()
     m0 = models[0]
     B, S, V1 = fc[0].size(0), m0.seq_length, m0.vocab_size + 1

@@ -1,7 +1,7 @@
 """Host-side pieces that need no GPU."""
 import pickle
 
-from recurrent_fusion_network_amd.fusion_model import _LazyList
+from recurrent_fusion_network_amd.decode import _LazyList, early_exit
 
 
 def test_lazy_list_never_shows_a_placeholder():
@@ -46,3 +46,13 @@ def test_lazy_list_has_no_c_level_back_door():
     assert np.asarray(_LazyList(2, lambda: [1.0, 2.0])).tolist() == [1.0, 2.0]
     with pytest.raises(Exception):
         _LazyList(3, lambda: [1]).materialize()               # a producer that breaks its promise is an error, not a short list
+
+
+def test_early_exit_is_the_first_step_with_no_unfinished_row():
+    """alive[t - 1] = rows still unfinished after the t-th token; the loop stops at the first t >= 1 where it is 0."""
+    assert early_exit([3, 1, 0, 0], 4) == 3                 # the first zero in the middle; later zeros do not matter
+    assert early_exit([0, 0, 0, 0], 4) == 1                 # every row ended with its first token
+    assert early_exit([3, 0, 2, 0], 4) == 2                 # the FIRST zero, whatever follows
+    assert early_exit([4, 4, 2, 1], 4) == 5                 # no zero: S + 1, all S tokens are kept
+    assert early_exit([2, 1, 1, 0], 4) == 4                 # a zero only at the last step
+    assert early_exit([0], 1) == 1 and early_exit([7], 1) == 2      # S = 1
