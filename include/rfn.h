@@ -701,6 +701,33 @@ typedef struct rfn_decode_constraints {
     int32_t* blk;
     int32_t* blk_n;
 } rfn_decode_constraints;
+/* ---- truncated sampling: top-k and nucleus (top-p) (off by default; the reference has neither) -----------------------------
+ * Another edit of a row's log-probs after the log-softmax (and after the constraints' masking), again without renormalising.
+ * x[0 .. V1): log-probs, possibly holding -inf already; inv_temperature > 0, top_k, top_p.
+ *   - weight w_v = exp(x_v * inv_temperature); a -inf entry has weight 0 and is never kept;
+ *   - the order is x descending, then token id ascending (the order rfn_log_softmax_topk lists);
+ *   - top_k = k > 0: the first min(k, number of finite entries) in that order are kept -- ties at the cut go to the lower ids,
+ *     so exactly that many; top_k <= 0 or >= V1: off;
+ *   - top_p = p, 0 < p < 1, over the survivors of top-k: with c_j the sum of the first j weights and c_n the sum of all, the
+ *     first J = min{ j : c_j >= p * c_n } are kept (J >= 1); p >= 1: off;
+ *   - every entry not kept becomes -inf, kept entries keep their bits: the log-prob recorded for a drawn token stays the model's
+ *     own, and rfn_multinomial_pick normalises by the sum of what is left;
+ *   - a row with no finite entry, or one holding a NaN, is left untouched (the pick's own rules then apply).
+ * rfn_logp_truncate_rows does this in place for `rows` rows of stride ldl >= V1, one launch, one block per row, without sorting
+ * (a radix select on the integer image of the floats; masses are exact 64-bit integer sums of fp64 weights rounded down to 2^-47
+ * of the row's largest, so the kept set is a function of the row alone: the same in any launch, at any row position, rows and
+ * ldl).  kept_n (rows, or NULL): the number of kept entries (0 for a row without finite entry, -1 for one holding a NaN).
+ * RFN_ERR_SHAPE: rows <= 0, V1 <= 0, ldl < V1, !(inv_temperature > 0), top_p not in (0, +inf); RFN_ERR_ARG: logp NULL; both
+ * knobs off: RFN_OK, nothing launched; V1 > 65536: RFN_ERR_UNSUPPORTED. */
+int rfn_logp_truncate_rows(float* logp, int64_t ldl, int rows, int V1, int top_k, float top_p, float inv_temperature,
+                           int32_t* kept_n, void* stream);
+/* What rfn_decoder_loop_ex2 takes besides the constraints. */
+typedef struct rfn_decode_sampling {
+    int32_t top_k;            /* <= 0: off */
+    float top_p;              /* >= 1: off */
+    int32_t rows_per_image;   /* n >= 1 draws per image (0 reads as 1) */
+    int32_t pad_;
+} rfn_decode_sampling;
 /* dst[r,:] = src[order[r],:]  (src != dst) */
 int rfn_gather_rows(const float* src, float* dst, const int32_t* order, int rows, int R, void* stream);
 
@@ -853,6 +880,18 @@ int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const float* const*
                         float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
                         int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
                         const rfn_decode_constraints* cons, void* stream);
+/* rfn_decoder_loop_ex with truncated sampling and n draws per image.  Per step t >= 1: rfn_decode_blocklist and
+ * rfn_logp_mask_rows (cons), rfn_logp_truncate_rows (mode 1 only: the argmax is always kept), rfn_multinomial_pick,
+ * rfn_pick_record; the cut entries of logp_all read -inf afterwards.  rows_per_image = n > 1: B counts ROWS, B % n == 0, row
+ * k * n + j is draw j of image k and reads image k's thought vectors: comb is (T2, B / n, R) and cproj comes from
+ * rfn_decoder_prepare(d, B / n, ...), as for the beam rows of rfn_beam_loop; h / c are (B, R), u and the workspace as for B
+ * rows.  n > 1 needs the hoisted decoder cell (RFN_ERR_UNSUPPORTED with RFN_PATH_OPT_DEC_UNHOISTED or the persistent decoder
+ * chains).  samp == NULL: rfn_decoder_loop_ex, which forwards here. */
+int rfn_decoder_loop_ex2(const rfn_dims* d, int B, int steps, const float* const* params, const float* comb,
+                         const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                         float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                         int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                         const rfn_decode_constraints* cons, const rfn_decode_sampling* samp, void* stream);
 int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const* params, const float* comb,
                      const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp, int64_t* beam_seq,
                      float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,

@@ -86,6 +86,11 @@ class DecodeConstraints(C.Structure):
                 ('banned', C.c_void_p), ('bad_endings', C.c_void_p), ('blk', C.c_void_p), ('blk_n', C.c_void_p)]
 
 
+class DecodeSampling(C.Structure):
+    """rfn_decode_sampling (rfn.h)."""
+    _fields_ = [('top_k', C.c_int32), ('top_p', C.c_float), ('rows_per_image', C.c_int32), ('pad_', C.c_int32)]
+
+
 DECODE_MAX_IDS = 64
 
 
@@ -99,7 +104,7 @@ def _load():
         raise RfnError('librfn_hip.so ABI %d != binding ABI %d: rebuild' % (lib.rfn_abi_version(), ABI_VERSION))
     lib.rfn_error_string.restype = C.c_char_p
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
-    DP, CP = C.POINTER(Dims), C.POINTER(DecodeConstraints)
+    DP, CP, SP = C.POINTER(Dims), C.POINTER(DecodeConstraints), C.POINTER(DecodeSampling)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -176,6 +181,7 @@ def _load():
         'rfn_log_softmax_topk_masked': (C.c_int, [P, L, I, I, I, P, L, P, P, P, P]),
         'rfn_decode_blocklist': (C.c_int, [P, L, L, P, I, I, I, I, P, I, P, I, I, P, P, P]),
         'rfn_logp_mask_rows': (C.c_int, [P, L, I, I, P, L, P, P]),
+        'rfn_logp_truncate_rows': (C.c_int, [P, L, I, I, I, F, F, P, P]),
         'rfn_prefix_ws_bytes': (SZ, [DP, I, I]),
         'rfn_prefix_fwd': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, SZ, I, U64, P]),
         'rfn_prefix_fwd_from_state': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, P]),
@@ -189,6 +195,7 @@ def _load():
         'rfn_pick_record': (C.c_int, [P, L, I, I, I, P, P, P, L, P, L, P, P, P]),
         'rfn_decoder_loop': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, P]),
         'rfn_decoder_loop_ex': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, P]),
+        'rfn_decoder_loop_ex2': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, SP, P]),
         'rfn_beam_loop_ex': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, P]),
         'rfn_decoder_fwd_sampled': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, P]),
         'rfn_beam_loop': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, P]),

@@ -1486,6 +1486,228 @@ extern "C" int rfn_multinomial_pick(const float* logp, int64_t ldl, int B, int V
     return RFN_OK;
 }
 
+// ---- truncated sampling: top-k, then nucleus (top-p), of every row, in place (rfn.h "truncated sampling") -----------------
+// One block per row, no sort: the kept set is {key > K} plus the m lowest ids with key == K, where key is the order-preserving
+// integer image of the float (-0 counted as +0, so the order is lsm_before's).  (K, m) come from a radix select by 8-bit
+// digits, top digit first, one histogram bin per thread:
+//   top-k   bins count entries; target = k;
+//   top-p   bins hold MASS over the survivors of top-k; target = ceil(p * total).
+// Mass is exact integer arithmetic: w = exp((x - max) * inv_temp) in fp64 (the common factor exp(max * inv_temp) cancels in
+// c_j >= p * c_n) is rounded DOWN to a multiple of 2^-47, and every sum is a 64-bit integer sum (V1 <= 65536 keeps the total
+// at or below 2^63).  Integer adds commute, so LDS atomics and any thread count give the same bins: the result is a function of
+// the row alone.  The tie group at K is cut by the same integers: m = ceil((target - mass above K) / w(K)).
+// Against exact arithmetic a mass is off by less than V1 * 2^-47 of the total from the rounding down (a weight below 2^-47 of
+// the largest counts as 0) plus fp64 rounding: below 5e-10 of the total.  fp32 weights would be off by about 1e-5 of it, which
+// is the mass of ONE entry near a top_p = 0.9 cut of a 10k-word row: fp64 is what makes the cut the definition's, and at 37
+// entries per thread its cost is small.
+// Rows of up to TRUNC_STAGE_MAX entries keep their keys in LDS between the passes (9488 entries: 38 KB, four blocks per CU);
+// longer rows re-read the log-probs, which the log-softmax before them left in L2.
+#define TRUNC_STAGE_MAX 15360     /* 60 KB of keys + the static arrays below stay inside the 64 KB a block gets by default */
+#define TRUNC_V1_MAX 65536
+#define TRUNC_KEY_NINF 0x007fffffu
+typedef unsigned long long trunc_u64;
+__device__ __forceinline__ unsigned trunc_key(float x) {
+    if (x == 0.f) x = 0.f;   // -0 and +0 are one value in the order
+    const unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float trunc_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+__device__ __forceinline__ trunc_u64 trunc_weight(unsigned key, float mx, float inv_temp) {
+    const double e = exp(((double)trunc_unkey(key) - (double)mx) * (double)inv_temp) * 140737488355328.0;   // * 2^47: exact
+    return e >= 1.0 ? (trunc_u64)e : 0ull;                                            // NaN (a row holding +inf) -> 0
+}
+// exclusive prefix sum over the 256 threads in thread order, and the total; scr: 4 words of LDS
+__device__ __forceinline__ trunc_u64 trunc_scan(trunc_u64 v, trunc_u64* scr, trunc_u64* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    trunc_u64 inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const trunc_u64 y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    __syncthreads();   // scr may still be read from the call before
+    if (lane == 63) scr[wave] = inc;
+    __syncthreads();
+    trunc_u64 before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const trunc_u64 s = scr[w];
+        if (w < wave) before += s;
+        tot += s;
+    }
+    *total = tot;
+    return before + inc - v;
+}
+struct TruncSel {
+    unsigned key;        // K
+    trunc_u64 above;     // count / mass of the participants with key > K
+    trunc_u64 target;
+};
+template <bool STAGE>
+__device__ __forceinline__ unsigned trunc_load(const unsigned* keys, const float* x, int v) {
+    if constexpr (STAGE) return keys[v];
+    else return trunc_key(x[v]);
+}
+// Participants: entries with key > lo, each worth 1 (MASS = false) or its weight, plus `tie_val` more at key == lo (top-k's
+// admitted part of its tie group; 0: none).  target: k, or top_p (then ceil(top_p * total) is taken).  A total of 0 returns
+// target 0: nothing to select.
+template <bool STAGE, bool MASS>
+__device__ TruncSel trunc_select(const unsigned* keys, const float* x, int V1, unsigned lo, trunc_u64 tie_val, float mx,
+                                 float inv_temp, trunc_u64 k, float top_p, trunc_u64* bins, trunc_u64* scr, unsigned* found) {
+    const int tid = threadIdx.x;
+    unsigned prefix = 0;
+    trunc_u64 above = 0, target = k;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        __syncthreads();     // the pass before has read bins / found
+        bins[tid] = 0;
+        __syncthreads();
+        const unsigned hi_mask = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+        int cur = -1;        // runs of one digit (the top digits of log-probs hardly differ) go to LDS as one add
+        trunc_u64 acc = 0;
+        for (int v = tid; v < V1; v += 256) {
+            const unsigned key = trunc_load<STAGE>(keys, x, v);
+            if (key <= lo || ((key ^ prefix) & hi_mask)) continue;
+            const int bin = (int)((key >> shift) & 255u);
+            const trunc_u64 val = MASS ? trunc_weight(key, mx, inv_temp) : 1ull;
+            if (bin != cur) {
+                if (acc) atomicAdd(&bins[cur], acc);
+                cur = bin;
+                acc = 0;
+            }
+            acc += val;
+        }
+        if (acc) atomicAdd(&bins[cur], acc);
+        if (tid == 0 && tie_val && !((lo ^ prefix) & hi_mask)) atomicAdd(&bins[(lo >> shift) & 255u], tie_val);
+        __syncthreads();
+        // thread t looks at digit 255 - t: the scan in thread order is the sum over the higher digits
+        const int digit = 255 - tid;
+        const trunc_u64 mine = bins[digit];
+        trunc_u64 total;
+        const trunc_u64 higher = trunc_scan(mine, scr, &total);
+        if (shift == 24) {
+            if (total == 0) return TruncSel{lo, 0, 0};
+            if (MASS) {
+                const double want = ceil((double)top_p * (double)total);
+                target = want >= (double)total ? total : (trunc_u64)want;
+                if (target < 1) target = 1;
+            }
+        }
+        if (above + higher < target && above + higher + mine >= target) {   // exactly one thread
+            found[0] = (unsigned)digit;
+            bins[digit] = above + higher;      // its own bin: nobody else reads it any more
+        }
+        __syncthreads();
+        const unsigned dg = found[0] & 255u;
+        above = bins[dg];
+        prefix |= dg << shift;
+    }
+    return TruncSel{prefix, above, target};
+}
+template <bool STAGE>
+__global__ __launch_bounds__(256) void logp_truncate_rows_k(float* __restrict__ logp, long ldl, int V1, int top_k, float top_p,
+                                                            float inv_temp, int* __restrict__ kept_n) {
+    extern __shared__ unsigned trunc_keys[];     // STAGE: V1 keys
+    __shared__ trunc_u64 bins[256];
+    __shared__ trunc_u64 scr[4];
+    __shared__ float wmax[4];
+    __shared__ unsigned found[2];
+    __shared__ int flags[2];                     // a NaN seen; kept entries
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* x = logp + r * ldl;
+    if (tid == 0) flags[0] = flags[1] = 0, found[0] = found[1] = 0;
+    __syncthreads();
+    // pass 0: keys to LDS, the maximum, the finite count, NaN
+    float mx = -INFINITY;
+    int nfin = 0;
+    bool nan = false;
+    for (int v = tid; v < V1; v += 256) {
+        const float xv = x[v];
+        if constexpr (STAGE) trunc_keys[v] = trunc_key(xv);
+        nan = nan || xv != xv;
+        nfin += xv > -INFINITY;
+        mx = fmaxf(mx, xv);
+    }
+    if (nan) flags[0] = 1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) wmax[wave] = mx;
+    trunc_u64 nfinite;
+    trunc_scan((trunc_u64)nfin, scr, &nfinite);   // its barriers also publish the keys, wmax and flags
+    mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (flags[0] || nfinite == 0) {               // left untouched: the pick's own rules apply
+        if (tid == 0 && kept_n) kept_n[r] = flags[0] ? -1 : 0;
+        return;
+    }
+    unsigned K = TRUNC_KEY_NINF;     // kept: key > K, and the m lowest ids with key == K
+    trunc_u64 m = 0;
+    if (top_k > 0 && (trunc_u64)top_k < nfinite) {
+        const TruncSel s = trunc_select<STAGE, false>(trunc_keys, x, V1, TRUNC_KEY_NINF, 0, mx, inv_temp, (trunc_u64)top_k, 1.f,
+                                                      bins, scr, found);
+        K = s.key;
+        m = s.target - s.above;
+    }
+    if (top_p < 1.f) {
+        const trunc_u64 wK = m ? trunc_weight(K, mx, inv_temp) : 0ull;
+        const TruncSel s = trunc_select<STAGE, true>(trunc_keys, x, V1, K, m * wK, mx, inv_temp, 0, top_p, bins, scr, found);
+        if (s.target) {
+            const trunc_u64 w = trunc_weight(s.key, mx, inv_temp), need = s.target - s.above;
+            trunc_u64 mp = w ? (need + w - 1) / w : 1;
+            if (s.key == K && mp > m) mp = m;     // cannot happen: the admitted part of top-k's tie group reaches the target
+            K = s.key;
+            m = mp;
+        }
+    }
+    // the id of the m-th entry with key == K: thread t owns the contiguous ids [t * C, (t + 1) * C), as the multinomial pick
+    int cut = -1;
+    if (m) {
+        const int C = (V1 + 255) / 256, v0 = min(V1, tid * C), v1 = min(V1, v0 + C);
+        int ties = 0;
+        for (int v = v0; v < v1; ++v) ties += trunc_load<STAGE>(trunc_keys, x, v) == K;
+        trunc_u64 total;
+        const trunc_u64 before = trunc_scan((trunc_u64)ties, scr, &total);
+        if (tid == 0) found[1] = (unsigned)(V1 - 1);     // m >= the group's size (cannot happen): all of it
+        __syncthreads();
+        if (before < m && m <= before + (trunc_u64)ties) {
+            int left = (int)(m - before);
+            for (int v = v0; v < v1; ++v)
+                if (trunc_load<STAGE>(trunc_keys, x, v) == K && --left == 0) {
+                    found[1] = (unsigned)v;
+                    break;
+                }
+        }
+        __syncthreads();
+        cut = (int)found[1];
+    }
+    int kept = 0;
+    for (int v = tid; v < V1; v += 256) {
+        const unsigned key = trunc_load<STAGE>(trunc_keys, x, v);
+        const bool keep = key > K || (key == K && v <= cut);
+        kept += keep;
+        if (!keep && key != TRUNC_KEY_NINF) x[v] = -INFINITY;
+    }
+    if (kept_n) {
+        if (kept) atomicAdd(&flags[1], kept);
+        __syncthreads();
+        if (tid == 0) kept_n[r] = flags[1];
+    }
+}
+extern "C" int rfn_logp_truncate_rows(float* logp, int64_t ldl, int rows, int V1, int top_k, float top_p, float inv_temperature,
+                                      int32_t* kept_n, void* stream) {
+    if (rows <= 0 || V1 <= 0 || ldl < V1 || !(inv_temperature > 0.f) || !(top_p > 0.f && top_p < INFINITY))
+        return RFN_ERR_SHAPE;
+    if (!logp) return RFN_ERR_ARG;
+    if ((top_k <= 0 || top_k >= V1) && top_p >= 1.f) return RFN_OK;     // both off: nothing is launched
+    if (V1 > TRUNC_V1_MAX) return RFN_ERR_UNSUPPORTED;
+    if (V1 <= TRUNC_STAGE_MAX)
+        hipLaunchKernelGGL(logp_truncate_rows_k<true>, dim3(rows), dim3(256), (size_t)V1 * sizeof(unsigned), (hipStream_t)stream,
+                           logp, (long)ldl, V1, top_k, top_p, inv_temperature, kept_n);
+    else
+        hipLaunchKernelGGL(logp_truncate_rows_k<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logp, (long)ldl, V1, top_k,
+                           top_p, inv_temperature, kept_n);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
 // ---- greedy pick of sample() (misc/RecurrentFusionModel.py:619-649) -----------------------------------
 // Order of the arg-max, as torch.max has it: NaN ranks above every number, equals (two NaNs included) go to the lower index.
 // Every thread that owns an element starts from it, so a row of all -inf yields token 0 and a row with NaN its first NaN:

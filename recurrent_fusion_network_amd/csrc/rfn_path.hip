@@ -2098,11 +2098,11 @@ static int check_constraints(const rfn_decode_constraints* cons, int S) {
     if (!cons->blk || !cons->blk_n || (cons->n_banned && !cons->banned) || (cons->n_bad && !cons->bad_endings)) return RFN_ERR_ARG;
     return RFN_OK;
 }
-extern "C" int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
-                                   const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
-                                   float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
-                                   int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
-                                   const rfn_decode_constraints* cons, void* st) {
+extern "C" int rfn_decoder_loop_ex2(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
+                                    const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                                    float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                                    int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                                    const rfn_decode_constraints* cons, const rfn_decode_sampling* samp, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed_checked;
     RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
@@ -2111,6 +2111,12 @@ extern "C" int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const fl
     if (mode == 1 && !u) return RFN_ERR_ARG;
     const int V1 = d->V1, S = steps - 1;
     if (cons && S >= 1) RFN_TRY(check_constraints(cons, S));
+    // samp: truncate the rows before a draw (mode 1; the argmax survives any truncation), n rows per image
+    const int n_img = samp && samp->rows_per_image ? samp->rows_per_image : 1;
+    const bool trunc = samp && mode == 1 && ((samp->top_k > 0 && samp->top_k < V1) || samp->top_p < 1.f);
+    if (n_img < 1 || B % n_img) return RFN_ERR_SHAPE;
+    if (n_img > 1 && !dec_hoisted(d)) return RFN_ERR_UNSUPPORTED;   // the three-launch cell reads comb per row
+    if (trunc && (!(samp->top_p > 0.f) || !(inv_temperature > 0.f))) return RFN_ERR_SHAPE;
     if (hipMemsetAsync(ids, 0, (size_t)B * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;   // BOS
     for (int t = 0; t < steps; ++t) {
         if (t >= 1) {
@@ -2120,15 +2126,24 @@ extern "C" int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const fl
                                              cons->bad_endings, cons->n_bad, V1, cons->blk, cons->blk_n, st));
                 RFN_TRY(rfn_logp_mask_rows(prev, ld_b, B, V1, cons->blk, RFN_DECODE_MAX_IDS + S, cons->blk_n, st));
             }
+            if (trunc) RFN_TRY(rfn_logp_truncate_rows(prev, ld_b, B, V1, samp->top_k, samp->top_p, inv_temperature, nullptr, st));
             if (mode == 1)   // the draw first: the greedy-pick kernel below then records ITS log-prob and finished flags
                 RFN_TRY(rfn_multinomial_pick(prev, ld_b, B, V1, inv_temperature, u + (long)(t - 1) * B, nullptr, 1.f, ids, 1, st));
             RFN_TRY(rfn_pick_record(prev, ld_b, B, V1, t, mode == 1 ? ids : nullptr, ids, seq + (t - 1), ld_seq, seq_lp + (t - 1),
                                     ld_lp, t > 1 ? unf + (long)(t - 1) * B : nullptr, unf + (long)t * B, st));
         }
-        RFN_TRY(rfn_decoder_step(d, B, prm, comb, cproj, ids, h, c, nullptr, logp_all + (long)t * ld_t, ld_b, ws, ws_bytes, seed, t,
-                                 st));
+        RFN_TRY(decoder_step_impl(d, B, prm, comb, cproj, ids, nullptr, 0, h, c, nullptr, logp_all + (long)t * ld_t, ld_b, ws,
+                                  ws_bytes, seed, t, st, nullptr, nullptr, 0, n_img));   // n_img = 1: rfn_decoder_step
     }
     return RFN_OK;
+}
+extern "C" int rfn_decoder_loop_ex(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
+                                   const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,
+                                   float* logp_all, int64_t ld_b, int64_t ld_t, int64_t* seq, int64_t ld_seq, float* seq_lp,
+                                   int64_t ld_lp, int32_t* unf, int64_t* ids, void* ws, size_t ws_bytes, uint64_t seed,
+                                   const rfn_decode_constraints* cons, void* st) {
+    return rfn_decoder_loop_ex2(d, B, steps, prm, comb, cproj, h, c, mode, inv_temperature, u, logp_all, ld_b, ld_t, seq, ld_seq,
+                                seq_lp, ld_lp, unf, ids, ws, ws_bytes, seed, cons, nullptr, st);
 }
 extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float* const* prm, const float* comb,
                                 const float* cproj, float* h, float* c, int mode, float inv_temperature, const float* u,

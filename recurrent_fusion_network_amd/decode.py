@@ -98,17 +98,19 @@ class GreedyBuffers:
         return self.seq[:, :t_stop - 1], self.seq_lp[:, :t_stop - 1], self.logp_all[:, :t_stop].contiguous()
 
 
-def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons):
+def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
     """The whole free-running loop (pick, embed, cell, logit, log-softmax) in one call.  mode 0: greedy; 1: draw with the
-    uniforms u (S, B) at inverse temperature inv_temp.  cons: a parsed _Constraints or None."""
+    uniforms u (S, B) at inverse temperature inv_temp.  cons: a parsed _Constraints or None; samp: a parsed _Sampling or None
+    (with samp.n > 1 the stepper's B rows are n per thought vector, image-major)."""
     b, B = bufs, stepper.B
-    N.check(N.lib.rfn_decoder_loop_ex(C.byref(stepper.d), B, b.S + 1, stepper.table, stepper.comb.data_ptr(),
-                                      stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
-                                      N.ptr(u), b.logp_all.data_ptr(), b.logp_all.stride(0), b.logp_all.stride(1),
-                                      b.seq.data_ptr(), b.seq.stride(0), b.seq_lp.data_ptr(), b.seq_lp.stride(0), b.unf.data_ptr(),
-                                      b.it.data_ptr(), stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
-                                      C.byref(cons.bind(B, stepper.h.device).struct) if cons is not None else None,
-                                      N.stream_ptr()), 'rfn_decoder_loop_ex')
+    N.check(N.lib.rfn_decoder_loop_ex2(C.byref(stepper.d), B, b.S + 1, stepper.table, stepper.comb.data_ptr(),
+                                       stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
+                                       N.ptr(u), b.logp_all.data_ptr(), b.logp_all.stride(0), b.logp_all.stride(1),
+                                       b.seq.data_ptr(), b.seq.stride(0), b.seq_lp.data_ptr(), b.seq_lp.stride(0), b.unf.data_ptr(),
+                                       b.it.data_ptr(), stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                       C.byref(cons.bind(B, stepper.h.device).struct) if cons is not None else None,
+                                       C.byref(samp.struct()) if samp is not None else None,
+                                       N.stream_ptr()), 'rfn_decoder_loop_ex2')
 
 
 class BeamBuffers:
@@ -212,6 +214,34 @@ class _Constraints:
         N.check(N.lib.rfn_log_softmax_topk_masked(logits.data_ptr(), logits.stride(0), self.rows, self.V1, W, self.blk.data_ptr(),
                                                   self.blk.stride(0), self.blk_n.data_ptr(), topv.data_ptr(), topi.data_ptr(),
                                                   N.stream_ptr()), 'rfn_log_softmax_topk_masked')
+
+
+class _Sampling:
+    """Truncated sampling of one call (rfn.h "truncated sampling"): opt['top_k'] (int, 0 = off), opt['top_p'] (float in (0, 1],
+    1.0 = off) and opt['sample_n'] (int >= 1 draws per image).  `parse` returns None when all three are off, so such a call
+    issues exactly the launches it always did."""
+
+    KEYS = ('top_k', 'top_p', 'sample_n')
+
+    @classmethod
+    def parse(cls, opt):
+        k, p, n = opt.get('top_k', 0), opt.get('top_p', 1.0), opt.get('sample_n', 1)
+        k, p, n = int(0 if k is None else k), float(1.0 if p is None else p), int(1 if n is None else n)
+        if k < 0:
+            raise ValueError('top_k must be >= 0 (0 = off), got %d' % k)
+        if not 0.0 < p <= 1.0:
+            raise ValueError('top_p must be in (0, 1] (1 = off), got %r' % p)
+        if n < 1:
+            raise ValueError('sample_n must be >= 1, got %d' % n)
+        if k == 0 and p == 1.0 and n == 1:
+            return None
+        s = cls()
+        s.k, s.p, s.n = k, p, n
+        return s
+
+    def struct(self):
+        self._struct = N.DecodeSampling(self.k, self.p, self.n, 0)
+        return self._struct
 
 
 def _length_penalty(opt):

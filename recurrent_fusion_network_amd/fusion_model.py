@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _LazyList, _length_penalty, _sorted_done_beams, _Stepper,
-                     early_exit, run_beam_loop, run_greedy_loop)
+from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _LazyList, _length_penalty, _Sampling, _sorted_done_beams,
+                     _Stepper, early_exit, run_beam_loop, run_greedy_loop)
 
 _INIT = 0.1
 
@@ -771,13 +771,22 @@ class RecurrentFusionModel(nn.Module):
         sample_max = opt.get('sample_max', 1)
         beam_size = opt.get('beam_size', 1)
         temperature = opt.get('temperature', 1.0)
+        samp = _Sampling.parse(opt)
         if beam_size > 1:
+            if samp is not None:
+                raise ValueError('top_k / top_p / sample_n apply to multinomial sampling, not to beam search')
             return self.sample_beam(fc_feats, att_feats, opt)
         cons = _Constraints.parse(opt, self.vocab_size + 1, self.seq_length)
         if cons is not None and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
+        if samp is not None and opt.get('force_ids', None) is not None:
+            raise ValueError('force_ids replays given tokens: top_k / top_p / sample_n cannot be combined with it')
+        if samp is not None and sample_max:
+            if samp.n > 1:
+                raise ValueError('sample_n > 1 with sample_max=1 would return n identical captions: sample with sample_max=0')
+            samp = None           # the argmax survives any truncation
         want_grad = torch.is_grad_enabled() and not sample_max
-        if cons is not None and want_grad:
+        if (cons is not None or samp is not None) and want_grad:
             raise N.RfnError('decoding constraints are not applied to the differentiated sampling pass: sample under no_grad')
         # dropout follows the module's mode, as the reference's nn.Dropout layers do (train_rl.py samples in train()
         # mode)
@@ -787,10 +796,10 @@ class RecurrentFusionModel(nn.Module):
             comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
         reason_pred = list(reason.unbind(0))
         force = opt.get('force_ids', None)
-        if (not sample_max and cons is None) or force is not None:
+        if (not sample_max and cons is None and samp is None) or force is not None:
             out = self._sample_replayed(comb, h, c, train, seed, want_grad, temperature, force)
         else:
-            out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons)
+            out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp)
         return (*out, reason_pred)
 
     def _sample_replayed(self, comb, h, c, train, seed, want_grad, temperature, force):
@@ -819,10 +828,17 @@ class RecurrentFusionModel(nn.Module):
         return seq[:, :n_seq], seq_lp, logp.contiguous()
 
     @torch.no_grad()
-    def _sample_device_loop(self, comb, h, c, train, seed, sample_max, temperature, cons):
-        """Greedy, or constrained multinomial: the whole free-running loop in one call -> (seq, seq_lp, logp)."""
-        B, S, dev = h.size(0), self.seq_length, comb.device
-        stepper = _Stepper(self, comb.detach(), h.detach().clone(), c.detach().clone(), train, seed)
+    def _sample_device_loop(self, comb, h, c, train, seed, sample_max, temperature, cons, samp=None):
+        """Greedy, or constrained / truncated multinomial: the whole free-running loop in one call -> (seq, seq_lp, logp).
+        samp.n > 1: n rows per image, image-major, all reading the image's thought vectors (comb stays per image)."""
+        S, dev = self.seq_length, comb.device
+        n = samp.n if samp is not None else 1
+        if n > 1:
+            h, c = h.detach().repeat_interleave(n, dim=0), c.detach().repeat_interleave(n, dim=0)
+        else:
+            h, c = h.detach().clone(), c.detach().clone()
+        B = h.size(0)
+        stepper = _Stepper(self, comb.detach(), h, c, train, seed)
         bufs = GreedyBuffers(B, S, self.vocab_size + 1, dev)
         mode, inv_temp, u = 0, 1.0, None
         if not sample_max:     # the same loop drawing with the uniforms the sampled pass would use
@@ -832,7 +848,7 @@ class RecurrentFusionModel(nn.Module):
             elif tuple(r.shape) != (2, S + 1, B) or r.device != dev:
                 raise N.RfnError('sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S + 1, B)))
             mode, inv_temp, u = 1, 1.0 / float(temperature), r[0, 1:].contiguous()
-        run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons)
+        run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp)
         return bufs.read_back()        # waits for the loop: the call's one read-back
 
     def sample_beam(self, fc_feats, att_feats, opt={}):

@@ -71,6 +71,79 @@ def constraints_ab(out_path, rounds=5):
         json.dump(res, f, indent=1)
         f.write('\n')
 
+def truncation_ab(out_path, rounds=7):
+    """--truncate: config 5, the mode-1 (multinomial) device loop untruncated, with top_k = 50, top_p = 0.9, both, and with
+    sample_n = 5 against the same call on features repeated five times; calls alternate, medians of `rounds`, kernel launches
+    per call by the profiler.  Every setting runs stages I / II and then the device loop (untruncated plain multinomial is
+    served by the replayed pass in sample(), so the loop is called directly here).  Plus one rfn_logp_truncate_rows launch at
+    (128, 9488) next to one rfn_multinomial_pick launch, by device events around the single launch."""
+    import ctypes as C
+    from recurrent_fusion_network_amd import _native as N
+    from recurrent_fusion_network_amd.decode import _Sampling
+    S, V1 = cfg.seq_length, cfg.vocab_size + 1
+    model.eval()
+    fc5, att5 = [f.repeat_interleave(5, dim=0) for f in fc], [a.repeat_interleave(5, dim=0) for a in att]
+
+    def loop(o, f=fc, a=att):
+        with torch.no_grad():
+            comb, h, c, _ = model._prefix(f, a, False, 0)
+            return model._sample_device_loop(comb, h, c, False, 0, 0, 1.0, None, _Sampling.parse(o))
+
+    settings = [('untruncated', lambda: loop({})), ('top_k_50', lambda: loop({'top_k': 50})), ('top_p_0.9', lambda: loop({'top_p': 0.9})),
+                ('top_k_50_top_p_0.9', lambda: loop({'top_k': 50, 'top_p': 0.9})),
+                ('sample_n_5_on_128_images', lambda: loop({'sample_n': 5})), ('features_repeated_5x_640_rows', lambda: loop({}, fc5, att5))]
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=%d, seq=%d, B=%d' % (V1, S, B), 'rounds': rounds,
+           'what': 'ms per call of stages I / II + the mode-1 device loop (rfn_decoder_loop_ex2), calls alternating'}
+    ms = {k: [] for k, _ in settings}
+    for _ in range(rounds):
+        for k, fn in settings:
+            ms[k].append(timed(fn, 3)[0] * 1e3)
+    with torch.no_grad():
+        greedy_n = HB.count_launches(lambda: model.sample(fc, att, {'sample_max': 1}))
+        never = {'sample_max': 0, 'banned_ids': [cfg.vocab_size]}
+        cons_n = HB.count_launches(lambda: model.sample(fc, att, never))
+    for k, fn in settings:
+        res[k] = {'ms': round(sorted(ms[k])[rounds // 2], 3), 'launches_per_call': HB.count_launches(fn)}
+        print(json.dumps({k: res[k]}), flush=True)
+    res['launch_check'] = {'greedy_sample (the parent\'s path)': greedy_n, 'constrained multinomial sample (the parent\'s mode-1 loop)': cons_n,
+                           'steps': S,
+                           'note': 'the untruncated mode-1 loop must issue the greedy call\'s launches + one multinomial pick per step, '
+                                   'and the parent\'s constrained mode-1 loop\'s minus blocklist and mask per step; a truncated loop one more per step',
+                           'untruncated_is_greedy_plus_S': (res['untruncated']['launches_per_call'] == greedy_n + S) if greedy_n else None,
+                           'untruncated_is_constrained_minus_2S': (res['untruncated']['launches_per_call'] == cons_n - 2 * S) if cons_n else None}
+    # one launch of each kernel on log-probs of randn * 3 logits
+    g = torch.Generator().manual_seed(1)
+    src = torch.log_softmax(torch.randn(B, V1, generator=g) * 3.0, 1).to(dev)
+    u, ids, work = torch.rand(B, generator=g).to(dev), torch.zeros(B, dtype=torch.long, device=dev), src.clone()
+
+    def one(call, reps=50):
+        t = []
+        for _ in range(reps + 5):
+            work.copy_(src)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            N.check(call())
+            e1.record()
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) * 1e3)
+        return round(sorted(t[5:])[reps // 2], 2)
+
+    tr = lambda k, p: one(lambda: N.lib.rfn_logp_truncate_rows(work.data_ptr(), V1, B, V1, k, p, 1.0, None, N.stream_ptr()))  # noqa: E731
+    res['single_launch_us'] = {
+        'shape': [B, V1], 'note': 'median of 50, device events around one launch (they include the launch gap)',
+        'rfn_multinomial_pick': one(lambda: N.lib.rfn_multinomial_pick(work.data_ptr(), V1, B, V1, 1.0, u.data_ptr(), None, 1.0,
+                                                                       ids.data_ptr(), 1, N.stream_ptr())),
+        'rfn_logp_truncate_rows top_k=50': tr(50, 1.0), 'rfn_logp_truncate_rows top_p=0.9': tr(0, 0.9),
+        'rfn_logp_truncate_rows top_k=50 top_p=0.9': tr(50, 0.9)}
+    print(json.dumps(res['single_launch_us']), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
+PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
+if '--truncate' in sys.argv:
+    truncation_ab(os.path.join(PROFILES, 'decode_truncation.json'))
+    sys.exit(0)
 if '--constraints' in sys.argv:
     constraints_ab(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'decode_constraints.json'))
     sys.exit(0)
