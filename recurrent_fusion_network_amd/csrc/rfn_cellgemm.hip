@@ -1,7 +1,7 @@
 // Row-panel GEMM of the recurrences: the per-step products of the three cells (M = batch rows, a few hundred) with their
 // epilogues fused, so that one cell step is three launches instead of six or seven.
 //
-// Replaces, inside the step loops of rfn_path.hip, the sequences
+// Replaces, inside the step loops of rfn_path_*.hip, the sequences
 //     gemm (64x64 tiles, K cut across blocks) -> rfn_gemm_reduce_k -> lstm_fwd_k               (forward)
 //     axpby -> lstm_bwd_k -> gemm -> rfn_gemm_reduce_k -> ... -> gemm -> rfn_gemm_reduce_k      (backward)
 // of misc/RecurrentFusionModel.py:53-73 (stage I gates), misc/LSTMSoftMultiAttentionFeatArrayNoInputCore.py:46-72

@@ -12,7 +12,7 @@
 //     K2  scores, softmax, gates += b_z + sum_l alpha_l U_l, LSTM update          (dec_cell_fwd_k, this file)
 // Backward: with z gone, the attention backward needs only d gates of its own step (d alpha_l = <d gates, U_l>), and
 // d h = d gates . W_hh + d hproj . W_h splits into a long part that does NOT depend on the attention backward and a short one
-// that does.  A step is two launches (rfn_path.hip, rfn_decoder_bwd):
+// that does.  A step is two launches (rfn_path_decoder.hip, rfn_decoder_bwd):
 //     X   the attention-backward rows (dec_attn_bwd_fast_body) BESIDE the tiles of d gates . W_hh cut 4 ways along K into
 //         partial slabs, in one grid (cell_gemm_rows_k, rfn_cellgemm.hip)
 //     Y   d hproj . W_h + the slabs, with the LSTM backward of the step below as epilogue (rfn_cell_gemm, acc_slabs)

@@ -78,7 +78,7 @@ def test_random_configuration_matches_oracle(dev, seed, gemm):
 def test_mid_size_batches_of_uniform_encoders(dev, M, B, gemm):
     """The batch sizes of data-parallel shards: uniform encoders with maps too big for the small-map rule (L * D > 32768),
     M * B on both sides of the threshold at which the stage-I attention backward of all encoders runs as ONE fused launch
-    (csrc/rfn_path.hip attn_bwd_grouped: 96 blocks; with bf16x3 that launch also writes dP1 as bf16 planes).  Every
+    (csrc/rfn_path_common.hip attn_bwd_form: 96 blocks; with bf16x3 that launch also writes dP1 as bf16 planes).  Every
     gradient against the oracle, greedy ids bit-exact."""
     import recurrent_fusion_network_amd as R
     from oracle import rfn_oracle as O

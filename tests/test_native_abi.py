@@ -122,3 +122,108 @@ def test_model_shell_schema_and_loud_failure_on_cpu():
     shapes5 = O.param_shapes(cfg)
     assert all(tuple(v.shape) == shapes5[k] for k, v in m5.state_dict().items())
     assert m5.decoder.h2h.weight.shape[0] == 5 * 16 and m5.review_steps_individual[0].lstm[0].H2h.weight.shape[0] == 4 * 16
+
+
+_OK_DIMS = dict(M=2, R=16, A=16, E=16, T1=3, T2=3, K=20, V1=51, L=[5, 7], D=[24, 40], Fc=[24, 32])
+
+
+def _refused_call(N, entry, defects):
+    """One call of a path entry point whose arguments are sound except for `defects`.  Every pointer is the same dummy address:
+    a refused call returns before it reads through any of them and before anything is launched."""
+    kw = dict(_OK_DIMS)
+    if 'bad_dims' in defects:
+        kw['R'] = 0
+    seed_dev = bool({'seed_zero', 'seed_misaligned'} & set(defects))
+    d = N.make_dims(path_flags=N.PATH_OPT_SEED_DEV if seed_dev else 0, **kw)
+    good = N.make_dims(**_OK_DIMS)                      # sizes the workspace whatever `d` has become
+    dp = None if 'null_dims' in defects else C.byref(d)
+    P = C.c_void_p(0x10000)
+    B = 0 if 'B0' in defects else 3
+    S = 0 if 'S0' in defects else 4
+    s = S if 's_high' in defects else (-1 if 's_negative' in defects else 1)
+    prm = None if 'null_prm' in defects else P
+    seed = 0 if 'seed_zero' in defects else (0x10004 if 'seed_misaligned' in defects else 0x10000)
+    gp = C.byref(good)
+    W = 2                                               # beam width
+    if entry.startswith('rfn_prefix'):
+        size = N.lib.rfn_prefix_ws_bytes(gp, 3, 0 if entry == 'rfn_prefix_fwd_from_state' else 1)
+    elif entry in ('rfn_decoder_step', 'rfn_decoder_loop_ex2', 'rfn_beam_loop_ex'):
+        size = N.lib.rfn_decoder_step_ws_bytes(gp, 3 * W if entry == 'rfn_beam_loop_ex' else 3)
+    else:
+        size = N.lib.rfn_decoder_ws_bytes(gp, 3, 4, 1)
+    assert size > 0
+    ws = None if 'null_ws' in defects else P
+    wsb = size - 1 if 'ws_short' in defects else size
+    V1 = _OK_DIMS['V1']
+    args = {
+        'rfn_prefix_fwd': lambda: [dp, B, prm, P, P, P, P, P, P, ws, wsb, 1, seed, None],
+        'rfn_prefix_fwd_from_state': lambda: [dp, B, prm, P, P, P, P, P, P, P, ws, wsb, None],
+        'rfn_prefix_bwd': lambda: [dp, B, prm, P, P, P, P, P, P, P, ws, wsb, seed, 1, None],
+        'rfn_prefix_bwd_wgrad': lambda: [dp, B, P, P, ws, wsb, 0, 3, None],
+        'rfn_decoder_fwd': lambda: [dp, B, S, prm, P, P, P, P, S, P, ws, wsb, 1, seed, None],
+        'rfn_decoder_fwd_begin': lambda: [dp, B, S, prm, P, P, P, ws, wsb, 1, None],
+        'rfn_decoder_fwd_step': lambda: [dp, B, S, s, prm, P, P, S, P, ws, wsb, 1, seed, None],
+        'rfn_decoder_bwd': lambda: [dp, B, S, prm, P, P, P, P, S, P, P, P, P, P, P, ws, wsb, seed, None],
+        'rfn_decoder_step': lambda: [dp, B, prm, P, P, P, P, P, P, P, V1, ws, wsb, seed, 0, None],
+        'rfn_decoder_loop_ex2': lambda: [dp, B, S, prm, P, P, P, P, 0, 1.0, None, P, V1, B * V1, P, S, P, S, P, P, ws, wsb, seed, None, None, None],
+        'rfn_beam_loop_ex': lambda: [dp, B, W, S, prm] + [P] * 17 + [4, ws, wsb, seed, None, None],
+        'rfn_decoder_fwd_sampled': lambda: [dp, B, S, prm, P, P, P, P, S, 0.5, 1.0, P, P, P, ws, wsb, 1, seed, None],
+    }[entry]()
+    return getattr(N.lib, entry)(*args)
+
+
+# Expected codes: what the library of the commit before the path sources were split returned for the same calls.
+# 'a+b': two defects in one call, to pin which check wins.  -1 RFN_ERR_SHAPE, -4 RFN_ERR_WORKSPACE, -5 RFN_ERR_ARG.
+_REFUSALS = {
+    'rfn_prefix_fwd': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'null_prm': -5, 'ws_short': -4,
+        'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5,
+        'bad_dims+seed_zero': -5, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5, 'null_prm+ws_short': -5},
+    'rfn_prefix_fwd_from_state': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'null_prm': -5,
+        'ws_short': -4, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5, 'null_prm+ws_short': -5},
+    'rfn_prefix_bwd': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'null_prm': -5, 'ws_short': -4,
+        'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5,
+        'bad_dims+seed_zero': -1, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5, 'null_prm+ws_short': -5},
+    'rfn_prefix_bwd_wgrad': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'ws_short': -4, 'B0+null_ws':
+        -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5},
+    'rfn_decoder_fwd': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'ws_short': -4, 'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1,
+        'null_ws+ws_short': -5, 'bad_dims+seed_zero': -1, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5,
+        'null_prm+ws_short': -5, 'S0+null_prm': -1},
+    'rfn_decoder_fwd_begin': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'ws_short': -4, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5, 'null_prm+ws_short': -5,
+        'S0+null_prm': -1},
+    'rfn_decoder_fwd_step': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 's_high': -1,
+        's_negative': -1, 'null_prm': -5, 'ws_short': -4, 'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1,
+        'bad_dims+null_ws': -1, 'null_ws+ws_short': -5, 'bad_dims+seed_zero': -1, 'B0+seed_zero': -5,
+        'seed_misaligned+null_ws': -5, 'null_prm+ws_short': -5, 'S0+null_prm': -1},
+    'rfn_decoder_bwd': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'ws_short': -4, 'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1,
+        'null_ws+ws_short': -5, 'bad_dims+seed_zero': -1, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5,
+        'null_prm+ws_short': -5, 'S0+null_prm': -1},
+    'rfn_decoder_step': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'null_prm': -5, 'ws_short': -4,
+        'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'null_ws+ws_short': -5,
+        'bad_dims+seed_zero': -1, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5, 'null_prm+ws_short': -5},
+    'rfn_decoder_loop_ex2': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'bad_dims+seed_zero': -1,
+        'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5, 'S0+null_prm': -1},
+    'rfn_beam_loop_ex': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1, 'bad_dims+seed_zero': -1,
+        'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5, 'S0+null_prm': -1},
+    'rfn_decoder_fwd_sampled': {'null_dims': -5, 'bad_dims': -1, 'B0': -1, 'null_ws': -5, 'S0': -1, 'null_prm': -5,
+        'ws_short': -4, 'seed_zero': -5, 'seed_misaligned': -5, 'B0+null_ws': -1, 'bad_dims+null_ws': -1,
+        'null_ws+ws_short': -5, 'bad_dims+seed_zero': -1, 'B0+seed_zero': -5, 'seed_misaligned+null_ws': -5,
+        'null_prm+ws_short': -5, 'S0+null_prm': -1},
+}
+
+def test_path_entry_points_refuse_bad_calls_before_launching():
+    """The table of refused calls to the path entry points that take a workspace or a seed: NULL / bad dims, B = 0, S = 0, s out of
+    range, NULL prm, NULL workspace, a workspace one byte short, a zero or misaligned seed under RFN_PATH_OPT_SEED_DEV -- one
+    defect per call, plus a few pairs.  Every one returns its code before anything is launched (no GPU needed).  A workspace
+    one byte short is not in the table for the two decode loops: they size it inside their first step, after the BOS fill."""
+    N = native()
+    assert len(_REFUSALS) == 12
+    for entry, cases in _REFUSALS.items():
+        for defects, code in cases.items():
+            assert code < 0
+            got = _refused_call(N, entry, defects.split('+'))
+            assert got == code, (entry, defects, got, code)

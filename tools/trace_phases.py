@@ -1,6 +1,6 @@
 """Per-phase breakdown of one C3 train step from a `rocprofv3 --kernel-trace` CSV of bench.py.
 
-Phases are delimited by marker kernels of the fixed launch schedule (csrc/rfn_path.hip): the grouped feature
+Phases are delimited by marker kernels of the fixed launch schedule (csrc/rfn_path_prefix.hip, rfn_path_decoder.hip): the grouped feature
 projections, the stage-I forward recurrence, stage II + decoder forward + criterion, the logit-layer backward, decoder +
 stage-II backward, the stage-I backward recurrence, the stage-I weight gradients, clamp+Adam.  Prints span, kernel time
 and the heaviest kernels of each phase for the last complete step in the trace.
