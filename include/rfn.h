@@ -262,7 +262,35 @@ int rfn_copy_small_f32(float* const* dst_host, const float* const* src_host, int
  *   hproj[b,:]  = h_2_att_h(pre_h[b,:])        (GEMM, :36)
  * scores:  alpha[b,:] = softmax_l( w . tanh(proj[b,l,:] + hproj[b,:]) + b_o )      (:39-44)
  * context: z[b,:]     = sum_l alpha[b,l] * att_seq[b,l,:]                          (:45-47)
- * Element (b,l,x) of proj / att_seq lives at base + b*stride_b + l*stride_l + x. */
+ * Element (b,l,x) of proj / att_seq lives at base + b*stride_b + l*stride_l + x.
+ *
+ * Alignment and strides (every rfn_attn_* entry): any float-aligned pointer and any stride is accepted.  The fast case is
+ * the aligned one: 16-byte loads / stores are used for proj and dproj when A % 4 == 0, both pointers are 16-byte aligned and
+ * all their strides are multiples of 4 floats; for att_seq and z when D % 4 == 0, the pointers are 16-byte aligned and
+ * sb, sl, ldz are multiples of 4 (the fused backward decides for att_seq independently of proj / dproj).  Otherwise the
+ * same entry runs its scalar instantiation: same results to rounding (another summation order within a row), not the same
+ * bits.  hproj, w_out, b_out, alpha, dalpha, dz (any lddz) and the raw-score scratch are only ever accessed as scalars and
+ * never matter.  In a grouped or heterogeneous launch the decision is all-or-nothing: one encoder off these conditions
+ * puts every encoder of the launch on the scalar kernels.  rfn_attn_small_bwd takes its 16-byte form only when ALL of
+ * A % 4 == 0, D % 4 == 0, every stride (lddz included) a multiple of 4 and proj, att_seq, dproj, dhproj, dw_part, datt_seq
+ * 16-byte aligned hold; rfn_attn_small_fwd decides per encoder from A and proj alone.
+ *
+ * Limits (RFN_ERR_SHAPE, nothing launched, no output touched -- the raw-score scratch included); Xp = X rounded up to 4:
+ *   every extent (B, L, A, D) >= 1; 1 <= ngroups <= RFN_MAX_ENC;
+ *   rfn_attn_scores_fwd, rfn_attn_fwd[_grouped|_het]:      2 * Ap floats <= 64 KiB                      (A <= 8192)
+ *   rfn_attn_context_fwd, rfn_attn_fwd[_grouped|_het]:     L floats <= 64 KiB                           (L <= 16384)
+ *   rfn_attn_context_bwd_dalpha:                           Dp floats <= 64 KiB                          (D <= 16384)
+ *   rfn_attn_scores_bwd:                                   34 * Ap + 16 + L floats <= 150 KiB
+ *   rfn_attn_bwd[_grouped|_grouped_ks|_het]:               34 * Ap + 16 + 2 * Lp + Dp floats <= 150 KiB (largest L, D of the launch)
+ *   rfn_attn_small_fwd:                                    L <= 1024 and 2 * Ap + L floats <= 64 KiB
+ *   rfn_attn_small_bwd:                                    L <= 1024 and 2 * Ap + Dp + 2 * Lp floats <= 64 KiB
+ *   rfn_attn_context_bwd_dseq:                             none beyond the extents.
+ * A NULL required pointer (or host array, or array entry) is RFN_ERR_ARG; b_out, its array, and datt_seq of
+ * rfn_attn_small_bwd may be NULL.
+ *
+ * Aliasing: dproj may be proj itself (same pointer and strides: in place) in every
+ * backward entry; scores_scratch must not be alpha (RFN_ERR_ARG).  No other output may overlap an input or another
+ * output; inputs may overlap each other freely.  (tests/test_attention_edges_gpu.py pins all of the above.) */
 int rfn_attn_scores_fwd(const float* proj, int64_t proj_sb, int64_t proj_sl, const float* hproj,
                         const float* w_out, const float* b_out, int B, int L, int A, float* alpha,
                         void* stream);
@@ -306,7 +334,9 @@ int rfn_attn_bwd(const float* proj, int64_t proj_sb, int64_t proj_sl, const floa
  * encoder: misc/RecurrentFusionModel.py:139-146) -- in ONE pair of launches / one launch: the M cells of a stage-I step are
  * independent (misc/RecurrentFusionModel.py:101-114).  Contiguous layouts: proj / dproj (B, L_g, A), att_seq (B, L_g, D_g),
  * z / dz (B, D_g), alpha and the raw-score scratch (B, L_g).  Same kernels and per-row arithmetic as the per-encoder calls:
- * bit-identical results.  L_host / D_host: host arrays of ngroups ints. */
+ * bit-identical results, as long as the per-encoder call takes the same (16-byte or scalar) instantiation -- see the
+ * all-or-nothing rule above: a map with D_g % 4 != 0 puts its neighbours on the scalar context / dalpha code as well.
+ * L_host / D_host: host arrays of ngroups ints. */
 int rfn_attn_fwd_het(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
                      const float* const* b_out, const float* const* att_seq, int B, const int* L_host, int A,
                      const int* D_host, float* const* scores_scratch, float* const* alpha, float* const* z, void* stream);

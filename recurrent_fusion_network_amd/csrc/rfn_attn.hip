@@ -206,8 +206,10 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_context_fwd_k(const AttnEncP
     }
 }
 
+// Everything launch_context_d refuses, without the launch: the two-launch forward asks first, so that a call it refuses has
+// not already run its score kernel (nothing is launched on an error, rfn.h).
 template <bool SOFTMAX>
-static int launch_context_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm, int B, hipStream_t st) {
+static int check_context_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm, int B, bool* vec_out) {
     if (B <= 0 || ng < 1 || ng > RFN_MAX_ENC || Dm.maxL <= 0 || Dm.maxD <= 0) return RFN_ERR_SHAPE;
     if ((size_t)Dm.maxL * sizeof(float) > 64 * 1024) return RFN_ERR_SHAPE;
     bool vec = true;
@@ -216,6 +218,13 @@ static int launch_context_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm, in
         vec = vec && (Dm.D[g] % 4 == 0) && (Dm.xsb[g] % 4 == 0) && (Dm.xsl[g] % 4 == 0) && (Dm.ldz[g] % 4 == 0) &&
               rfn_aligned16(E.x[g]) && rfn_aligned16(E.z[g]);
     }
+    *vec_out = vec;
+    return RFN_OK;
+}
+template <bool SOFTMAX>
+static int launch_context_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm, int B, hipStream_t st) {
+    bool vec = false;
+    RFN_TRY(check_context_d<SOFTMAX>(ng, E, Dm, B, &vec));
     if (vec)
         hipLaunchKernelGGL((attn_context_fwd_k<true, SOFTMAX>), dim3(rfn_cdiv(Dm.maxD, 4 * ATT_THREADS), B, ng),
                            dim3(ATT_THREADS), Dm.maxL * sizeof(float), st, E, Dm);
@@ -300,6 +309,9 @@ extern "C" int rfn_attn_fwd_grouped(int ngroups, const float* const* proj, int64
         E.alpha_out[g] = alpha[g];
         E.z[g] = z[g];
     }
+    if (L <= 0 || D <= 0) return RFN_ERR_SHAPE;
+    bool vec_unused = false;
+    RFN_TRY(check_context_d<true>(ngroups, E, attn_dims_uniform(ngroups, L, D, 0, 0, sb, sl, 0, 0, ldz), B, &vec_unused));
     RFN_TRY(launch_scores_raw_g(ngroups, E, proj_sb, proj_sl, B, L, A, (hipStream_t)stream));
     return launch_context<true>(ngroups, E, sb, sl, B, L, D, ldz, (hipStream_t)stream);
 }
@@ -716,6 +728,8 @@ extern "C" int rfn_attn_fwd_het(int ngroups, const float* const* proj, const flo
         E.alpha_out[g] = alpha[g];
         E.z[g] = z[g];
     }
+    bool vec_unused = false;
+    RFN_TRY(check_context_d<true>(ngroups, E, Dm, B, &vec_unused));
     RFN_TRY(launch_scores_raw_d(ngroups, E, Dm, B, A, (hipStream_t)stream));
     return launch_context_d<true>(ngroups, E, Dm, B, (hipStream_t)stream);
 }
