@@ -120,7 +120,32 @@ int rfn_param_shape(const rfn_dims* d, int idx, int64_t* rows, int64_t* cols);
  * lda; B is [N,K] = an nn.Linear weight).  *_kfast = 0: the output index is contiguous (A is
  * [K,M] with row stride lda; B is [K,N]).  Up to RFN_GEMM_MAXSEG K-segments accumulate into one C
  * (gate sums such as H2h(H) + z2h(z), misc/RecurrentFusionModel.py:53); up to RFN_GEMM_MAXGROUP
- * same-shape problems run in one launch (the per-step weights of one encoder). */
+ * same-shape problems run in one launch (the per-step weights of one encoder).
+ *
+ * Operands.  Any base pointer and any lda / ldb / ldc >= the row length are accepted.  The 16-byte (float4) staging is
+ * taken when EVERY segment of EVERY group has A and B 16-byte aligned, lda % 4 == 0 and ldb % 4 == 0, and whole float4s
+ * along the contiguous index: K_s % 4 == 0 for a *_kfast = 1 operand, M % 4 == 0 (A) / N % 4 == 0 (B) for a *_kfast = 0
+ * one; otherwise the whole call stages scalars (slower, same results).  C, bias and a_colsum are accessed as scalars by
+ * the tile kernels and need no alignment; the separate split-K reduce reads and writes them 16 bytes wide only when
+ * N % 4 == 0, every C is 16-byte aligned with ldc % 4 == 0 and every bias is 16-byte aligned.  a_kfast / b_kfast must be
+ * the same in every segment and group (RFN_ERR_SHAPE).
+ * K rule.  K_s >= 1 (K_s < 0: RFN_ERR_ARG).  K_s = 0 is accepted only when EVERY segment of the problem is empty -- the
+ * call then means C (+)= sum_s bias_s -- and refused with RFN_ERR_SHAPE next to a non-empty segment (the tile kernels
+ * count an empty segment as no K step but would spend one on it).  Leave an empty segment out instead.
+ * M <= 0 or N <= 0: RFN_OK, nothing is written.  A refused call launches nothing and writes nothing.
+ *
+ * Bit-identical results (the same k-ordered chain per output element, asserted by tests/test_gemm_edges_gpu.py):
+ *   - float4 and scalar staging of the same values; any leading dimensions; any tile shape the launcher picks (128 x 128,
+ *     64 x 64, the half-height and quarter tiles of a last round); LDS-DMA and register staging: an UNSPLIT product does
+ *     not depend on RFN_GEMM_OPT_LDS_LEAN / RFN_GEMM_OPT_NO_DMA at all;
+ *   - repeated calls, with or without a K split (the split is a function of the arguments, the partial tiles are added in
+ *     K-range order);
+ *   - under a K split: RFN_GEMM_OPT_LDS_LEAN == default, always (its 16-deep kernel cuts the K ranges of the layout's
+ *     default kernel); the in-kernel ticket finish == the separate reduce; rfn_gemm_f32_lstm == rfn_gemm_f32_ws +
+ *     rfn_lstm_fwd_grouped; RFN_GEMM_OPT_NO_DMA == default wherever both cut the same K ranges: always on the 64 x 64
+ *     tile and for a_kfast = b_kfast = 1, and for the other layouts of a split big-tile product (default K step 16,
+ *     register kernel 32) unless 0 < (K / 32) mod s <= s / 2 -- there the two differ by fp32 re-association only.
+ *   A split product differs from the unsplit one by fp32 re-association. */
 #define RFN_GEMM_MAXSEG 8
 #define RFN_GEMM_MAXGROUP 8
 typedef struct rfn_gemm_seg {
@@ -146,7 +171,11 @@ int rfn_gemm_f32(int M, int N, int ngroups, const rfn_gemm_problem* problems_hos
                  void* stream);
 /* Same, with a scratch buffer (>= 1 MiB, 16-B aligned).  Skinny problems (M = batch rows, few output tiles)
  * are then cut along K across thread blocks; the partial tiles are summed in a fixed order by a second
- * kernel, so the result is deterministic (it differs from the unsplit result only by fp32 re-association). */
+ * kernel, so the result is deterministic (it differs from the unsplit result only by fp32 re-association).
+ * A buffer below 1 MiB or not 16-byte aligned is ignored (the unsplit product, bit for bit; the buffer is not touched).
+ * Only whole MiB count: a split into s ranges needs (M * N + M) * ngroups * s floats <= (ws_bytes >> 20) MiB and is
+ * capped accordingly; the launch writes the first (M * N [+ M with an a_colsum]) * ngroups * s floats and nothing behind
+ * them.  The buffer must not be shared by launches that can overlap. */
 int rfn_gemm_f32_ws(int M, int N, int ngroups, const rfn_gemm_problem* problems_host, int accumulate,
                     void* ws, size_t ws_bytes, void* stream);
 /* Same, with option bits (every tuning choice travels with the call: the library reads no environment variable and
@@ -154,9 +183,11 @@ int rfn_gemm_f32_ws(int M, int N, int ngroups, const rfn_gemm_problem* problems_
  *   RFN_GEMM_OPT_LDS_LEAN  the long big-tile GEMMs take 32 KB of LDS per block (64 KB per CU for a one-round
  *                          weight-gradient launch) instead of 64 KB per block, so that kernels of other streams --
  *                          RCCL's under data parallelism -- can co-reside instead of waiting for a
- *                          multi-millisecond GEMM to drain; same results, same speed within 1 %;
- *   RFN_GEMM_OPT_NO_DMA    interior big tiles use the register-staged kernel instead of the LDS-DMA one (A/B hook;
- *                          both give bit-identical results: same k order per output element);
+ *                          multi-millisecond GEMM to drain; bit-identical results, split along K or not; same speed
+ *                          within 1 %;
+ *   RFN_GEMM_OPT_NO_DMA    interior tiles use the register-staged kernel instead of the LDS-DMA one (A/B hook; same k
+ *                          order per output element: bit-identical when unsplit and wherever both kernels cut the same K
+ *                          ranges -- see the list above -- otherwise equal up to fp32 re-association);
  *   RFN_GEMM_OPT_BF16X3    (rfn_dims.gemm_flags only) the two long products of the path -- the hoisted stage-I feature
  *                          projection and its weight gradient -- run on the bf16 matrix cores with every f32 operand
  *                          held as three bf16 planes and six plane products accumulated in f32 (rfn_x3_*, below):
@@ -182,7 +213,10 @@ int rfn_gemm_f32_opt(int M, int N, int ngroups, const rfn_gemm_problem* problems
  * (the library leaves them zero: a caller zeroes them once per workspace and keeps them for its GEMMs).  The K ranges of
  * an output tile draw tickets on the tile's counter; the last one to arrive adds the partial tiles in K-range order
  * (the order the separate reduce kernel uses: bit-identical results) -- no second launch.  Launches with more output
- * tiles than counters use the separate reduce kernel. */
+ * tiles than counters (ngroups * ceil(M / tile) * ceil(N / tile), tile = 128 or 64 as the launcher picks: 64 x 64 tiles
+ * are the safe count) use the separate reduce kernel and leave every counter alone, as do unsplit launches and
+ * rfn_gemm_f32_lstm.  Counters need 4-byte alignment only; a counter that is not zero on entry gives a wrong or unfinished
+ * tile.  Launches that can overlap must not share counters. */
 int rfn_gemm_f32_tk(int M, int N, int ngroups, const rfn_gemm_problem* problems_host, int accumulate, void* ws,
                     size_t ws_bytes, unsigned flags, int32_t* tickets, int n_tickets, void* stream);
 /* Gate GEMM + LSTM update in one call (stage I: misc/RecurrentFusionModel.py:53-73): gates_g[M, 4R] = sum_s A_s W_s^T + b

@@ -749,7 +749,12 @@ __device__ __forceinline__ void gemm_tile_dma(const GemmArgs& args, const int gr
     for (int s = 0; s < P.nseg; ++s) total_iters += P.seg[s].K / BK;
     int seg = 0, k0 = 0;
     if (splitk > 1) {
-        const int per = (total_iters + splitk - 1) / splitk;
+        // K ranges are cut in steps of the DEFAULT kernel of this layout, whatever this instantiation's own BK is: the
+        // 16-deep lean form of a [row][k] x [row][k] product (default: 32-deep) then adds the same partial sums in the
+        // same order as the default and stays bit-identical to it under every split.  RU = 1 for every default kernel.
+        constexpr int RBK = (AK && BKF) ? GEMM_DMA_BK : GEMM_DMA_BK_XX;
+        constexpr int RU = RBK > BK ? RBK / BK : 1;
+        const int per = (total_iters / RU + splitk - 1) / splitk * RU;
         int it_begin = ks * per;
         const int it_end = min(total_iters, it_begin + per);
         total_iters = max(0, it_end - it_begin);
@@ -1392,15 +1397,20 @@ static int gemm_entry(int M, int N, int ngroups, const rfn_gemm_problem* problem
     for (int g = 0; g < ngroups; ++g) {
         const rfn_gemm_problem& p = problems[g];
         if (p.nseg < 1 || p.nseg > RFN_GEMM_MAXSEG || !p.C) return RFN_ERR_SHAPE;
+        bool k_empty = false, k_full = false;
         for (int s = 0; s < p.nseg; ++s) {
             const rfn_gemm_seg& sg = p.seg[s];
             if (!sg.A || !sg.B || sg.K < 0) return RFN_ERR_ARG;
+            (sg.K == 0 ? k_empty : k_full) = true;
             if ((sg.a_kfast != 0) != (ak != 0) || (sg.b_kfast != 0) != (bk != 0)) return RFN_ERR_SHAPE;
             // float4 staging needs 16-B aligned rows and whole float4s along the contiguous index
             const bool a_ok = rfn_aligned16(sg.A) && (sg.lda % 4 == 0) && (ak ? sg.K % 4 == 0 : M % 4 == 0);
             const bool b_ok = rfn_aligned16(sg.B) && (sg.ldb % 4 == 0) && (bk ? sg.K % 4 == 0 : N % 4 == 0);
             vec = vec && a_ok && b_ok;
         }
+        // The tile kernels count an empty segment as zero K steps but would spend a load on it, and so stop one step
+        // short of the end: K = 0 is accepted only when every segment of the problem is empty (C (+)= sum of the biases).
+        if (k_empty && k_full) return RFN_ERR_SHAPE;
         a.g[g] = p;
     }
     hipStream_t st = (hipStream_t)stream;

@@ -137,7 +137,10 @@ def test_gemm_split_k_is_deterministic_and_correct(dev, ak, bk):
 def test_gemm_medium_products_split_by_the_cost_model(dev, M, Nn, K, ak, bk, groups):
     """Products below two rounds of 128 x 128 tiles take their K split from launch_tile's cost model (tools/split_probe.py):
     every choice must match fp64, be deterministic, not depend on the LDS-lean flag (data-parallel hosts set it: the step
-    must stay bit-equal), and a forced different split must agree to re-association error."""
+    must stay bit-equal), and a forced different split must agree to re-association error.  The layouts here all take a
+    16-deep default kernel, whose K ranges the lean kernel shares by construction, and RFN_GEMM_OPT_NO_DMA is never set:
+    the [row][k] x [row][k] layout (default step 32, lean step 16) and NO_DMA under every split are swept by
+    test_gemm_edges_gpu.py::test_medium_big_tile_split."""
     n = N()
     ws = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
     g = torch.Generator(device=dev).manual_seed(M + Nn + K)
