@@ -11,19 +11,18 @@
 //   * done beams appended in construction order when END is emitted or t == seq_length (:508-514);
 //   * an image with no candidate left stops (:480-481).
 // Nothing is read back per step; the host sorts the (few) done beams once at the end.
-#include "rfn_common.h"
+#include "rfn_rows.h"
 
 #define BEAM_MAX_W 32     /* beams per image; the full-row form (rfn_beam_step: phase 1 below) serves up to BEAM_WAVES of them */
 #define BEAM_MAX_S 64     /* decode steps a block keeps the beams' histories for (seq_length) */
 #define BEAM_THREADS 1024
 #define BEAM_WAVES 16
 
-// (value desc, index asc): the order in which the reference's descending sort lists the columns it uses
-__device__ __forceinline__ bool beam_before(float x, int i, float y, int j) { return x > y || (x == y && i < j); }
-
 // One block per image.  Phase 1: top `cols` columns of every live beam row -- each row is cut over 16 / rows waves,
 // every lane keeps a sorted top-LW list of its strided share in registers (one pass over the row), the wave merges
-// the lanes' lists with `cols` arg-max butterflies, one lane merges the waves' lists.  Phase 2: thread 0 builds and
+// the lanes' lists with `cols` arg-max butterflies, one lane merges the waves' lists.  The list and its order (row_before:
+// value desc, index asc, as the reference's descending sort lists the columns it uses) are rfn_rows.h's, the ones
+// rfn_log_softmax_topk uses: the two forms of the step agree because they share them.  Phase 2: thread 0 builds and
 // stably sorts the <= W*W candidates in LDS and decides forks / done slots; all threads then write the forked
 // beam_seq / beam_logprobs columns and the done beams in parallel.
 template <int LW>
@@ -62,50 +61,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
         const float* row = logp + (long)(k * W + q) * ldl;
         const int chunk = (V1 + wpr - 1) / wpr;
         const int v0 = part * chunk, v1 = min(V1, v0 + chunk);
-        float tv[LW];
-        int ti[LW];
-#pragma unroll
-        for (int j = 0; j < LW; ++j) {
-            tv[j] = -INFINITY;
-            ti[j] = 0x7fffffff;
-        }
-        for (int v = v0 + lane; v < v1; v += 64) {   // ascending v per lane: a later equal value stays behind
-            float x = row[v];
-            if (x > tv[LW - 1] || (ti[LW - 1] == 0x7fffffff)) {
-                int xi = v;
-#pragma unroll
-                for (int j = 0; j < LW; ++j) {       // sorted insert by compare-exchange down the list
-                    const bool fwd = beam_before(x, xi, tv[j], ti[j]);
-                    const float ov = tv[j];
-                    const int oi = ti[j];
-                    tv[j] = fwd ? x : ov;
-                    ti[j] = fwd ? xi : oi;
-                    x = fwd ? ov : x;
-                    xi = fwd ? oi : xi;
-                }
-            }
-        }
+        RowTopList<LW> top;
+        top.fill();
+        for (int v = v0 + lane; v < v1; v += 64) top.offer(row[v], v);   // ascending v per lane: a later equal value stays behind
         for (int c = 0; c < cols; ++c) {             // wave merge: pop the best head `cols` times
-            float best = tv[0];
-            int bi = ti[0];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(best, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (beam_before(ob, oi, best, bi)) {
-                    best = ob;
-                    bi = oi;
-                }
-            }
-            if (ti[0] == bi && bi != 0x7fffffff) {   // this lane owned the winner: pop it
-#pragma unroll
-                for (int j = 0; j + 1 < LW; ++j) {
-                    tv[j] = tv[j + 1];
-                    ti[j] = ti[j + 1];
-                }
-                tv[LW - 1] = -INFINITY;
-                ti[LW - 1] = 0x7fffffff;
-            }
+            float best;
+            int bi;
+            top.wave_pop(best, bi);
             if (lane == 0) {
                 wys[wave][c] = best;
                 wix[wave][c] = bi;
@@ -134,8 +96,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
                 if (pos[p] >= cols) continue;
                 const int w = tid * wpr + p;
                 if (wix[w][pos[p]] == 0x7fffffff) continue;
-                if (bp < 0 || beam_before(wys[w][pos[p]], wix[w][pos[p]], wys[tid * wpr + bp][pos[bp]],
-                                          wix[tid * wpr + bp][pos[bp]]))
+                if (bp < 0 || row_before(wys[w][pos[p]], wix[w][pos[p]], wys[tid * wpr + bp][pos[bp]],
+                                         wix[tid * wpr + bp][pos[bp]]))
                     bp = p;
             }
             ys[tid][c] = wys[tid * wpr + bp][pos[bp]];

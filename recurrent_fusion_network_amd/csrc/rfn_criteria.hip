@@ -1,0 +1,380 @@
+// The three criteria and their gradients: the XE language loss (from log-probs, and fused from the logits), the RL reward
+// criterion, and nn.MultiLabelMarginLoss for the reason heads.  One block of 256 per row writes the row's loss term; sum_k /
+// sum_groups_k add the terms in a fixed order (no float atomics), so a loss is bitwise reproducible.
+#include <string.h>
+
+#include "rfn_rows.h"
+
+// ---- fixed-order sum of n floats -> out[0] ---------------------------------------------------------
+__global__ __launch_bounds__(256) void sum_k(const float* __restrict__ x, int n, float scale, float* __restrict__ out,
+                                             int accumulate) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) s += x[i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s * scale : s * scale;
+}
+
+// ---- XE language loss (misc/utils.py:163-184) -------------------------------------------------------
+__global__ __launch_bounds__(256) void xe_loss_k(const float* __restrict__ logp, int T, int V1,
+                                                 const int64_t* __restrict__ target, long ld_t,
+                                                 const float* __restrict__ mask, long ld_m, float eps, float gcoef,
+                                                 const float* __restrict__ gdev, float* __restrict__ row_loss,
+                                                 float* __restrict__ dlogp) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, b = r / T, t = r - b * T;
+    const float* lp = logp + (long)r * V1;
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    const float uni = eps / (float)V1;
+    float term = 0.f;
+    if (row_loss) {
+        if (eps > 0.f) {
+            float s = 0.f;
+            for (int v = threadIdx.x; v < V1; v += 256) s += lp[v];
+            s = block_sum_256(s, red);
+            term = (1.0f - eps) * lp[tg] + uni * s;
+        } else {
+            term = lp[tg];
+        }
+        if (threadIdx.x == 0) row_loss[r] = -mk * term;
+    }
+    if (dlogp) {
+        float* d = dlogp + (long)r * V1;
+        const float gc = gdev ? gcoef * gdev[0] : gcoef;  // upstream d loss, read on the device (no host sync)
+        const float base = -mk * gc * uni;              // 0 when eps == 0
+        const float hot = -mk * gc * (1.0f - eps);
+        for (int v = threadIdx.x; v < V1; v += 256) d[v] = (v == tg) ? base + hot : base;
+    }
+}
+extern "C" int rfn_xe_loss_ex(const float* logp, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                              const float* mask, int64_t ld_mask, float eps, float gscale, const float* gscale_dev,
+                              float* scratch, float* loss_out, int accumulate_loss, float* dlogp, void* stream) {
+    if (B <= 0 || T <= 0 || V1 <= 0) return RFN_ERR_SHAPE;
+    if (!logp || !target || !mask || (loss_out && !scratch)) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(xe_loss_k, dim3(B * T), dim3(256), 0, st, logp, T, V1, target, (long)ld_target, mask,
+                       (long)ld_mask, eps, gscale / (float)B, gscale_dev, loss_out ? scratch : nullptr, dlogp);
+    RFN_CHECK_LAUNCH();
+    if (loss_out) {
+        hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, loss_out,
+                           accumulate_loss);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+extern "C" int rfn_xe_loss(const float* logp, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                           const float* mask, int64_t ld_mask, float eps, float gscale, float* scratch,
+                           float* loss_out, int accumulate_loss, float* dlogp, void* stream) {
+    return rfn_xe_loss_ex(logp, B, T, V1, target, ld_target, mask, ld_mask, eps, gscale, nullptr, scratch, loss_out,
+                          accumulate_loss, dlogp, stream);
+}
+
+// ---- XE language loss straight from the logits (misc/utils.py:163-184 + F.log_softmax of :276) --------------
+// The unfused pass writes log_prob (B, T, V+1), the criterion reads it back for the loss, writes d log_prob (B, T, V+1), and the
+// log-softmax backward reads both to write d logits: four passes over a 165 MB tensor at C3 that exist only because
+// `forward` has to hand `log_prob` to a caller-owned criterion (train.py:154-159).  When the caller asks for the LOSS
+// (RecurrentFusionModel.forward_loss) neither tensor is needed:
+//   forward : one pass over the time-major logits rows r = t * B + b -- the row's logsumexp (log_softmax_row: the same bits
+//             rfn_log_softmax_fwd would subtract) -> lse[r], and the row's loss term
+//             -mask * ((1 - eps) * (x[tg] - lse) + eps / V1 * (sum_v x[v] - V1 * lse)) -> row_loss[b * T + t]
+//   backward: d logits[v] = mask * g / B * (exp(x[v] - lse) - (1 - eps) * [v == tg] - eps / V1), written over the logits.
+// (sum_v d logp = -mask * g / B whatever eps is, which is what the log-softmax backward multiplies the probabilities with.)
+template <bool VEC>
+__global__ __launch_bounds__(256) void xe_logits_fwd_k(const float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ target, long ld_t,
+                                                       const float* __restrict__ mask, long ld_m, float eps,
+                                                       float* __restrict__ lse_out, float* __restrict__ row_loss) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, t = r / B, b = r - t * B;      // time-major rows
+    const float* x = logits + r * ldl;
+    f32x4 xr[LSM_R4];
+    const float lse = log_softmax_row<VEC>(x, V1, xr, red);
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    float term = x[tg] - lse;
+    if (eps > 0.f) {
+        float s = 0.f;
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) s += ((xr[j][0] - lse) + (xr[j][1] - lse)) + ((xr[j][2] - lse) + (xr[j][3] - lse));
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) s += x[v] - lse;
+        }
+        s = block_sum_256(s, red);
+        term = (1.0f - eps) * term + (eps / (float)V1) * s;
+    }
+    if (threadIdx.x == 0) {
+        lse_out[r] = lse;
+        row_loss[b * T + t] = -mk * term;
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void xe_logits_bwd_k(float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ target, long ld_t,
+                                                       const float* __restrict__ mask, long ld_m, float eps, float gcoef,
+                                                       const float* __restrict__ gdev, const float* __restrict__ lse_in) {
+    const int r = blockIdx.x, t = r / B, b = r - t * B;
+    float* x = logits + r * ldl;
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float c = mask[b * ld_m + t] * (gdev ? gcoef * gdev[0] : gcoef);     // mask * d loss / B
+    const float lse = lse_in[r], uni = eps / (float)V1, hot = 1.0f - eps;
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i), o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = c * ((expf(v[e] - lse) - uni) - ((4 * i + e == tg) ? hot : 0.f));
+            *reinterpret_cast<f32x4*>(x + 4 * i) = o;
+        }
+    } else {
+        for (int v = threadIdx.x; v < V1; v += 256) x[v] = c * ((expf(x[v] - lse) - uni) - ((v == tg) ? hot : 0.f));
+    }
+}
+extern "C" int rfn_xe_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target,
+                                 int64_t ld_target, const float* mask, int64_t ld_mask, float eps, float* lse,
+                                 float* scratch, float* loss_out, int accumulate_loss, void* stream) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || ldl < V1 || eps < 0.f || eps >= 1.f) return RFN_ERR_SHAPE;
+    if (!logits || !target || !mask || !lse || !scratch || !loss_out) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(xe_logits_fwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, lse, scratch);
+    else
+        hipLaunchKernelGGL(xe_logits_fwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, lse, scratch);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, loss_out, accumulate_loss);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+extern "C" int rfn_xe_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                                 const float* mask, int64_t ld_mask, float eps, const float* lse, float gscale,
+                                 const float* gscale_dev, void* stream) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || ldl < V1 || eps < 0.f || eps >= 1.f) return RFN_ERR_SHAPE;
+    if (!logits || !target || !mask || !lse) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(xe_logits_bwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, gscale / (float)B, gscale_dev, lse);
+    else
+        hipLaunchKernelGGL(xe_logits_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, gscale / (float)B, gscale_dev, lse);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- RL reward criterion, policy + entropy terms (misc/utils.py:50-72) ------------------------------------
+// One block per (b, t) row:  term = -pol(b,t) * mask(b,t) + entropy_reg * mask0(b,t) * sum_v lp*exp(lp),
+// mask0 = seq > 0, mask = [1, mask0[:, :-1]] (the step AFTER an END still counts), pol = input*reward or the
+// PPO-clip surrogate min(surr1, clamp(surr1, 1-c, 1+c)*reward) with surr1 = exp(input)/(1e-5+exp(old))*reward
+// (written as in the reference: it clamps surr1, not the ratio).  Gradients w.r.t. input and logprobs_all.
+__global__ __launch_bounds__(256) void rl_loss_k(const float* __restrict__ inp, long ld_in, const int64_t* __restrict__ seq,
+                                                 long ld_seq, const float* __restrict__ reward, long ld_rw,
+                                                 const float* __restrict__ lp_all, long lp_sb, long lp_st, int T, int V1,
+                                                 float entropy_reg, const float* __restrict__ old_lp, long ld_old,
+                                                 int use_ppo, float ppo_clip, float inv_B_host, float* __restrict__ row_loss,
+                                                 float* __restrict__ d_inp, long ld_din, float* __restrict__ d_lp,
+                                                 long dlp_sb, long dlp_st, int T_all, const float* __restrict__ gdev) {
+    __shared__ float red[4];
+    // T_all >= T rows per caption are launched; rows t >= T do not enter the loss: their d_logprobs_all row is zero
+    const int r = blockIdx.x, b = r / T_all, t = r - b * T_all;
+    if (t >= T) {
+        if (d_lp) {
+            float* d = d_lp + b * dlp_sb + t * dlp_st;
+            for (int v = threadIdx.x; v < V1; v += 256) d[v] = 0.f;
+        }
+        return;
+    }
+    const float inv_B = gdev ? inv_B_host * gdev[0] : inv_B_host;   // upstream d loss, read on the device (no host sync)
+    const float m0 = (seq[b * ld_seq + t] > 0) ? 1.f : 0.f;
+    const float mk = (t == 0) ? 1.f : ((seq[b * ld_seq + t - 1] > 0) ? 1.f : 0.f);
+    const float* lp = lp_all + b * lp_sb + t * lp_st;
+    if (row_loss) {
+        float e = 0.f;
+        if (m0 != 0.f && entropy_reg != 0.f)
+            for (int v = threadIdx.x; v < V1; v += 256) e += lp[v] * expf(lp[v]);
+        e = block_sum_256(e, red);
+        if (threadIdx.x == 0) {
+            const float x = inp[b * ld_in + t], rw = reward[b * ld_rw + t];
+            float pol;
+            if (use_ppo) {
+                const float ratio = expf(x) / (1e-5f + expf(old_lp[b * ld_old + t]));
+                const float s1 = ratio * rw;
+                const float s2 = fminf(fmaxf(s1, 1.f - ppo_clip), 1.f + ppo_clip) * rw;
+                pol = fminf(s1, s2);
+            } else {
+                pol = x * rw;
+            }
+            row_loss[b * T + t] = -pol * mk + entropy_reg * m0 * e;
+        }
+    }
+    if (d_lp) {
+        float* d = d_lp + b * dlp_sb + t * dlp_st;
+        const float c = entropy_reg * m0 * inv_B;
+        for (int v = threadIdx.x; v < V1; v += 256) d[v] = (c != 0.f) ? c * expf(lp[v]) * (1.f + lp[v]) : 0.f;
+    }
+    if (d_inp && threadIdx.x == 0) {
+        const float x = inp[b * ld_in + t], rw = reward[b * ld_rw + t];
+        float g;
+        if (use_ppo) {
+            const float ratio = expf(x) / (1e-5f + expf(old_lp[b * ld_old + t]));
+            const float s1 = ratio * rw;
+            const float cl = fminf(fmaxf(s1, 1.f - ppo_clip), 1.f + ppo_clip);
+            const float s2 = cl * rw;
+            const float ds1 = ratio * rw;                                        // d surr1 / d input
+            const float ds2 = (s1 > 1.f - ppo_clip && s1 < 1.f + ppo_clip) ? ds1 * rw : 0.f;
+            g = (s1 <= s2) ? ds1 : ds2;
+        } else {
+            g = rw;
+        }
+        d_inp[b * ld_din + t] = -g * mk * inv_B;
+    }
+}
+extern "C" int rfn_rl_loss_ex(const float* input, int64_t ld_in, const int64_t* seq, int64_t ld_seq, const float* reward,
+                              int64_t ld_rw, const float* logprobs_all, int64_t lp_sb, int64_t lp_st, int B, int T, int T_all,
+                              int V1, float entropy_reg, const float* old_logprobs, int64_t ld_old, int use_ppo,
+                              float ppo_clip, const float* gscale_dev, float* scratch, float* loss_out, int accumulate_loss,
+                              float* d_input, int64_t ld_din, float* d_logprobs_all, int64_t dlp_sb, int64_t dlp_st,
+                              void* stream) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || T_all < T) return RFN_ERR_SHAPE;
+    if (!input || !seq || !reward || !logprobs_all || (loss_out && !scratch) || (use_ppo && !old_logprobs))
+        return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = d_logprobs_all ? T_all : T;      // the extra rows exist only to zero d_logprobs_all[:, T:]
+    hipLaunchKernelGGL(rl_loss_k, dim3(B * rows), dim3(256), 0, st, input, (long)ld_in, seq, (long)ld_seq, reward,
+                       (long)ld_rw, logprobs_all, (long)lp_sb, (long)lp_st, T, V1, entropy_reg, old_logprobs,
+                       (long)ld_old, use_ppo, ppo_clip, 1.0f / (float)B, loss_out ? scratch : nullptr, d_input,
+                       (long)ld_din, d_logprobs_all, (long)dlp_sb, (long)dlp_st, rows, gscale_dev);
+    RFN_CHECK_LAUNCH();
+    if (loss_out) {
+        hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, loss_out, accumulate_loss);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+extern "C" int rfn_rl_loss(const float* input, int64_t ld_in, const int64_t* seq, int64_t ld_seq, const float* reward,
+                           int64_t ld_rw, const float* logprobs_all, int64_t lp_sb, int64_t lp_st, int B, int T, int V1,
+                           float entropy_reg, const float* old_logprobs, int64_t ld_old, int use_ppo, float ppo_clip,
+                           float* scratch, float* loss_out, int accumulate_loss, float* d_input, int64_t ld_din,
+                           float* d_logprobs_all, int64_t dlp_sb, int64_t dlp_st, void* stream) {
+    return rfn_rl_loss_ex(input, ld_in, seq, ld_seq, reward, ld_rw, logprobs_all, lp_sb, lp_st, B, T, T, V1, entropy_reg,
+                          old_logprobs, ld_old, use_ppo, ppo_clip, nullptr, scratch, loss_out, accumulate_loss, d_input,
+                          ld_din, d_logprobs_all, dlp_sb, dlp_st, stream);
+}
+
+// ---- nn.MultiLabelMarginLoss (mean) -----------------------------------------------------------------
+// Row b: targets = ids before the first -1; loss_b = sum_{j in targets} sum_{i not target}
+// max(0, 1 - x[j] + x[i]) / K.  One block per row; hit counts per target through LDS integer atomics.
+struct MlmHeads {
+    const float* pred[RFN_MAX_ENC + 1];
+    float* dpred[RFN_MAX_ENC + 1];
+};
+__global__ __launch_bounds__(256) void mlm_k(const MlmHeads hd, int K, const int64_t* __restrict__ target, float gcoef,
+                                             const float* __restrict__ gdev, float* __restrict__ row_loss) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* x = sm;                                   // [K]
+    int* tg = reinterpret_cast<int*>(sm + K);        // [K] target list
+    int* cnt = tg + K;                               // [K] hits per target slot
+    unsigned char* is_t = reinterpret_cast<unsigned char*>(cnt + K);  // [K]
+    __shared__ int nt_s;
+    __shared__ float red[4];
+    const int b = blockIdx.x, head = blockIdx.y;
+    const float* pred = hd.pred[head];
+    float* dpred = hd.dpred[head];
+    if (gdev) gcoef *= gdev[0];
+    for (int i = threadIdx.x; i < K; i += 256) {
+        x[i] = pred[(long)b * K + i];
+        is_t[i] = 0;
+        cnt[i] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (; n < K; ++n) {
+            const long t = target[(long)b * K + n];
+            if (t < 0 || t >= K) break;
+            tg[n] = (int)t;
+            is_t[t] = 1;
+        }
+        nt_s = n;
+    }
+    __syncthreads();
+    const int nt = nt_s;
+    const float invK = 1.0f / (float)K;
+    float loss = 0.f;
+    for (int i = threadIdx.x; i < K; i += 256) {
+        float gi = 0.f;
+        if (!is_t[i]) {
+            for (int n = 0; n < nt; ++n) {
+                const float z = 1.0f - x[tg[n]] + x[i];
+                if (z > 0.f) {
+                    loss += z;
+                    gi += 1.0f;
+                    atomicAdd(&cnt[n], 1);
+                }
+            }
+        }
+        if (dpred) dpred[(long)b * K + i] = gi * invK * gcoef;  // targets fixed up below
+    }
+    loss = block_sum_256(loss, red);  // also orders the dpred writes above before the fix-up
+    if (row_loss && threadIdx.x == 0) row_loss[(long)head * gridDim.x + b] = loss * invK;
+    if (dpred && threadIdx.x == 0) {
+        // a duplicated target id receives the hits of every slot that names it
+        for (int n = 0; n < nt; ++n) dpred[(long)b * K + tg[n]] = 0.f;
+        for (int n = 0; n < nt; ++n) dpred[(long)b * K + tg[n]] -= (float)cnt[n] * invK * gcoef;
+    }
+}
+// out[0] (+)= scale * sum(x[g*n .. g*n+n)) for g = 0..G-1 in order: the per-head sums are added one after the other,
+// exactly as G calls of sum_k would
+__global__ __launch_bounds__(256) void sum_groups_k(const float* __restrict__ x, int n, int G, float scale,
+                                                    float* __restrict__ out, int accumulate) {
+    __shared__ float red[4];
+    float total = accumulate ? out[0] : 0.f;
+    for (int g = 0; g < G; ++g) {
+        float s = 0.f;
+        for (int i = threadIdx.x; i < n; i += 256) s += x[(long)g * n + i];
+        s = block_sum_256(s, red);
+        total = (g == 0 && !accumulate) ? s * scale : total + s * scale;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = total;
+}
+extern "C" int rfn_multilabel_margin_grouped(int nheads, const float* const* preds, int B, int K, const int64_t* target,
+                                             float scale, float gscale, const float* gscale_dev, float* scratch,
+                                             float* loss_out, int accumulate_loss, float* const* dpreds,
+                                             void* stream) {
+    if (nheads < 1 || nheads > RFN_MAX_ENC + 1 || B <= 0 || K <= 0) return RFN_ERR_SHAPE;
+    if (!preds || !target || (loss_out && !scratch)) return RFN_ERR_ARG;
+    const size_t lds = (size_t)K * (sizeof(float) + 2 * sizeof(int) + 1) + 16;
+    if (lds > 60 * 1024) return RFN_ERR_SHAPE;
+    MlmHeads hd;
+    memset(&hd, 0, sizeof(hd));
+    for (int h = 0; h < nheads; ++h) {
+        if (!preds[h]) return RFN_ERR_ARG;
+        hd.pred[h] = preds[h];
+        hd.dpred[h] = dpreds ? dpreds[h] : nullptr;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(mlm_k, dim3(B, nheads), dim3(256), lds, st, hd, K, target, scale * gscale / (float)B, gscale_dev,
+                       loss_out ? scratch : nullptr);
+    RFN_CHECK_LAUNCH();
+    if (loss_out) {
+        hipLaunchKernelGGL(sum_groups_k, dim3(1), dim3(256), 0, st, scratch, B, nheads, scale / (float)B, loss_out,
+                           accumulate_loss);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+extern "C" int rfn_multilabel_margin(const float* pred, int B, int K, const int64_t* target, float scale, float gscale,
+                                     float* scratch, float* loss_out, int accumulate_loss, float* dpred,
+                                     void* stream) {
+    if (!pred) return RFN_ERR_ARG;
+    return rfn_multilabel_margin_grouped(1, &pred, B, K, target, scale, gscale, nullptr, scratch, loss_out,
+                                         accumulate_loss, dpred ? &dpred : nullptr, stream);
+}

@@ -13,7 +13,7 @@ no boundary a kernel could stop at) or |c_J - p c_n| is at most NEAR of c_n; on 
 earlier or later.  For a kernel that sums fp32 __expf weights in blocks of at most 128 per thread and a 256-way tree the margin
 would be 1e-4 (sum (128 + 8) * 2^-24 = 8e-6, weight |x| * 2^-24 + 2 ulp, times ten).  But 1e-4 of the total is about the mass of
 ONE entry at a top_p = 0.9 cut of a 9488-word row of randn * 3 logits (the entry at the cut weighs 2e-4 of the total), so under
-that margin nearly every such row is near and the cap below cannot hold for any kernel.  The kernel (csrc/rfn_misc.hip)
+that margin nearly every such row is near and the cap below cannot hold for any kernel.  The kernel (csrc/rfn_pick.hip)
 therefore accumulates differently, and the margin is re-derived for it: each weight is exp((x - max) * inv_temp) in fp64,
 rounded DOWN to a multiple of 2^-47 of the largest weight, and all sums are exact 64-bit integer sums.  Against exact arithmetic:
   - the rounding down: less than 2^-47 of the largest weight per entry, so V1 * 2^-47 <= 2.4e-10 of c_n for V1 <= 32768 (a

@@ -1,5 +1,6 @@
-"""The streaming kernels between the GEMMs (csrc/rfn_cell.hip, csrc/rfn_misc.hip, rfn_gather_rows), swept over the
-shapes and alignments at which each of them changes its code path, through the C ABI, against plain restatements.
+"""The streaming kernels between the GEMMs (csrc/rfn_cell.hip, csrc/rfn_glue.hip, rfn_logsoftmax.hip, rfn_criteria.hip,
+rfn_adam.hip, rfn_pick.hip, rfn_gather_rows), swept over the shapes and alignments at which each of them changes its code
+path, through the C ABI, against plain restatements.
 
 Every output buffer is pre-filled with NaN (integers: a sentinel), leading dimensions are wider than the rows, and the
 padding as well as the elements past the end are checked unchanged.

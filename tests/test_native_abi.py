@@ -31,6 +31,17 @@ def test_library_exports_every_declared_symbol():
     assert N.lib.rfn_abi_version() == N.ABI_VERSION
 
 
+def test_makefile_lists_every_translation_unit():
+    """SRCS of csrc/Makefile -- the one list every build takes its sources from -- is exactly the csrc/*.hip files."""
+    csrc = os.path.join(ROOT, 'recurrent_fusion_network_amd', 'csrc')
+    m = re.search(r'^SRCS\s*=\s*(.*)$', open(os.path.join(csrc, 'Makefile')).read(), flags=re.M)
+    assert m, 'csrc/Makefile has no SRCS line'
+    listed = m.group(1).split()
+    assert len(listed) == len(set(listed)), sorted(listed)
+    on_disk = set(f for f in os.listdir(csrc) if f.endswith('.hip'))
+    assert set(listed) == on_disk, 'not in SRCS: %s; no such file: %s' % (sorted(on_disk - set(listed)), sorted(set(listed) - on_disk))
+
+
 def test_struct_layouts_match_the_header():
     N = native()
     assert C.sizeof(N.GemmSeg) == 56

@@ -1,5 +1,5 @@
 // Access-pattern variants of the clamp + Adam stream (4 arrays in, 3 out, 28 B per parameter) on one 390 M-parameter bucket:
-// which of them moves the bytes fastest on MI355X.  Same element arithmetic in every variant (csrc/rfn_misc.hip adam_elem).
+// which of them moves the bytes fastest on MI355X.  Same element arithmetic in every variant (csrc/rfn_adam.hip adam_elem).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/adam_variants_probe.hip -o /tmp/adam_variants && /tmp/adam_variants
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -1,5 +1,5 @@
 """Times rfn_adam_step on a C3-sized flat bucket (350 M parameters = 1.4 GB per stream, 7 streams) and prints the
-achieved HBM rate (28 B per parameter).  Diagnostic only."""
+achieved HBM rate (28 B per parameter): the one-bucket call of adam_multi_k (csrc/rfn_adam.hip).  Diagnostic only."""
 import os
 import sys
 

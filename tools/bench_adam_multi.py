@@ -1,5 +1,5 @@
 """Times rfn_adam_step_multi on the C3 bucket mix (decoder 54 MB, core 262 MB, four encoders a 277 MB + 34 MB: 1.56 GB per
-stream, 7 streams) and prints the achieved HBM rate.  Diagnostic only (csrc/rfn_misc.hip ADAM_CONTIG / ADAM_NT A/B)."""
+stream, 7 streams) and prints the achieved HBM rate.  Diagnostic only (csrc/rfn_adam.hip ADAM_CONTIG / ADAM_NT A/B)."""
 import ctypes as C
 import os
 import sys

@@ -7,8 +7,12 @@ O=/tmp/rfn_variant_$TAG
 mkdir -p $O
 cd $R/recurrent_fusion_network_amd/csrc
 RT=$(python3 -c "import os, torch; print(os.path.join(os.path.dirname(torch.__file__), 'lib'))")
+SRCS=$(make -s --no-print-directory print-srcs) || exit 1     # the translation units are the Makefile's, listed once
+[ -n "$SRCS" ] || exit 1
+rm -f $O/*.o
 pids=()
-for f in rfn_gemm rfn_gemm_x3 rfn_cellgemm rfn_chain rfn_attn rfn_deccell rfn_cell rfn_misc rfn_beam rfn_path_common rfn_path_prefix rfn_path_decoder rfn_path_decode; do
+for s in $SRCS; do
+  f=${s%.hip}
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-value -Wno-unused-result $FLAGS -c $f.hip -o $O/$f.o &
   pids+=($!)
 done
