@@ -249,7 +249,9 @@ int rfn_gemm_f32_lstm(int M, int R, int ngroups, const rfn_gemm_problem* problem
 size_t rfn_x3_image_bytes(int rows, int K);
 /* Image of Y[ngroups * rows][K] whose row block g is the f32 matrix srcs_host[g] (device pointers in a host array;
  * k_fast = 1: element (row, k) at src[row * ld + k], k_fast = 0: at src[k * ld + row]).  rows % 32 == 0 unless
- * ngroups == 1; ngroups <= 64. */
+ * ngroups == 1 (RFN_ERR_SHAPE); 1 <= ngroups <= 64, rows, K >= 1, no NULL (RFN_ERR_ARG).  Any ld and any 4-byte aligned
+ * source: 16-byte loads are used where a k_fast source allows them (ld % 4 == 0, 16-byte aligned base), and every storage of
+ * the same values gives the same image bytes. */
 int rfn_x3_split(const float* const* srcs_host, int ngroups, int64_t ld, int rows, int K, int k_fast, void* image,
                  void* stream);
 /* C (+)= A . B^T from two images (A: M rows, B: N rows, both with reduction length K): the six plane products
@@ -257,7 +259,24 @@ int rfn_x3_split(const float* const* srcs_host, int ngroups, int64_t ld, int row
  * The output is cut into groups of gm rows x gn columns, group (i, j) written to C_host[i * ceil(N/gn) + j] with leading
  * dimension ldc (+ bias_host[..][column inside the group] when bias_host and the entry are non-NULL); gm and gn must be
  * multiples of 256 unless they cover the whole dimension; at most 64 groups.  splitk > 1 cuts K over blocks; the partial
- * tiles (part: rfn_x3_part_floats floats) are summed in slice order by a second kernel (deterministic; N % 4 == 0). */
+ * tiles (part: rfn_x3_part_floats floats) are summed in slice order by a second kernel (deterministic; N % 4 == 0).
+ *
+ * Stores.  A wave tile (64 x 128 outputs; 128 x 64 for rfn_x3_gemm_ks) that lies wholly inside M x N is stored 16 bytes per
+ * lane when accumulate == 0, the address of its first element is a multiple of 16 and ldc % 4 == 0 -- for every wave tile
+ * of a launch: every C_host[g] 16-byte aligned and ldc % 4 == 0 (N % 4 == 0 follows for packed groups).  Any other wave
+ * tile (ragged, accumulate, an odd ldc, a base one float off) is stored one float at a time.  Both ways store the same
+ * bits, acc + bias (+ previous C, in that order), and neither touches the columns between gn and ldc.
+ *
+ * Split.  With nkc = ceil(K / 32) pieces and per = ceil(nkc / splitk), slice s holds the pieces [s * per, min((s + 1) * per,
+ * nkc)); 1 <= splitk <= nkc (RFN_ERR_SHAPE beyond), so trailing slices may be EMPTY (nkc = 10, splitk = 7: per = 2, slices 5
+ * and 6) and then contribute zeros.  Slice s writes all of part[s][M][N]; the result is ((p_0 + p_1) + ... + p_(splitk-1)) + bias
+ * + previous C in f32, p_s bit-identical to the unsplit product over the slice's k range.  part is read with 16-byte loads:
+ * N % 4 == 0 and gn % 4 == 0 (RFN_ERR_ARG otherwise, as for part == NULL), and the caller keeps part 16-byte aligned (not
+ * checked).
+ *
+ * Limits.  Offsets inside a block tile are 32-bit: 256 * ldc * 4 < 2^32 (ldc < 2^22; with splitk > 1: 256 * N * 4), and for
+ * rfn_x3_gemm_ks 96 * Mp * 2 < 2^32 per image; RFN_ERR_SHAPE otherwise.  M, N, K >= 1 and non-NULL images and C_host, else
+ * RFN_ERR_ARG.  A refused call launches nothing and writes nothing. */
 int rfn_x3_gemm(int M, int N, int K, const void* imageA, const void* imageB, int gm, int gn, float* const* C_host,
                 const float* const* bias_host, int64_t ldc, int accumulate, int splitk, float* part, void* stream);
 /* K-SLOW images: a logical operand stored reduction-index-major in memory, Y[K][cols] (the weight gradient's two operands:

@@ -27,7 +27,7 @@ Tolerances -- no invented numbers
   per case and committed in gemm_cases.YARD; the kernel gets 4 x that for another association (32x32x2 MFMA pairs, split
   ranges).  A dropped or doubled term is ~1 in size, four orders of magnitude above any yardstick (checked on the CPU).
 
-Out of scope: rfn_gemm_x3.hip and rfn_cell_gemm (tests/test_x3_gpu.py, tests/test_cellgemm_gpu.py); operands of >= 4 GiB
+Out of scope: rfn_gemm_x3.hip (its own sweep: tests/test_x3_edges_gpu.py) and rfn_cell_gemm (tests/test_cellgemm_gpu.py); operands of >= 4 GiB
 (the span32 fallback); any timing.
 """
 import ctypes as C
