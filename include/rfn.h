@@ -439,7 +439,43 @@ int rfn_attn_small_bwd(int ngroups, const float* const* proj, int64_t proj_sb, i
  * rfn_dec_attn_bwd: the attention backward of one step from that step's gate gradients: d alpha_l = <dgates, U_l>, softmax
  *   and tanh backward; dproj (accumulated when `accumulate`), dhproj, dw_part as rfn_attn_small_bwd.  GD = 4R or 5R.
  * rfn_dec_du: after the loop, dU[b, l, :] = sum_s alpha[s, b, l] * dgates[s, b, :] (alpha (S, B, L), dgates (S, B, GD)
- *   contiguous; dU strides as U). */
+ *   contiguous; dU strides as U).
+ *
+ * Operands.  proj (b', l, :) at proj + b' * psb + l * psl and U at U + b' * usb + l * usl with b' = b / row_div: both need
+ *   ceil(B / row_div) rows (rfn_dec_attn_bwd has no row_div: B rows).  gates, c_prev, c_next, h_next, dgates have a row stride
+ *   (ldg, ldcp, ldcn, ldh); dproj has strides of its own (dpsb, dpsl), dU those handed to rfn_dec_du.  Packed, without a
+ *   stride: hproj (B, A), w_out (A), bz (GD), alpha (B, L), dhproj and dw_part (B, A), and rfn_dec_du's alpha (S, B, L) and
+ *   dgates (S, B, GD).  c_next may be c_prev (same pointer, same stride: a unit reads its c_prev before it writes; the
+ *   free-running decoders call the cell in place), and h_next may be any buffer the call does not read; results are those of the
+ *   out-of-place call.  With U = 0 and b_z = 0 the gate activations are rfn_lstm_fwd's bits on the same gates_in; c and h agree
+ *   with it to rounding (f * c_prev + i * g is left to the compiler's contraction in both).  The dropout counter of unit j of
+ *   row b is b * R + j (rfn_dropout_mask over B * R values) whatever ldh is.
+ * Limits (RFN_ERR_SHAPE, nothing launched, no output touched); Xp = X rounded up to 4:
+ *   every extent (B, L, A, R, GD, S) >= 1; row_div >= 1; 0 <= drop_p < 1;
+ *   rfn_dec_cell_fwd:   L <= 1024; off its fast kernel 2 * Ap + L floats <= 64 KiB
+ *   rfn_dec_attn_bwd:   L <= 1024 and 2 * Ap + 2 * Lp + 32 floats <= 64 KiB (whichever kernel would serve the call)
+ *   rfn_dec_du:         on its 16-byte kernel (below) the S * L alpha values of a row are staged in LDS: S * L floats <= 64 KiB,
+ *                       else refused; the scalar kernel reads alpha from memory and takes any S * L.
+ *   A NULL pointer is RFN_ERR_ARG; b_out alone may be NULL (no bias: the results of b_out = {0}).
+ * Alignment: any float-aligned pointer and any stride is accepted.
+ *   rfn_dec_cell_fwd takes its fast kernel when A % 4 == 0, A <= 512, L <= 8, R % 256 == 0, psb and psl are multiples of 4 and
+ *   proj, hproj, w_out are 16-byte aligned; else the general kernel, which reads proj in 16-byte pieces when A % 4 == 0, psb and
+ *   psl are multiples of 4 and proj is 16-byte aligned.  A row's results (gates, c, h, alpha) are the same bits on the fast
+ *   kernel, whatever the share of a row it gives a block, and on the general kernel with 16-byte proj reads, at any B and any
+ *   block size; the general kernel's scalar proj reads sum a score in another order (same results to rounding).
+ *   rfn_dec_attn_bwd takes its fast kernel when A % 4 == 0, A <= 512, L <= 8, GD % 4 == 0, every stride (psb, psl, usb, usl, ldg,
+ *   dpsb, dpsl) is a multiple of 4 and proj, hproj, w_out, U, dgates, dproj, dhproj, dw_part are 16-byte aligned.  Otherwise
+ *   the general kernel decides twice: 16-byte accesses on the (L, A) side when A % 4 == 0, psb, psl, dpsb, dpsl are multiples of
+ *   4 and proj, dproj, dhproj, dw_part are aligned; on the GD side when GD % 4 == 0, usb, usl, ldg are multiples of 4 and U,
+ *   dgates are aligned.  The five kernels are the same formulas and agree to rounding; bit-equality between two of them is
+ *   not promised (contraction is left to the compiler: the fast kernel and the general one with both 16-byte forms fuse
+ *   1 - t * t and the d pre-activation products into fmas differently; the fast kernel adds the sums of rows 0..3 and 4..7
+ *   separately; the scalar forms sum a dot in another order).  A row's results do not depend on B or on the other rows.
+ *   accumulate != 0: dproj = dproj_before + the gradient with one rounding (the gradient's last product is fused into the
+ *   sum): within u * (|accumulated| + |overwritten|), u = 2^-24, of dproj_before + the overwrite result, not its bits;
+ *   dhproj, dw_part do not depend on accumulate.
+ *   rfn_dec_du takes its 16-byte kernel when GD % 4 == 0, usb and usl are multiples of 4 and dgates, dU are 16-byte aligned, else
+ *   the scalar one; both add the steps in order from 0 and give the same bits.  Only dU[b, l, 0:GD], l < L, is written. */
 int rfn_dec_cell_fwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
                      const float* b_out, const float* U, int64_t usb, int64_t usl, const float* bz, float* gates,
                      int64_t ldg, const float* c_prev, int64_t ldcp, float* c_next, int64_t ldcn, float* h_next,

@@ -114,7 +114,9 @@ __global__ __launch_bounds__(256) void dec_cell_fwd_k(const DecCellArgs a) {
     float pre[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) pre[g] = (acc[g] + bzv[g]) + gin[g];
-    // ---- LSTM update (rfn_cell.hip lstm_fwd_k, same formulas; :83-101) ----------------------------------------------------
+    // ---- LSTM update (misc/LSTMSoftAttentionCore.py:83-101; the formulas of lstm_fwd_k, rfn_cell.hip): the gate activations
+    // are lstm_fwd_k's bits, c and h agree with it to rounding only -- its `fg * c_prev[..] + ig * gg` and this
+    // `fg * cprev + ig * gg` are contracted around either product as the compiler sees fit
     const float ig = rfn_sigmoid(pre[0]), fg = rfn_sigmoid(pre[1]), og = rfn_sigmoid(pre[2]);
     float gg;
     if constexpr (NG == 5) {   // maxout: max of the two candidate chunks, no tanh; chunk 4 keeps the selector
@@ -236,7 +238,9 @@ __global__ __launch_bounds__(256) void dec_cell_fwd_fast_k(const DecCellArgs a) 
 #pragma unroll
         for (int g = 0; g < NG; ++g) pg[g] = pre[g];
     }
-    // ---- LSTM update (rfn_cell.hip lstm_fwd_k, same formulas; :83-101) ----------------------------------------------------
+    // ---- LSTM update (misc/LSTMSoftAttentionCore.py:83-101; the formulas of lstm_fwd_k, rfn_cell.hip): the gate activations
+    // are lstm_fwd_k's bits, c and h agree with it to rounding only -- its `fg * c_prev[..] + ig * gg` and this
+    // `fg * cprev + ig * gg` are contracted around either product as the compiler sees fit
     const float ig = rfn_sigmoid(pg[0]), fg = rfn_sigmoid(pg[1]), og = rfn_sigmoid(pg[2]);
     float gg;
     if constexpr (NG == 5) {

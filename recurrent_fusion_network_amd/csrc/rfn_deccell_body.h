@@ -25,6 +25,8 @@ struct DecAttnBwdArgs {
 // the gate gradients of the d alpha sums, the thread's four projection rows and their running gradients, hproj, w_out --
 // requested before the first dependent instruction; all 256 threads in the tanh-backward (thread = 4 hidden units x 4 of the 8
 // rows; the two row halves' column sums meet in LDS and are added lower half first).
+// Same formulas as dec_attn_bwd_k<true, true> (rfn_deccell.hip), not the same bits: contraction is left on, and the compiler fuses
+// 1 - t * t and the d pre-activation products into the sums around them differently in the two kernels.
 __device__ __forceinline__ void dec_attn_bwd_fast_body(const DecAttnBwdArgs& a, const int b) {
     __shared__ float red[ATT_WAVES * DEC_LREG];
     __shared__ float da_s[DEC_LREG], al_s[DEC_LREG];

@@ -40,6 +40,15 @@ def test_makefile_lists_every_translation_unit():
     assert len(listed) == len(set(listed)), sorted(listed)
     on_disk = set(f for f in os.listdir(csrc) if f.endswith('.hip'))
     assert set(listed) == on_disk, 'not in SRCS: %s; no such file: %s' % (sorted(on_disk - set(listed)), sorted(set(listed) - on_disk))
+    # ... and HDRS, which every object depends on, is exactly the csrc/*.h files plus the public header: a header left out is a
+    # header whose edits do not rebuild the objects that include it
+    m = re.search(r'^HDRS\s*=\s*(.*)$', open(os.path.join(csrc, 'Makefile')).read(), flags=re.M)
+    assert m, 'csrc/Makefile has no HDRS line'
+    hdrs = m.group(1).split()
+    assert len(hdrs) == len(set(hdrs)), sorted(hdrs)
+    h_on_disk = set(f for f in os.listdir(csrc) if f.endswith('.h')) | {'../../include/rfn.h'}
+    assert set(hdrs) == h_on_disk, 'not in HDRS: %s; no such file: %s' % (sorted(h_on_disk - set(hdrs)), sorted(set(hdrs) - h_on_disk))
+    assert re.search(r'^%\.o:\s*%\.hip\s+\$\(HDRS\)\s*$', open(os.path.join(csrc, 'Makefile')).read(), flags=re.M)
 
 
 def test_struct_layouts_match_the_header():
