@@ -847,6 +847,49 @@ typedef struct rfn_decode_sampling {
     int32_t rows_per_image;   /* n >= 1 draws per image (0 reads as 1) */
     int32_t pad_;
 } rfn_decode_sampling;
+/* ---- diverse beam search: beam groups with a Hamming penalty (off by default; the reference has none) -----------------------
+ * The W beams of an image are G groups of Wg = W / G beams, group g owning beams g*Wg .. g*Wg+Wg-1.  One step t (1 .. S) of
+ * one image runs the groups in order g = 0 .. G-1, all groups at the same t (no stagger in time); each group follows the rules
+ * of rfn_beam_step restricted to its own beams:
+ *   - live rows: at t == 1 the group's first row only, else its Wg rows; a row whose last token is 0 gives no candidates;
+ *   - count[v], v != 0: the number of beams that groups 0 .. g-1 newly selected at this step with token v.  Token 0 (END) is
+ *     never counted and never penalised (the exemption n-gram blocking makes: diversity never decides whether a caption may
+ *     end); a beam that kept its previous state (vix >= the number of new beams) is not counted;
+ *   - candidates in (column c of the row's top list outer, beam q inner) order over the live rows, with today's values
+ *     local = ys[q][c] and p = fp32(beam_sum[q] + local);
+ *   - ranking key: p where count[v] == 0, else fp32(beam_sum[q] + fp32(local - fp32(lambda * count[v]))) -- three operations,
+ *     each rounded to fp32 on its own, never fused;
+ *   - stable descending order by key; the first min(Wg, candidates) become the group's beams 0 .. Wg-1;
+ *   - beam_lp, beam_sum, done_lp and done_p get the unaugmented local / p: lambda decides which hypotheses survive, never a
+ *     reported log-probability;
+ *   - a selected candidate that emits 0, or any selected candidate at t == S, is appended to the image's done beams in
+ *     construction order (group, then rank), done_group[k, slot] = g beside it; max_done = W * S bounds them as before;
+ *   - a group without a candidate leaves its rows inert (order = identity, next_ids = 0); active[k] becomes 0 only when no
+ *     group of the image has one.
+ * The constraints act on the top lists before the step sees them, the length penalty ranks the done beams afterwards: both
+ * unchanged.  Keys that are NaN (a NaN log-prob) are not ordered; the step then stays in bounds but selects no defined set.
+ *
+ * Why the W best entries of a row suffice.  Define the search on full rows: every row's V1 entries sorted descending (value,
+ * then token id), candidates taken in (column, beam) order.  At group g at most g * Wg <= W - Wg distinct tokens are
+ * penalised.  A candidate beyond column W of its row therefore has at least Wg unpenalised entries of the same row in earlier
+ * columns; their keys are not smaller (they are p values of larger or equal local on the same beam_sum, the fp32 add is
+ * monotone, and a penalty only lowers a key), and on a tie they come earlier in construction order.  So that candidate is
+ * never among the first Wg, and a stable sort keeps the relative order of the ones that remain.  With V1 < W the list is the
+ * whole row.
+ *
+ * rfn_beam_step_div: rfn_beam_step_topk's arguments plus G, lambda and done_group (NB, max_done) int32.  One block per image,
+ * the groups in a serial loop, every candidate computing its own rank (no single-thread sort).  G == 1 forwards to
+ * rfn_beam_step_topk (lambda is ignored, done_group may be NULL).  RFN_ERR_SHAPE: G < 1, W % G != 0, !(lambda >= 0). */
+int rfn_beam_step_div(const float* topv, const int32_t* topi, int V1, int W, int G, float lambda, int S, int t, int NB,
+                      int max_done, int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* next_ids,
+                      int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* done_group, int32_t* active,
+                      void* stream);
+/* What rfn_beam_loop_ex2 takes besides the constraints. */
+typedef struct rfn_beam_diversity {
+    int32_t groups;           /* G >= 1, W % G == 0; 1: the plain search */
+    float lambda;             /* >= 0 */
+    int32_t* done_group;      /* (NB, max_done), device; may be NULL when groups == 1 */
+} rfn_beam_diversity;
 /* dst[r,:] = src[order[r],:]  (src != dst) */
 int rfn_gather_rows(const float* src, float* dst, const int32_t* order, int rows, int R, void* stream);
 
@@ -1016,6 +1059,14 @@ int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const
                      float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
                      float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
                      const rfn_decode_constraints* cons, void* stream);
+/* rfn_beam_loop_ex as a diverse beam search (above): rfn_beam_step_div in place of rfn_beam_step_topk, on the same top-W lists;
+ * div->done_group (NB, max_done) receives the group of every done beam.  div == NULL or div->groups == 1: the calls and the
+ * bits of rfn_beam_loop_ex, which forwards here.  RFN_ERR_SHAPE as rfn_beam_step_div; RFN_ERR_ARG: groups > 1 without done_group. */
+int rfn_beam_loop_ex2(const rfn_dims* d, int NB, int W, int S, const float* const* params, const float* comb,
+                      const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp, int64_t* beam_seq,
+                      float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
+                      float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
+                      const rfn_decode_constraints* cons, const rfn_beam_diversity* div, void* stream);
 
 /* ---- self-critical reward: CIDEr-D of token-id captions (get_rewards.py:39-112, cider/pyciderevalcap/ciderD) ---------
  * CiderD(n=4, sigma) as compute_reward calls it (csrc/rfn_reward.hip).  A caption is the ids of its row up to and including

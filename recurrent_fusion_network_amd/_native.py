@@ -91,6 +91,11 @@ class DecodeSampling(C.Structure):
     _fields_ = [('top_k', C.c_int32), ('top_p', C.c_float), ('rows_per_image', C.c_int32), ('pad_', C.c_int32)]
 
 
+class BeamDiversity(C.Structure):
+    """rfn_beam_diversity (rfn.h)."""
+    _fields_ = [('groups', C.c_int32), ('lambda_', C.c_float), ('done_group', C.c_void_p)]
+
+
 DECODE_MAX_IDS = 64
 
 
@@ -105,6 +110,7 @@ def _load():
     lib.rfn_error_string.restype = C.c_char_p
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
     DP, CP, SP = C.POINTER(Dims), C.POINTER(DecodeConstraints), C.POINTER(DecodeSampling)
+    BDP = C.POINTER(BeamDiversity)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -177,6 +183,7 @@ def _load():
         'rfn_beam_step': (C.c_int, [P, L, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
         'rfn_gather_rows': (C.c_int, [P, P, P, I, I, P]),
         'rfn_beam_step_topk': (C.c_int, [P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
+        'rfn_beam_step_div': (C.c_int, [P, P, I, I, I, F, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
         'rfn_log_softmax_topk': (C.c_int, [P, L, I, I, I, P, P, P]),
         'rfn_log_softmax_topk_masked': (C.c_int, [P, L, I, I, I, P, L, P, P, P, P]),
         'rfn_decode_blocklist': (C.c_int, [P, L, L, P, I, I, I, I, P, I, P, I, I, P, P, P]),
@@ -197,6 +204,7 @@ def _load():
         'rfn_decoder_loop_ex': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, P]),
         'rfn_decoder_loop_ex2': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, SP, P]),
         'rfn_beam_loop_ex': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, P]),
+        'rfn_beam_loop_ex2': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, P]),
         'rfn_decoder_fwd_sampled': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, P]),
         'rfn_beam_loop': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, P]),
         'rfn_decoder_step_ws_bytes': (SZ, [DP, I]),

@@ -11,12 +11,64 @@
 //   * done beams appended in construction order when END is emitted or t == seq_length (:508-514);
 //   * an image with no candidate left stops (:480-481).
 // Nothing is read back per step; the host sorts the (few) done beams once at the end.
+// The diverse search (beam groups with a Hamming penalty, which the reference does not have) is the second kernel below.
 #include "rfn_rows.h"
 
 #define BEAM_MAX_W 32     /* beams per image; the full-row form (rfn_beam_step: phase 1 below) serves up to BEAM_WAVES of them */
 #define BEAM_MAX_S 64     /* decode steps a block keeps the beams' histories for (seq_length) */
 #define BEAM_THREADS 1024
 #define BEAM_WAVES 16
+
+// Phase 2b of a step (all threads of the block): the forked columns and the done beams of the beams b0 .. b0+nb-1 of image k
+// (the whole image, or one group of a diverse search).  sel_ci[vix] is the candidate that becomes beam b0 + vix (vix < nnew),
+// cand_q its source beam within the image, slot_s[vix] its done slot or -1; prev_* is the snapshot of the image's beams before
+// the step.  Needs nthr >= nb.
+__device__ __forceinline__ void beam_fork_write(int k, int tid, int nthr, int W, int b0, int nb, int nnew, int S, int t, int NB,
+                                                int MAXD, int64_t* __restrict__ bs, float* __restrict__ bl,
+                                                float* __restrict__ bsum, int32_t* __restrict__ order, int64_t* __restrict__ nxt,
+                                                int64_t* __restrict__ done_seq, float* __restrict__ done_lp,
+                                                const int (*prev_seq)[BEAM_MAX_W], const float (*prev_lp)[BEAM_MAX_W],
+                                                const float* cand_p, const float* cand_r, const int* cand_c, const int* cand_q,
+                                                const int* sel_ci, const int* slot_s) {
+    for (int i = tid; i < nnew * S; i += nthr) {
+        const int vix = i / S, s = i - vix * S;
+        const int ci = sel_ci[vix], qq = cand_q[ci];
+        int64_t tok;
+        float lp;
+        const long at = ((long)s * NB + k) * W + b0 + vix;
+        if (s < t - 1) {
+            tok = prev_seq[s][qq];
+            lp = prev_lp[s][qq];
+            bs[at] = tok;
+            bl[at] = lp;
+        } else if (s == t - 1) {
+            tok = cand_c[ci];
+            lp = cand_r[ci];
+            bs[at] = tok;
+            bl[at] = lp;
+        } else {  // columns this search has not reached yet (still the initial zeros)
+            tok = bs[at];
+            lp = bl[at];
+        }
+        const int slot = slot_s[vix];
+        if (slot >= 0) {
+            done_seq[((long)k * MAXD + slot) * S + s] = tok;
+            done_lp[((long)k * MAXD + slot) * S + s] = lp;
+        }
+    }
+    if (tid < nb) {
+        const int vix = tid, row = k * W + b0 + vix;
+        if (vix < nnew) {
+            const int ci = sel_ci[vix];
+            order[row] = k * W + cand_q[ci];
+            nxt[row] = cand_c[ci];
+            bsum[row] = cand_p[ci];                  // every read of these beams' bsum happened before the caller's barrier
+        } else {  // keeps its previous state and tokens (new_state = clone(state), :485)
+            order[row] = row;
+            nxt[row] = bs[((long)(t - 1) * NB + k) * W + b0 + vix];
+        }
+    }
+}
 
 // One block per image.  Phase 1: top `cols` columns of every live beam row -- each row is cut over 16 / rows waves,
 // every lane keeps a sorted top-LW list of its strided share in registers (one pass over the row), the wave merges
@@ -155,45 +207,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
         }
         return;
     }
-    // ---- phase 2b (all threads): forked columns and done beams ---------------------------------------------------
-    for (int i = tid; i < nnew * S; i += (int)blockDim.x) {
-        const int vix = i / S, s = i - vix * S;
-        const int ci = sel_ci[vix], qq = cand_q[ci];
-        int64_t tok;
-        float lp;
-        const long at = ((long)s * NB + k) * W + vix;
-        if (s < t - 1) {
-            tok = prev_seq[s][qq];
-            lp = prev_lp[s][qq];
-            bs[at] = tok;
-            bl[at] = lp;
-        } else if (s == t - 1) {
-            tok = cand_c[ci];
-            lp = cand_r[ci];
-            bs[at] = tok;
-            bl[at] = lp;
-        } else {  // columns this search has not reached yet (still the initial zeros)
-            tok = bs[at];
-            lp = bl[at];
-        }
-        const int slot = slot_s[vix];
-        if (slot >= 0) {
-            done_seq[((long)k * MAXD + slot) * S + s] = tok;
-            done_lp[((long)k * MAXD + slot) * S + s] = lp;
-        }
-    }
-    if (tid < W) {
-        const int vix = tid;
-        if (vix < nnew) {
-            const int ci = sel_ci[vix];
-            order[k * W + vix] = k * W + cand_q[ci];
-            nxt[k * W + vix] = cand_c[ci];
-            bsum[k * W + vix] = cand_p[ci];          // every read of bsum happened before the barrier above
-        } else {  // keeps its previous state and tokens (new_state = clone(state), :485)
-            order[k * W + vix] = k * W + vix;
-            nxt[k * W + vix] = bs[((long)(t - 1) * NB + k) * W + vix];
-        }
-    }
+    beam_fork_write(k, tid, (int)blockDim.x, W, 0, W, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp, prev_seq,
+                    prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
 }
 
 static int beam_step_launch(const float* logp, int64_t ldl, const float* topv, const int32_t* topi, int V1, int W, int S, int t,
@@ -236,6 +251,153 @@ extern "C" int rfn_beam_step_topk(const float* topv, const int32_t* topi, int V1
     if (!topv || !topi) return RFN_ERR_ARG;
     return beam_step_launch(nullptr, 0, topv, topi, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids,
                             done_seq, done_lp, done_p, done_n, active, stream);
+}
+
+// =============================================================================================
+// diverse beam search: G groups of Wg = W / G beams with a Hamming penalty (rfn.h "diverse beam search")
+// =============================================================================================
+#define BEAM_DIV_THREADS 256
+#define BEAM_DIV_MAXC (BEAM_MAX_W * BEAM_MAX_W / 2)   /* candidates of one group: cols * Wg <= W * W / G, G >= 2 */
+
+// The ranking key of a penalised candidate: three fp32 operations, each rounded on its own (no FMA).
+__device__ __forceinline__ float beam_div_key(float sum, float local, float lambda, int count) {
+#pragma clang fp contract(off)
+    const float pen = lambda * (float)count;
+    const float aug = local - pen;
+    return sum + aug;
+}
+
+// One block per image, the groups one after the other.  Per group: thread 0 lists the live rows; every candidate (column c
+// outer, live row inner) gets its unaugmented p and its key from the LDS list of the tokens the earlier groups chose at this
+// step; every candidate counts the candidates that precede it in the stable descending order of the keys (greater key, or
+// equal key and lower construction index) -- that count is its rank, and ranks < Wg are the group's new beams; thread 0
+// hands out the done slots in rank order and appends the chosen tokens to the list; all threads write the forks
+// (beam_fork_write, as beam_step_k).  A group reads and writes its own beams' columns and sums only.
+__global__ __launch_bounds__(BEAM_DIV_THREADS) void beam_step_div_k(
+    const float* __restrict__ topv, const int32_t* __restrict__ topi, int V1, int W, int G, float lambda, int S, int t, int NB,
+    int MAXD, int64_t* __restrict__ bs, float* __restrict__ bl, float* __restrict__ bsum, int32_t* __restrict__ order,
+    int64_t* __restrict__ nxt, int64_t* __restrict__ done_seq, float* __restrict__ done_lp, float* __restrict__ done_p,
+    int32_t* __restrict__ done_n, int32_t* __restrict__ done_group, int32_t* __restrict__ active) {
+    __shared__ float ys[BEAM_MAX_W][BEAM_MAX_W];
+    __shared__ int ix[BEAM_MAX_W][BEAM_MAX_W];
+    __shared__ int prev_seq[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ float prev_lp[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ float cand_key[BEAM_DIV_MAXC], cand_p[BEAM_DIV_MAXC], cand_r[BEAM_DIV_MAXC];
+    __shared__ int cand_c[BEAM_DIV_MAXC], cand_q[BEAM_DIV_MAXC];
+    __shared__ int sel_ci[BEAM_MAX_W], slot_s[BEAM_MAX_W], pen_tok[BEAM_MAX_W], liveq[BEAM_MAX_W];
+    __shared__ int nl_s, npen_s;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int cols = min(W, V1), Wg = W / G;
+    if (!active[k]) {  // this image's search has ended: keep its rows inert
+        if (tid < W) {
+            order[k * W + tid] = k * W + tid;
+            nxt[k * W + tid] = 0;
+        }
+        return;
+    }
+    for (int i = tid; i < W * cols; i += BEAM_DIV_THREADS) {
+        const int q = i / cols, c = i - q * cols;
+        ys[q][c] = topv[(long)(k * W + q) * W + c];
+        ix[q][c] = topi[(long)(k * W + q) * W + c];
+    }
+    for (int i = tid; i < (t - 1) * W; i += BEAM_DIV_THREADS) {  // the beams before this step (forks read the OLD columns)
+        const int s = i / W, w = i - s * W;
+        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
+        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
+    }
+    __syncthreads();
+    int npen = 0, n = 0, any = 0;                    // thread 0's: penalised tokens so far, done beams so far, a group had a candidate
+    if (tid == 0) n = done_n[k];
+    for (int g = 0; g < G; ++g) {
+        const int b0 = g * Wg;
+        if (tid == 0) {
+            int nl = 0;
+            for (int j = 0; j < (t == 1 ? 1 : Wg); ++j) {
+                if (t > 1 && prev_seq[t - 2][b0 + j] == 0) continue;
+                liveq[nl++] = b0 + j;
+            }
+            nl_s = nl;
+            npen_s = npen;
+            for (int v = 0; v < Wg; ++v) sel_ci[v] = 0;
+        }
+        __syncthreads();
+        const int nl = nl_s, nc = cols * nl, np = npen_s;
+        for (int i = tid; i < nc; i += BEAM_DIV_THREADS) {
+            const int c = i / nl, q = liveq[i - c * nl];
+            const float local = ys[q][c], sum = bsum[k * W + q];
+            const int v = ix[q][c];
+            const float p = sum + local;             // fp32 add, as the reference's tensor arithmetic
+            int count = 0;
+            if (v != 0)
+                for (int j = 0; j < np; ++j) count += pen_tok[j] == v;
+            cand_c[i] = v;
+            cand_q[i] = q;
+            cand_r[i] = local;
+            cand_p[i] = p;
+            cand_key[i] = count ? beam_div_key(sum, local, lambda, count) : p;
+        }
+        __syncthreads();
+        for (int i = tid; i < nc; i += BEAM_DIV_THREADS) {
+            const float ki = cand_key[i];
+            int rank = 0;
+            for (int j = 0; j < nc && rank < Wg; ++j) {
+                const float kj = cand_key[j];
+                rank += (kj > ki) || (kj == ki && j < i);
+            }
+            if (rank < Wg) sel_ci[rank] = i;
+        }
+        __syncthreads();
+        const int nnew = min(Wg, nc);
+        if (tid == 0) {
+            for (int vix = 0; vix < Wg; ++vix) {
+                slot_s[vix] = -1;
+                if (vix >= nnew) continue;
+                const int ci = sel_ci[vix], tok = cand_c[ci];
+                if ((tok == 0 || t == S) && n < MAXD) {  // appended in construction order: group, then vix
+                    slot_s[vix] = n;
+                    done_p[(long)k * MAXD + n] = cand_p[ci];
+                    done_group[(long)k * MAXD + n] = g;
+                    ++n;
+                }
+                if (tok != 0) pen_tok[npen++] = tok;     // END is never counted
+            }
+            any |= nc > 0;
+        }
+        __syncthreads();
+        if (nc == 0) {  // no candidate left: the group's rows stay inert
+            if (tid < Wg) {
+                order[k * W + b0 + tid] = k * W + b0 + tid;
+                nxt[k * W + b0 + tid] = 0;
+            }
+        } else {
+            beam_fork_write(k, tid, BEAM_DIV_THREADS, W, b0, Wg, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp,
+                            prev_seq, prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
+        }
+        __syncthreads();                             // the next group reuses the candidate arrays
+    }
+    if (tid == 0) {
+        done_n[k] = n;
+        if (!any) active[k] = 0;
+    }
+}
+
+extern "C" int rfn_beam_step_div(const float* topv, const int32_t* topi, int V1, int W, int G, float lambda, int S, int t, int NB,
+                                 int max_done, int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order,
+                                 int64_t* next_ids, int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n,
+                                 int32_t* done_group, int32_t* active, void* stream) {
+    if (G < 1 || W < 1 || W % G || !(lambda >= 0.f)) return RFN_ERR_SHAPE;
+    if (G == 1)
+        return rfn_beam_step_topk(topv, topi, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids, done_seq,
+                                  done_lp, done_p, done_n, active, stream);
+    if (W > BEAM_MAX_W || S < 1 || S > BEAM_MAX_S || t < 1 || t > S || NB < 1 || V1 < 1 || max_done < 1) return RFN_ERR_SHAPE;
+    if (!topv || !topi || !beam_seq || !beam_lp || !beam_sum || !order || !next_ids || !done_seq || !done_lp || !done_p ||
+        !done_n || !done_group || !active)
+        return RFN_ERR_ARG;
+    hipLaunchKernelGGL(beam_step_div_k, dim3(NB), dim3(BEAM_DIV_THREADS), 0, (hipStream_t)stream, topv, topi, V1, W, G, lambda, S,
+                       t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids, done_seq, done_lp, done_p, done_n,
+                       done_group, active);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
 }
 
 // dst[r, :] = src[order[r], :]  -- recurrent-state re-gather of the forked beams (:499-501)

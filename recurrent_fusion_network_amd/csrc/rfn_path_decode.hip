@@ -199,11 +199,13 @@ extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const fl
 // sample_beam's search (misc/RecurrentFusionModel.py:451-531) for all images at once, queued by one call: per step the
 // device-side bookkeeping (rfn_beam_step), the re-gather of the recurrent state rows and one decoder step on the
 // NB * W beam rows.  h / c are ping-ponged with h_alt / c_alt; on return the live state is in h / c again.
-extern "C" int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
-                                const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
-                                int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
-                                int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
-                                void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons, void* st) {
+// div: diverse beam search (rfn.h): the step is rfn_beam_step_div on the same top-W lists, everything else is unchanged.
+extern "C" int rfn_beam_loop_ex2(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+                                 const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
+                                 int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
+                                 int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
+                                 void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons,
+                                 const rfn_beam_diversity* div, void* st) {
     // `logp` holds, per beam row, its W best log-probs and their tokens (2 * W values): the search never looks at more
     // (:463-466), so the full (rows, V+1) log-prob matrix is neither written nor read back
     RFN_TRY(check_dims(d));
@@ -215,14 +217,21 @@ extern "C" int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const f
     if (W > 32) return RFN_ERR_SHAPE;
     RFN_TRY(check_constraints(cons, S));
     if (cons && !beam_seq) return RFN_ERR_ARG;
+    if (div && (div->groups < 1 || W % div->groups || !(div->lambda >= 0.f))) return RFN_ERR_SHAPE;
+    const bool diverse = div && div->groups > 1;     // one group: the plain search, same launches
+    if (diverse && !div->done_group) return RFN_ERR_ARG;
     float* topv = logp;
     int32_t* topi = (int32_t*)(logp + (size_t)rows * W);
     float *hc = h, *cc = c, *ha = h_alt, *ca = c_alt;
     if (hipMemsetAsync(ids, 0, (size_t)rows * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;
     for (int t = 0; t <= S; ++t) {
         if (t >= 1) {
-            RFN_TRY(rfn_beam_step_topk(topv, topi, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, ids, done_seq,
-                                       done_lp, done_p, done_n, active, st));
+            if (diverse)
+                RFN_TRY(rfn_beam_step_div(topv, topi, V1, W, div->groups, div->lambda, S, t, NB, max_done, beam_seq, beam_lp,
+                                          beam_sum, order, ids, done_seq, done_lp, done_p, done_n, div->done_group, active, st));
+            else
+                RFN_TRY(rfn_beam_step_topk(topv, topi, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, ids, done_seq,
+                                           done_lp, done_p, done_n, active, st));
             if (t == S) break;   // the reference still runs one more decoder step whose output is never used
             RFN_TRY(rfn_gather_rows(hc, ha, order, rows, R, st));
             RFN_TRY(rfn_gather_rows(cc, ca, order, rows, R, st));
@@ -240,6 +249,14 @@ extern "C" int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const f
         RFN_TRY(mem_batch({{h, hc, (long)rows * R}, {c, cc, (long)rows * R}}, st));
     }
     return RFN_OK;
+}
+extern "C" int rfn_beam_loop_ex(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+                                const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
+                                int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
+                                int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
+                                void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons, void* st) {
+    return rfn_beam_loop_ex2(d, NB, W, S, prm, comb, cproj, h, c, h_alt, c_alt, logp, beam_seq, beam_lp, beam_sum, order, ids, done_seq,
+                             done_lp, done_p, done_n, active, max_done, ws, ws_bytes, seed, cons, nullptr, st);
 }
 extern "C" int rfn_beam_loop(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
                              const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,

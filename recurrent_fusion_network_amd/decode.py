@@ -115,9 +115,10 @@ def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
 
 class BeamBuffers:
     """The state of a beam search over B images x W beams x S steps.  The rows' top-W lists are uninitialised storage, as
-    one float buffer (`top_flat`, rfn_beam_loop) or as values and indices (`top_lists`, a host-stepped search)."""
+    one float buffer (`top_flat`, rfn_beam_loop) or as values and indices (`top_lists`, a host-stepped search).  `done_group`
+    (the group of every done beam) exists only for a diverse search (groups > 1)."""
 
-    def __init__(self, B, W, S, dev):
+    def __init__(self, B, W, S, dev, groups=1):
         self.B, self.W, self.S, self.dev = B, W, S, dev
         self.rows, self.max_done = rows, max_done = B * W, W * S
         self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
@@ -130,6 +131,7 @@ class BeamBuffers:
         self.done_p = torch.zeros(B, max_done, device=dev)
         self.done_n = torch.zeros(B, dtype=torch.int32, device=dev)
         self.active = torch.ones(B, dtype=torch.int32, device=dev)
+        self.done_group = torch.zeros(B, max_done, dtype=torch.int32, device=dev) if groups > 1 else None
 
     def top_flat(self):
         return torch.empty(2 * self.rows * self.W, device=self.dev)
@@ -138,18 +140,20 @@ class BeamBuffers:
         return torch.empty(self.rows, self.W, device=self.dev), torch.empty(self.rows, self.W, dtype=torch.int32, device=self.dev)
 
 
-def run_beam_loop(stepper, bufs, cons):
-    """The whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows)."""
+def run_beam_loop(stepper, bufs, cons, div=None):
+    """The whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows).  cons: a parsed
+    _Constraints or None; div: a parsed _Diversity or None (bufs then holds done_group)."""
     b, logp = bufs, bufs.top_flat()
     h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
-    N.check(N.lib.rfn_beam_loop_ex(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
-                                   stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
-                                   c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(),
-                                   b.order.data_ptr(), b.ids.data_ptr(), b.done_seq.data_ptr(), b.done_lp.data_ptr(),
-                                   b.done_p.data_ptr(), b.done_n.data_ptr(), b.active.data_ptr(), b.max_done,
-                                   stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
-                                   C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None, N.stream_ptr()),
-            'rfn_beam_loop_ex')
+    N.check(N.lib.rfn_beam_loop_ex2(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
+                                    stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
+                                    c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(),
+                                    b.order.data_ptr(), b.ids.data_ptr(), b.done_seq.data_ptr(), b.done_lp.data_ptr(),
+                                    b.done_p.data_ptr(), b.done_n.data_ptr(), b.active.data_ptr(), b.max_done,
+                                    stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                    C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None,
+                                    C.byref(div.struct(b)) if div is not None else None, N.stream_ptr()),
+            'rfn_beam_loop_ex2')
 
 
 class _Constraints:
@@ -244,6 +248,47 @@ class _Sampling:
         return self._struct
 
 
+class _Diversity:
+    """Diverse beam search of one call (rfn.h "diverse beam search"): opt['group_size'] = G (default 1) groups of beam_size / G
+    beams each, opt['diversity_lambda'] (default 0.5) the Hamming penalty per earlier group that chose the token at this step.
+    `parse` returns None for G == 1, whatever lambda is, so such a call issues exactly the launches it always did."""
+
+    @classmethod
+    def parse(cls, opt, W):
+        g, lam = opt.get('group_size', 1), opt.get('diversity_lambda', 0.5)
+        g, lam = int(1 if g is None else g), float(0.5 if lam is None else lam)
+        if g < 1:
+            raise ValueError('group_size must be >= 1, got %d' % g)
+        if W % g:
+            raise ValueError('beam_size %d is not a multiple of group_size %d' % (W, g))
+        if not lam >= 0.0:
+            raise ValueError('diversity_lambda must be >= 0, got %r' % lam)
+        if g == 1:
+            return None
+        d = cls()
+        d.groups, d.lam = g, lam
+        return d
+
+    def struct(self, bufs):
+        self._struct = N.BeamDiversity(self.groups, self.lam, bufs.done_group.data_ptr())
+        return self._struct
+
+    def step(self, bufs, topv, topi, V1, t):
+        """One step of a host-stepped search (the ensemble's): rfn_beam_step_div on the rows' top-W lists."""
+        b = bufs
+        N.check(N.lib.rfn_beam_step_div(topv.data_ptr(), topi.data_ptr(), V1, b.W, self.groups, self.lam, b.S, t, b.B, b.max_done,
+                                        b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
+                                        b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(), b.done_n.data_ptr(),
+                                        b.done_group.data_ptr(), b.active.data_ptr(), N.stream_ptr()), 'rfn_beam_step_div')
+
+
+def _diverse_beams(done_beams, groups):
+    """Per image the G group bests: entry g is the first of the image's ranked done beams (length penalty included) that group
+    g produced.  Lazy, as done_beams is."""
+    return _LazyList(len(done_beams), lambda: [[next((d for d in img if d['group'] == g), None) for g in range(groups)]
+                                               for img in done_beams])
+
+
 def _length_penalty(opt):
     alpha = float(opt.get('length_penalty', 0.0) or 0.0)
     if alpha < 0.0 or alpha != alpha:
@@ -251,7 +296,7 @@ def _length_penalty(opt):
     return alpha
 
 
-def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0):
+def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None):
     """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
     once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
@@ -261,7 +306,10 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
 
     length_penalty = alpha > 0 ranks by p / len^alpha instead (len: the tokens up to and including the first 0, S without one);
     ties keep construction order, and `p` / top_prob stay the raw sums.  len^alpha comes from a host table of S + 1 doubles
-    and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly."""
+    and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly.
+
+    done_group (a diverse search): every done beam's group goes through the same gather, and every done_beams dict gets it as
+    'group'."""
     dev, B = done_p.device, done_p.size(0)
     score = done_p
     if length_penalty:
@@ -275,7 +323,7 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     rank = torch.sort(key, dim=1, stable=True).indices
     pick = rank[:, :, None].expand(-1, -1, S)
     s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
-    src = _BeamResults(s_all, l_all, p_all, done_n)
+    src = _BeamResults(s_all, l_all, p_all, done_n, done_group.gather(1, rank) if done_group is not None else None)
     return (s_all[:, 0].contiguous(), l_all[:, 0].contiguous(), _LazyList(B, lambda: src.top_seq()),
             _LazyList(B, lambda: src.top_prob()), _LazyList(B, lambda: src.done_beams()))
 
@@ -283,14 +331,16 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
 class _BeamResults:
     """Host copies of the sorted done beams, fetched once, on demand."""
 
-    def __init__(self, s_all, l_all, p_all, done_n):
+    def __init__(self, s_all, l_all, p_all, done_n, g_all=None):
         self._dev = (s_all, l_all, p_all, done_n)
+        self._g_dev = g_all
         self._host = None
 
     def host(self):
         if self._host is None:
             s_all, l_all, p_all, done_n = self._dev
             self._host = (s_all.cpu(), l_all.cpu(), p_all.cpu().tolist(), done_n.cpu().tolist())
+            self._g_host = self._g_dev.cpu().tolist() if self._g_dev is not None else None
         return self._host
 
     def top_seq(self):
@@ -304,8 +354,13 @@ class _BeamResults:
     def done_beams(self):
         """misc/RecurrentFusionModel.py:529-531: per image the list of {'seq', 'logps', 'p'} dicts, best first."""
         s_all, l_all, probs, counts = self.host()
-        return [[{'seq': a, 'logps': b_, 'p': c_} for a, b_, c_ in zip(s_all[k, :n].unbind(0), l_all[k, :n].unbind(0), probs[k][:n])]
-                for k, n in enumerate(counts)]
+        beams = [[{'seq': a, 'logps': b_, 'p': c_} for a, b_, c_ in zip(s_all[k, :n].unbind(0), l_all[k, :n].unbind(0), probs[k][:n])]
+                 for k, n in enumerate(counts)]
+        if self._g_host is not None:                 # a diverse search: the group that produced each beam
+            for k, img in enumerate(beams):
+                for d, g in zip(img, self._g_host[k]):
+                    d['group'] = g
+        return beams
 
 
 class _LazyList(collections.abc.MutableSequence):

@@ -17,7 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .decode import BeamBuffers, GreedyBuffers, _Constraints, _length_penalty, _sorted_done_beams, _Stepper
+from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _diverse_beams, _Diversity, _length_penalty, _sorted_done_beams,
+                     _Stepper)
 
 
 class EnsembleDecoder:
@@ -89,13 +90,14 @@ class EnsembleDecoder:
     def sample_beam(self, fc_feats, att_feats, opt={}):
         """Beam search on the members' averaged distribution -> (seq (B, S), seqLogprobs (B, S), top_seq, top_prob) with
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,
-        best first); `self.done_beams` as there.  A one-member ensemble IS that model's sample_beam, bit for bit."""
+        best first); `self.done_beams` as there, and with opt['group_size'] > 1 (diverse beam search) `self.diverse_beams` and the
+        'group' key as there.  A one-member ensemble IS that model's sample_beam, bit for bit."""
         W = opt.get('beam_size', 10)
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
         if W > 32 or S > 64 or W > V1:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
-        cons, alpha = _Constraints.parse(opt, V1, S), _length_penalty(opt)
+        cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
         steppers = []
         for m in self.models:
             comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
@@ -103,7 +105,7 @@ class EnsembleDecoder:
                                      h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous()))
         dev = steppers[0].h.device
         st = N.stream_ptr()
-        b = BeamBuffers(B, W, S, dev)
+        b = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
         rows = b.rows
         topv, topi = b.top_lists()
         logit_sum = torch.empty(rows, V1, device=dev)
@@ -112,10 +114,13 @@ class EnsembleDecoder:
             cons.bind(rows, dev)
         for t in range(S + 1):
             if t >= 1:
-                N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, b.max_done, b.bs.data_ptr(),
-                                                 b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
-                                                 b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(),
-                                                 b.done_n.data_ptr(), b.active.data_ptr(), st), 'rfn_beam_step_topk')
+                if div is not None:
+                    div.step(b, topv, topi, V1, t)
+                else:
+                    N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, b.max_done, b.bs.data_ptr(),
+                                                     b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
+                                                     b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(),
+                                                     b.done_n.data_ptr(), b.active.data_ptr(), st), 'rfn_beam_step_topk')
                 if t == S:
                     break                      # the reference runs one more decoder step whose output is never used
                 for sp in steppers:
@@ -128,6 +133,7 @@ class EnsembleDecoder:
                 N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
                         'rfn_log_softmax_topk')
         seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b.done_seq, b.done_lp, b.done_p, b.done_n, S,
-                                                                             b.max_done, alpha)
+                                                                             b.max_done, alpha, b.done_group)
+        self.diverse_beams = _diverse_beams(self.done_beams, div.groups) if div is not None else None
         return seq, seq_lp, top_seq, top_prob
 

@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _LazyList, _length_penalty, _Sampling, _sorted_done_beams,
-                     _Stepper, early_exit, run_beam_loop, run_greedy_loop)
+from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Sampling,
+                     _sorted_done_beams, _Stepper, early_exit, run_beam_loop, run_greedy_loop)
 
 _INIT = 0.1
 
@@ -441,6 +441,7 @@ class RecurrentFusionModel(nn.Module):
         self._seed_dev = None
         self._ss_uniforms = None
         self.done_beams = []
+        self.diverse_beams = None       # sample_beam with group_size > 1: per image the G group bests
 
     def init_weights(self):
         """misc/RecurrentFusionModel.py:188-196."""
@@ -857,14 +858,18 @@ class RecurrentFusionModel(nn.Module):
         Stages I/II run ONCE for the batch (the reference recomputes them per image on beam_size identical rows),
         all images' beams share one decoder batch of B*beam rows, and rfn_beam_step does the reference's
         candidate / stable-sort / fork / done-beam bookkeeping on the device -- no per-step host read-back.  The
-        done beams are sorted (stably, by -p, as :529) on the host once at the end."""
+        done beams are sorted (stably, by -p, as :529) on the host once at the end.
+
+        opt['group_size'] = G > 1 (with opt['diversity_lambda'], default 0.5): diverse beam search (rfn.h "diverse beam
+        search") -- beam_size is still the total number of beams.  Every `done_beams` dict then carries its 'group', and
+        `self.diverse_beams[k]` lists image k's G group bests under the call's ranking.  G = 1 is the plain search."""
         beam_size = opt.get('beam_size', 10)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
         assert beam_size <= V1, 'lets assume this for now'
         if beam_size > 32 or S > 64:
             raise N.RfnError('beam search supports beam_size <= 32 and seq_length <= 64')
         W = beam_size
-        cons, alpha = _Constraints.parse(opt, V1, S), _length_penalty(opt)
+        cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
         if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         with torch.no_grad():
@@ -875,12 +880,13 @@ class RecurrentFusionModel(nn.Module):
             # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
             stepper = _Stepper(self, comb_b, h_b.repeat_interleave(W, dim=0).contiguous(),
                                c_b.repeat_interleave(W, dim=0).contiguous(), drop, seed)
-            bufs = BeamBuffers(B, W, S, dev)
-            run_beam_loop(stepper, bufs, cons)
+            bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
+            run_beam_loop(stepper, bufs, cons, div)
             seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
-                                                                            S, bufs.max_done, alpha)
+                                                                            S, bufs.max_done, alpha, bufs.done_group)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
+        self.diverse_beams = _diverse_beams(done_beams, div.groups) if div is not None else None
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch
 

@@ -2,7 +2,9 @@
 """BASELINE.json configs[4]: beam-search eval (beam=5) + self-critical RL sample path, M=4, L=196, D=2048, B=128 on one
 MI355X.  Prints one JSON line per mode (images/s, inputs resident in HBM).  Not the headline metric: see bench.py."""
 import json, os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# --tree DIR: import the package (and bench.py) from another checkout of this repository -- the --diverse comparison's parent
+TREE = sys.argv[sys.argv.index('--tree') + 1] if '--tree' in sys.argv else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.abspath(TREE))
 import torch
 import bench as HB
 import recurrent_fusion_network_amd as R
@@ -140,7 +142,71 @@ def truncation_ab(out_path, rounds=7):
         json.dump(res, f, indent=1)
         f.write('\n')
 
+def _beam6_ms(extra, reps=10):
+    with torch.no_grad():
+        return timed(lambda: model.sample_beam(fc, att, dict(extra, beam_size=6)), reps)[0] * 1e3
+
+def diverse_child(rounds):
+    """--diverse-child: the plain beam_size = 6 call of whatever checkout --tree names, `rounds` windows -> one JSON line."""
+    model.eval()
+    _beam6_ms({})
+    print(json.dumps({'beam6_ms': [round(_beam6_ms({}), 3) for _ in range(rounds)]}), flush=True)
+
+def diverse_ab(out_path, parent_tree, rounds=7):
+    """--diverse [--parent DIR]: config 5, one sample_beam call at beam_size = 6 with group_size in {1, 2, 3, 6} (diversity_lambda
+    0.5), windows of 10 calls after a warm-up call, the four settings alternating, medians of `rounds`.  The parent commit's
+    plain call is timed by this same script in a fresh child process on a built checkout of it (--parent), once before and
+    once after, so its numbers come from the same box in the same session; its spread is the range of all its windows."""
+    import statistics, subprocess
+    S = cfg.seq_length
+    model.eval()
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=9488, seq=%d, B=%d, beam_size=6' % (S, B), 'rounds': rounds, 'calls_per_window': 10,
+           'diversity_lambda': 0.5}
+
+    def parent_run():
+        if not parent_tree:
+            return None
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), '--tree', parent_tree, '--diverse-child', str(rounds)],
+                             check=True, capture_output=True, text=True, timeout=600).stdout
+        return json.loads([l for l in out.splitlines() if l.startswith('{')][-1])['beam6_ms']
+
+    before = parent_run()
+    groups = (1, 2, 3, 6)
+    ms = {g: [] for g in groups}
+    for g in groups:
+        _beam6_ms({'group_size': g})                     # every shape warmed before the first window
+    for _ in range(rounds):
+        for g in groups:
+            ms[g].append(_beam6_ms({'group_size': g}))
+    after = parent_run()
+    for g in groups:
+        res['group_size_%d' % g] = {'ms': round(statistics.median(ms[g]), 3), 'min': round(min(ms[g]), 3), 'max': round(max(ms[g]), 3)}
+    with torch.no_grad():
+        res['launches_per_call'] = {('group_size_%d' % g): HB.count_launches(lambda: model.sample_beam(fc, att, {'beam_size': 6, 'group_size': g}))
+                                    for g in groups}
+    if before is None:
+        res['parent'] = 'not measured (no --parent checkout given)'
+    else:
+        both = before + after
+        spread = max(both) - min(both)
+        pm = statistics.median(both)
+        res['parent'] = {'ms': round(pm, 3), 'ms_before': round(statistics.median(before), 3), 'ms_after': round(statistics.median(after), 3),
+                         'min': round(min(both), 3), 'max': round(max(both), 3), 'spread_ms': round(spread, 3)}
+        res['minus_parent_ms'] = {('group_size_%d' % g): round(statistics.median(ms[g]) - pm, 3) for g in groups}
+        res['group_size_1_within_parent_spread'] = bool(abs(statistics.median(ms[1]) - pm) <= spread)
+    print(json.dumps(res), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
 PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
+if '--diverse-child' in sys.argv:
+    diverse_child(int(sys.argv[sys.argv.index('--diverse-child') + 1]))
+    sys.exit(0)
+if '--diverse' in sys.argv:
+    diverse_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'diverse_beam.json'),
+               sys.argv[sys.argv.index('--parent') + 1] if '--parent' in sys.argv else None)
+    sys.exit(0)
 if '--truncate' in sys.argv:
     truncation_ab(os.path.join(PROFILES, 'decode_truncation.json'))
     sys.exit(0)
