@@ -487,6 +487,29 @@ int rfn_dec_attn_bwd(const float* proj, int64_t psb, int64_t psl, const float* h
                      float* dhproj, float* dw_part, void* stream);
 int rfn_dec_du(const float* alpha, const float* dgates, int S, int B, int L, int GD, float* dU, int64_t usb,
                int64_t usl, void* stream);
+/* The backward pair with n = row_div rows per image ("multi-sample self-critical" below; misc/LSTMSoftAttentionCore.py:64-81 on
+ * n rows that hold the same thought vectors).  Limits, alignment rules and kernels as above; row_div < 1: RFN_ERR_SHAPE.
+ * rfn_dec_attn_bwd_ex: proj and U are read at image b / row_div (ceil(B / row_div) rows each), exactly as rfn_dec_cell_fwd reads
+ *   them; alpha, dgates, hproj, dhproj, dw_part AND dproj stay per row -- dproj is (b, l, :) at dproj + b * dpsb + l * dpsl for all
+ *   B rows, so no two rows of an image ever read-modify-write one address (no atomics; the caller sums the rows afterwards,
+ *   rfn_rowgroup_sum).  A row's arithmetic is that of rfn_dec_attn_bwd on physically repeated proj / U: the same bits on the
+ *   same kernel.  row_div = 1: rfn_dec_attn_bwd, which forwards here.
+ * rfn_dec_du_ex: B % row_div == 0 (RFN_ERR_SHAPE otherwise); dU is (B / row_div images, L, GD) with strides usb / usl and
+ *   dU[k, l, :] = sum_j sum_s alpha[s, k * n + j, l] * dgates[s, k * n + j, :]: ONE running sum from 0, the image's rows j
+ *   ascending outermost, the steps s ascending inside.  The 16-byte kernel stages row_div * S * L alpha values in LDS (<= 64 KiB,
+ *   else refused); the scalar kernel takes any.  Both give the same bits.  row_div = 1: rfn_dec_du, which forwards here. */
+int rfn_dec_attn_bwd_ex(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
+                        const float* alpha, const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg,
+                        int B, int row_div, int L, int A, int GD, float* dproj, int64_t dpsb, int64_t dpsl, int accumulate,
+                        float* dhproj, float* dw_part, void* stream);
+int rfn_dec_du_ex(const float* alpha, const float* dgates, int S, int B, int L, int GD, int row_div, float* dU, int64_t usb,
+                  int64_t usl, void* stream);
+/* y[r, 0:cols] = ((0 + x[r * n, :]) + x[r * n + 1, :]) + ... + x[r * n + n - 1, :] for r < rows: every n consecutive rows of x
+ * (row stride ldx) summed onto one row of y (row stride ldy), j ascending -- the fan-in of the per-row d att_2_att_h(v) slabs
+ * (T2, B, A) onto the images (T2, B / n, A), which is this call with rows = T2 * B / n.  One output chunk per thread (16 bytes when
+ * cols % 4 == 0, ldx and ldy are multiples of 4 and x, y are 16-byte aligned, else one float; same bits), no atomics.
+ * RFN_ERR_SHAPE: n < 1, rows < 1, cols < 1, a stride below cols.  x and y must not overlap. */
+int rfn_rowgroup_sum(const float* x, int64_t ldx, int n, float* y, int64_t ldy, int64_t rows, int cols, void* stream);
 
 /* ---- row-panel GEMM of the recurrences (csrc/rfn_cellgemm.hip) ------------------------------------------------------
  * One launch computes up to RFN_CELL_MAXOUT outputs over the same M (= batch) rows, each with its own destination,
@@ -1151,6 +1174,54 @@ int rfn_rougel_score(const int64_t* res, int n_rows, int T_res, const int32_t* r
  * none is left), *n_skipped (NULL or one int64) = how many were.  One workgroup, fp64 in a fixed order (strided partial sums,
  * then a binary tree): bitwise reproducible, no atomics.  n, stride >= 1 (RFN_ERR_SHAPE otherwise). */
 int rfn_score_mean(const double* scores, int64_t n, int64_t stride, double* mean, int64_t* n_skipped, void* stream);
+
+/* ---- multi-sample self-critical ------------------------------------------------------------------------------------------
+ * train_rl.py:160-203 draws one caption per row and pays a second, greedy decode for the baseline.  Here n captions are drawn
+ * per image and a draw's baseline is the mean score of the image's other n - 1 draws: no greedy pass, n policy-gradient samples
+ * per run of stages I / II (misc/RecurrentFusionModel.py:199-255).
+ *   Rows are image-major: row r = k * n + j is draw j of image k (as rows_per_image of rfn_decoder_loop_ex2 and the beam rows).
+ *   B counts rows, B % n == 0, Bc = B / n counts images.
+ *   comb is (T2, Bc, R).  h0 and c0 stay per row (B, R): the host fans them out and sums their gradients back.
+ *   d_comb comes back (T2, Bc, R), already summed over each image's n rows.
+ *   Dropout: stages I / II draw one mask per image (they run once per image); the decoder's mask is per ROW, counter b * R + unit
+ *   with b the row (rfn_dropout_mask over B * R values at RFN_DROP_OFFSET_DECODER + step).
+ *   Only the hoisted decoder cell has this form: RFN_PATH_OPT_DEC_UNHOISTED (or a persistent decoder chain) with n > 1 is
+ *   RFN_ERR_UNSUPPORTED, as in rfn_decoder_loop_ex2.  n < 1 or B % n != 0: RFN_ERR_SHAPE (rfn_decoder_ws_bytes_ex: 0).
+ * The _ex forms below are rfn_decoder_ws_bytes / _fwd / _fwd_sampled / _bwd (misc/RecurrentFusionModel.py:257-281, 623-631) with
+ * rows_per_image = n; the old names forward with 1, and with 1 every launch and every bit is theirs.
+ *   Forward: att_2_att_h(comb) and U = comb . z2h.weight^T (misc/LSTMSoftAttentionCore.py:64-66, 81) are computed once per image
+ *   (T2 * Bc GEMM rows); every step's cell reads them at image b / n (rfn_dec_cell_fwd's row_div).  Everything else is per row,
+ *   so a row's log-probs are the bits of the old call on comb physically repeated n times.
+ *   Backward: the sweep as before with rfn_dec_attn_bwd_ex(row_div = n), d Pd kept per row; then rfn_dec_du_ex (sum over j, s as
+ *   documented there), rfn_rowgroup_sum of d Pd onto the images (j ascending), d_comb = dPd_img . W_att + dU . W_z over T2 * Bc
+ *   rows, and d att_2_att_h / d z2h.weight from dPd_img / dU against comb over T2 * Bc rows.  All other gradients are per row.
+ *   The workspace grows by the per-image d Pd (T2 * Bc * A floats) when n > 1; Pd, U and dU shrink to Bc rows.  The logits-only
+ *   form (log_prob == NULL, rfn_decoder_logits) exists for one row per image only: RFN_ERR_ARG with n > 1. */
+size_t rfn_decoder_ws_bytes_ex(const rfn_dims* d, int B, int S, int train, int rows_per_image);
+int rfn_decoder_fwd_ex(const rfn_dims* d, int B, int S, const float* const* params, const float* comb /* (T2,B/n,R) */,
+                       const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob, void* ws,
+                       size_t ws_bytes, int train, uint64_t seed, int rows_per_image, void* stream);
+int rfn_decoder_fwd_sampled_ex(const rfn_dims* d, int B, int S, const float* const* params, const float* comb,
+                               const float* h0, const float* c0, int64_t* ids, int64_t ld_ids, float ss_prob,
+                               float inv_temperature, const float* u_draw, const float* u_coin, float* log_prob, void* ws,
+                               size_t ws_bytes, int train, uint64_t seed, int rows_per_image, void* stream);
+int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* params, const float* comb,
+                       const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, const float* log_prob,
+                       const float* d_log_prob, float* d_comb /* (T2,B/n,R) */, float* d_h0, float* d_c0,
+                       float* const* grads, void* ws, size_t ws_bytes, uint64_t seed, int rows_per_image, void* stream);
+/* The leave-one-out reward (compute_reward's mix, get_rewards.py:39-112, with the grouped baseline in place of the greedy row).
+ * For a score vector s of B rows and group size n:
+ *   baseline 1 (leave-one-out, n >= 2): base[k*n+j] = (((0.0 + s[k*n+i0]) + s[k*n+i1]) + ...) / (n - 1) over i != j ascending;
+ *                                       diff = s - base.        baseline 0 (none): diff = s.
+ *   reward[r, :] = ((diff_bleu4[r] * bleu4_weight) + (diff_cider[r] * cider_weight)) + 0.0, broadcast over T.
+ * Every sum, product and quotient is rounded on its own in fp64 (no contraction; the division is correctly rounded).  A NULL
+ * scorer is the reference's 0 * weight.  A NaN score poisons its image's group through the arithmetic, and only that group.
+ * cider: NULL or B doubles; bleu: NULL or B x 4 doubles (column 3 is used); out (B, T) f32 = the cast of out64 (B, T) f64, either
+ * may be NULL.  One launch, no allocation, no synchronisation (capturable in a graph).
+ * RFN_ERR_SHAPE: B < 1, T < 1, n < 1, B % n != 0, baseline not 0 or 1, n == 1 with baseline 1.  RFN_ERR_ARG: both scores NULL or
+ * both outputs NULL. */
+int rfn_scst_reward_group(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int n, int T,
+                          int baseline, float* out, double* out64, void* stream);
 
 #ifdef __cplusplus
 }

@@ -228,6 +228,15 @@ def _load():
         'rfn_rougel_ws_bytes': (SZ, [I, I, I, I, I]),
         'rfn_rougel_score': (C.c_int, [P, I, I, P, P, P, I, I, I, I, C.c_uint, C.c_double, P, P, P, SZ, P]),
         'rfn_score_mean': (C.c_int, [P, L, L, P, P, P]),
+        # multi-sample self-critical (rfn.h): the decoder entry points with rows_per_image, their kernels, the grouped reward
+        'rfn_decoder_ws_bytes_ex': (SZ, [DP, I, I, I, I]),
+        'rfn_decoder_fwd_ex': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, SZ, I, U64, I, P]),
+        'rfn_decoder_fwd_sampled_ex': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, I, P]),
+        'rfn_decoder_bwd_ex': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, P, P, P, P, P, SZ, U64, I, P]),
+        'rfn_dec_attn_bwd_ex': (C.c_int, [P, L, L, P, P, P, P, L, L, P, L, I, I, I, I, I, P, L, L, I, P, P, P]),
+        'rfn_dec_du_ex': (C.c_int, [P, P, I, I, I, I, I, P, L, L, P]),
+        'rfn_rowgroup_sum': (C.c_int, [P, L, I, P, L, L, I, P]),
+        'rfn_scst_reward_group': (C.c_int, [P, C.c_double, P, C.c_double, I, I, I, I, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

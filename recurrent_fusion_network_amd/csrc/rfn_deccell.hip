@@ -345,8 +345,8 @@ __global__ __launch_bounds__(ATT_THREADS) void dec_attn_bwd_k(const DecAttnBwdAr
     float* ds_s = al_s + Lp;        // [Lp]
     float* red = ds_s + Lp;         // [ATT_WAVES][DEC_LREG]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x;
-    const float* U = a.U + (long)b * a.usb;
+    const int b = blockIdx.x, pb = b / a.row_div;
+    const float* U = a.U + (long)pb * a.usb;
     const float* dg = a.dgates + (long)b * a.ldg;
     for (int i = tid; i < A; i += ATT_THREADS) {
         hp_s[i] = a.hproj[(long)b * A + i];
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(ATT_THREADS) void dec_attn_bwd_k(const DecAttnBwdAr
     for (int l = tid; l < L; l += ATT_THREADS) ds_s[l] = al_s[l] * (ds_s[l] - dot);   // softmax backward
     __syncthreads();
     // tanh backward over the (L, A) slice (the arithmetic of attn_small_bwd_body): rows in order
-    const float* proj = a.proj + (long)b * a.psb;
+    const float* proj = a.proj + (long)pb * a.psb;
     float* dproj = a.dproj + (long)b * a.dpsb;
     const bool acc = a.accumulate != 0;
     if constexpr (VEC) {
@@ -462,25 +462,26 @@ bool rfn_dec_attn_bwd_fast_ok(const DecAttnBwdArgs& a) {
            rfn_aligned16(a.dgates) && rfn_aligned16(a.hproj) && rfn_aligned16(a.w_out);
 }
 int rfn_dec_attn_bwd_args(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out, const float* alpha,
-                          const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg, int B, int L, int A, int GD,
-                          float* dproj, int64_t dpsb, int64_t dpsl, int accumulate, float* dhproj, float* dw_part, DecAttnBwdArgs* out) {
-    if (B <= 0 || L <= 0 || L > ATS_MAX_L || A <= 0 || GD <= 0) return RFN_ERR_SHAPE;
+                          const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg, int B, int row_div, int L, int A,
+                          int GD, float* dproj, int64_t dpsb, int64_t dpsl, int accumulate, float* dhproj, float* dw_part,
+                          DecAttnBwdArgs* out) {
+    if (B <= 0 || row_div < 1 || L <= 0 || L > ATS_MAX_L || A <= 0 || GD <= 0) return RFN_ERR_SHAPE;
     if (!proj || !hproj || !w_out || !alpha || !U || !dgates || !dproj || !dhproj || !dw_part) return RFN_ERR_ARG;
     DecAttnBwdArgs& a = *out;
     a.proj = proj; a.hproj = hproj; a.w_out = w_out; a.alpha = alpha; a.U = U; a.dgates = dgates;
     a.dproj = dproj; a.dhproj = dhproj; a.dw_part = dw_part;
     a.psb = psb; a.psl = psl; a.usb = usb; a.usl = usl; a.ldg = ldg; a.dpsb = dpsb; a.dpsl = dpsl;
-    a.L = L; a.A = A; a.GD = GD; a.accumulate = accumulate;
+    a.L = L; a.A = A; a.GD = GD; a.accumulate = accumulate; a.row_div = row_div;
     return RFN_OK;
 }
 
-extern "C" int rfn_dec_attn_bwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
-                                const float* alpha, const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg,
-                                int B, int L, int A, int GD, float* dproj, int64_t dpsb, int64_t dpsl, int accumulate,
-                                float* dhproj, float* dw_part, void* stream) {
+extern "C" int rfn_dec_attn_bwd_ex(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
+                                   const float* alpha, const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg,
+                                   int B, int row_div, int L, int A, int GD, float* dproj, int64_t dpsb, int64_t dpsl,
+                                   int accumulate, float* dhproj, float* dw_part, void* stream) {
     DecAttnBwdArgs a;
-    RFN_TRY(rfn_dec_attn_bwd_args(proj, psb, psl, hproj, w_out, alpha, U, usb, usl, dgates, ldg, B, L, A, GD, dproj, dpsb, dpsl,
-                                  accumulate, dhproj, dw_part, &a));
+    RFN_TRY(rfn_dec_attn_bwd_args(proj, psb, psl, hproj, w_out, alpha, U, usb, usl, dgates, ldg, B, row_div, L, A, GD, dproj, dpsb,
+                                  dpsl, accumulate, dhproj, dw_part, &a));
     const bool vecu = GD % 4 == 0 && rfn_aligned16(U) && rfn_aligned16(dgates) && (usb | usl | ldg) % 4 == 0;
     const size_t lds = (size_t)(2 * ((A + 3) & ~3) + 2 * ((L + 3) & ~3) + ATT_WAVES * DEC_LREG) * sizeof(float);
     if (lds > 64 * 1024) return RFN_ERR_SHAPE;
@@ -495,18 +496,26 @@ extern "C" int rfn_dec_attn_bwd(const float* proj, int64_t psb, int64_t psl, con
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
+extern "C" int rfn_dec_attn_bwd(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out,
+                                const float* alpha, const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg,
+                                int B, int L, int A, int GD, float* dproj, int64_t dpsb, int64_t dpsl, int accumulate,
+                                float* dhproj, float* dw_part, void* stream) {
+    return rfn_dec_attn_bwd_ex(proj, psb, psl, hproj, w_out, alpha, U, usb, usl, dgates, ldg, B, 1, L, A, GD, dproj, dpsb, dpsl,
+                               accumulate, dhproj, dw_part, stream);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// d U after the loop: dU[b, l, :] = sum_s alpha[s, b, l] * dgates[s, b, :], s in order.  Reads the stored gate gradients
-// once; one thread per 16-B column chunk of a row.
+// d U after the loop: dU[k, l, :] = sum_j sum_s alpha[s, k * n + j, l] * dgates[s, k * n + j, :] over the n = row_div rows of
+// image k -- j ascending outermost, s ascending inside, every product added to ONE running sum that starts at 0 (n = 1: the sum
+// over s alone).  Reads the stored gate gradients once; one thread per 16-B column chunk of an image; grid.y = images.
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dec_du_k(const float* __restrict__ alpha, const float* __restrict__ dgates, int S, int B,
-                                                int L, int GD, float* __restrict__ dU, long usb, long usl) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];   // [S][L] alpha of this row
-    const int b = blockIdx.y, tid = threadIdx.x;
-    for (int i = tid; i < S * L; i += 256) {
-        const int s = i / L, l = i - s * L;
-        sm[i] = alpha[((long)s * B + b) * L + l];
+                                                int L, int GD, int n, float* __restrict__ dU, long usb, long usl) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];   // [n][S][L] alpha of this image's rows
+    const int k = blockIdx.y, tid = threadIdx.x, SL = S * L;
+    for (int i = tid; i < n * SL; i += 256) {
+        const int j = i / SL, r = i - j * SL, s = r / L, l = r - s * L;
+        sm[i] = alpha[((long)s * B + (long)k * n + j) * L + l];
     }
     __syncthreads();
     const int c = 4 * (blockIdx.x * 256 + tid);
@@ -515,45 +524,56 @@ __global__ __launch_bounds__(256) void dec_du_k(const float* __restrict__ alpha,
         f32x4 acc[DEC_LREG];
 #pragma unroll
         for (int j = 0; j < DEC_LREG; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int s = 0; s < S; ++s) {
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(dgates + ((long)s * B + b) * GD + c);
+        for (int r = 0; r < n; ++r) {
+            const long b = (long)k * n + r;
+            for (int s = 0; s < S; ++s) {
+                const f32x4 gv = *reinterpret_cast<const f32x4*>(dgates + ((long)s * B + b) * GD + c);
 #pragma unroll
-            for (int j = 0; j < DEC_LREG; ++j) {
-                const float al = (l0 + j < L) ? sm[s * L + l0 + j] : 0.f;
-                acc[j] += al * gv;
+                for (int j = 0; j < DEC_LREG; ++j) {
+                    const float al = (l0 + j < L) ? sm[(r * S + s) * L + l0 + j] : 0.f;
+                    acc[j] += al * gv;
+                }
             }
         }
 #pragma unroll
         for (int j = 0; j < DEC_LREG; ++j)
-            if (l0 + j < L) *reinterpret_cast<f32x4*>(dU + (long)b * usb + (long)(l0 + j) * usl + c) = acc[j];
+            if (l0 + j < L) *reinterpret_cast<f32x4*>(dU + (long)k * usb + (long)(l0 + j) * usl + c) = acc[j];
     }
 }
 
 __global__ __launch_bounds__(256) void dec_du_scalar_k(const float* __restrict__ alpha, const float* __restrict__ dgates, int S,
-                                                       int B, int L, int GD, float* __restrict__ dU, long usb, long usl) {
-    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+                                                       int B, int L, int GD, int n, float* __restrict__ dU, long usb, long usl) {
+    const int k = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
     if (c >= GD) return;
     for (int l = 0; l < L; ++l) {
         float acc = 0.f;
-        for (int s = 0; s < S; ++s) acc += alpha[((long)s * B + b) * L + l] * dgates[((long)s * B + b) * GD + c];
-        dU[(long)b * usb + (long)l * usl + c] = acc;
+        for (int r = 0; r < n; ++r) {
+            const long b = (long)k * n + r;
+            for (int s = 0; s < S; ++s) acc += alpha[((long)s * B + b) * L + l] * dgates[((long)s * B + b) * GD + c];
+        }
+        dU[(long)k * usb + (long)l * usl + c] = acc;
     }
 }
 
-extern "C" int rfn_dec_du(const float* alpha, const float* dgates, int S, int B, int L, int GD, float* dU, int64_t usb,
-                          int64_t usl, void* stream) {
-    if (S <= 0 || B <= 0 || L <= 0 || GD <= 0) return RFN_ERR_SHAPE;
+extern "C" int rfn_dec_du_ex(const float* alpha, const float* dgates, int S, int B, int L, int GD, int row_div, float* dU,
+                             int64_t usb, int64_t usl, void* stream) {
+    if (S <= 0 || B <= 0 || L <= 0 || GD <= 0 || row_div < 1 || B % row_div) return RFN_ERR_SHAPE;
     if (!alpha || !dgates || !dU) return RFN_ERR_ARG;
+    const int Bc = B / row_div;
     if (GD % 4 || !rfn_aligned16(dgates) || !rfn_aligned16(dU) || (usb | usl) % 4) {
-        hipLaunchKernelGGL(dec_du_scalar_k, dim3(rfn_cdiv(GD, 256), B), dim3(256), 0, (hipStream_t)stream, alpha, dgates, S, B, L, GD,
-                           dU, (long)usb, (long)usl);
+        hipLaunchKernelGGL(dec_du_scalar_k, dim3(rfn_cdiv(GD, 256), Bc), dim3(256), 0, (hipStream_t)stream, alpha, dgates, S, B, L, GD,
+                           row_div, dU, (long)usb, (long)usl);
         RFN_CHECK_LAUNCH();
         return RFN_OK;
     }
-    const size_t lds = (size_t)S * L * sizeof(float);
+    const size_t lds = (size_t)row_div * S * L * sizeof(float);
     if (lds > 64 * 1024) return RFN_ERR_SHAPE;
-    hipLaunchKernelGGL(dec_du_k, dim3(rfn_cdiv(GD, 1024), B), dim3(256), lds, (hipStream_t)stream, alpha, dgates, S, B, L, GD, dU,
-                       (long)usb, (long)usl);
+    hipLaunchKernelGGL(dec_du_k, dim3(rfn_cdiv(GD, 1024), Bc), dim3(256), lds, (hipStream_t)stream, alpha, dgates, S, B, L, GD, row_div,
+                       dU, (long)usb, (long)usl);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
+}
+extern "C" int rfn_dec_du(const float* alpha, const float* dgates, int S, int B, int L, int GD, float* dU, int64_t usb,
+                          int64_t usl, void* stream) {
+    return rfn_dec_du_ex(alpha, dgates, S, B, L, GD, 1, dU, usb, usl, stream);
 }

@@ -8,17 +8,17 @@
 #define DEC_LREG 8   /* thought vectors whose U values a thread keeps in registers */
 
 struct DecAttnBwdArgs {
-    const float* proj;     // (b, l, :) at proj + b * psb + l * psl
+    const float* proj;     // (b', l, :) at proj + b' * psb + l * psl, b' = b / row_div (the rows of one image share it)
     const float* hproj;    // (B, A)
     const float* w_out;    // (A)
     const float* alpha;    // (B, L)
-    const float* U;        // (b, l, :) at U + b * usb + l * usl, GD wide
+    const float* U;        // (b', l, :) at U + b' * usb + l * usl, GD wide
     const float* dgates;   // (B, GD) row stride ldg
-    float* dproj;          // same shape as proj, strides dpsb / dpsl
+    float* dproj;          // PER ROW: (b, l, :) at dproj + b * dpsb + l * dpsl (no two rows share an address)
     float* dhproj;         // (B, A)
     float* dw_part;        // (B, A)
     long psb, psl, usb, usl, ldg, dpsb, dpsl;
-    int L, A, GD, accumulate;
+    int L, A, GD, accumulate, row_div;
 };
 
 // The same backward for the shapes the path runs at (16-B accesses throughout, A <= 512, L <= 8): every operand -- the U rows and
@@ -35,9 +35,10 @@ __device__ __forceinline__ void dec_attn_bwd_fast_body(const DecAttnBwdArgs& a, 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i4 = tid & 127, half = tid >> 7, col = 4 * i4;
     const bool colok = col < A;
-    const float* U = a.U + (long)b * a.usb;
+    const int pb = b / a.row_div;
+    const float* U = a.U + (long)pb * a.usb;
     const float* dg = a.dgates + (long)b * a.ldg;
-    const float* proj = a.proj + (long)b * a.psb;
+    const float* proj = a.proj + (long)pb * a.psb;
     float* dproj = a.dproj + (long)b * a.dpsb;
     const bool acc = a.accumulate != 0;
     // ---- requests of the tanh-backward phase (they land under the d alpha sums) --------------------------------------------

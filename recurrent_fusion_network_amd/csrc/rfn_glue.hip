@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "rfn_common.h"
+#include "rfn_rows.h"
 
 // ---- out[n] (+)= sum_r X[r, n] ----------------------------------------------------------------
 // block = CW columns x (1024 / CW) row lanes, 4 independent row streams per thread; the lanes' partial sums are
@@ -419,6 +420,45 @@ extern "C" int rfn_bcast_to_groups(int npairs, float alpha, const float* const* 
     }
     hipLaunchKernelGGL(bcast_groups_k, dim3(rfn_cdiv((long)rows * cols, 256), npairs), dim3(256), 0,
                        (hipStream_t)stream, a, alpha, (long)ldx, (long)gstride, G, (long)ldy, rows, cols);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- y[r, :] = ((0 + x[r*n, :]) + x[r*n + 1, :]) + ... + x[r*n + n - 1, :]: the n consecutive rows of a group summed, j
+// ascending (multi-sample self-critical, rfn.h: d Pd of an image's n decoder rows -> the image).  One output chunk per thread
+// (16 B where cols, the strides and the pointers allow, else one float), no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rowgroup_sum_k(const float* __restrict__ x, long ldx, int n, float* __restrict__ y, long ldy,
+                                                      long rows, int cols) {
+    constexpr int W = VEC ? 4 : 1;
+    const int cpr = (cols + W - 1) / W;                  // chunks per row
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * cpr) return;
+    const long r = i / cpr;
+    const int c = (int)(i - r * cpr) * W;
+    const float* p = x + r * n * ldx + c;
+    if constexpr (VEC) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < n; ++j) s += *reinterpret_cast<const f32x4*>(p + j * ldx);
+        *reinterpret_cast<f32x4*>(y + r * ldy + c) = s;
+    } else {
+        float s = 0.f;
+        for (int j = 0; j < n; ++j) s += p[j * ldx];
+        y[r * ldy + c] = s;
+    }
+}
+extern "C" int rfn_rowgroup_sum(const float* x, int64_t ldx, int n, float* y, int64_t ldy, int64_t rows, int cols, void* stream) {
+    if (n < 1 || rows <= 0 || cols <= 0 || ldx < cols || ldy < cols) return RFN_ERR_SHAPE;
+    if (!x || !y) return RFN_ERR_ARG;
+    const bool vec = cols % 4 == 0 && (ldx | ldy) % 4 == 0 && rfn_aligned16(x) && rfn_aligned16(y);
+    const long chunks = (long)rows * (vec ? cols / 4 : cols);
+    if (chunks > 0x7fffffffL * 256) return RFN_ERR_SHAPE;
+    if (vec)
+        hipLaunchKernelGGL(rowgroup_sum_k<true>, dim3(rfn_cdiv(chunks, 256)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, n, y,
+                           (long)ldy, (long)rows, cols);
+    else
+        hipLaunchKernelGGL(rowgroup_sum_k<false>, dim3(rfn_cdiv(chunks, 256)), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, n, y,
+                           (long)ldy, (long)rows, cols);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -20,8 +20,9 @@ int rfn_cg_replan32(CgPrepared* pz);      // re-tile a prepared launch on the 32
 // body, and a prepared store-epilogue dX product launched WITH those rows in one grid (rfn_cellgemm.hip; RFN_ERR_UNSUPPORTED =
 // nothing launched, the caller issues the two launches).
 int rfn_dec_attn_bwd_args(const float* proj, int64_t psb, int64_t psl, const float* hproj, const float* w_out, const float* alpha,
-                          const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg, int B, int L, int A, int GD,
-                          float* dproj, int64_t dpsb, int64_t dpsl, int accumulate, float* dhproj, float* dw_part, DecAttnBwdArgs* out);
+                          const float* U, int64_t usb, int64_t usl, const float* dgates, int64_t ldg, int B, int row_div, int L, int A,
+                          int GD, float* dproj, int64_t dpsb, int64_t dpsl, int accumulate, float* dhproj, float* dw_part,
+                          DecAttnBwdArgs* out);
 bool rfn_dec_attn_bwd_fast_ok(const DecAttnBwdArgs& a);
 int rfn_cg_launch_with_rows(const CgPrepared& pz, const DecAttnBwdArgs& rows_args, int rows, void* stream);
 

@@ -278,11 +278,12 @@ PrefixLayout prefix_layout(const rfn_dims* d, int B, int train);
 const int DEC_KSPLIT = 4;   // the decoder's d gates . W_hh (K = 4R) is computed as this many K-split partial products (rfn_decoder_bwd)
 struct DecoderLayout {
     size_t Pd, Ud, xs, gd, hd, cd, hpd, ald, zd, logits;
-    size_t dhe, dhrec, dc, dz, dal, dwp, dhpd, dPd, dUd, dxs;
+    size_t dhe, dhrec, dc, dz, dal, dwp, dhpd, dPd, dPi, dUd, dxs;
     size_t gws, tk, bar;
     size_t total;
 };
-DecoderLayout decoder_layout(const rfn_dims* d, int B, int S, int train);
+// n = rows per image (rfn.h "multi-sample self-critical"; must divide B): Pd, Ud, dUd and dPi hold B / n images
+DecoderLayout decoder_layout(const rfn_dims* d, int B, int S, int train, int n = 1);
 int stage1_cell_cus();   // CU count of the current device (cached); 256 when it cannot be read
 
 const uint64_t OFF_STAGE2 = RFN_DROP_OFFSET_STAGE2, OFF_DECODER = RFN_DROP_OFFSET_DECODER;   // rfn.h: rfn_dropout_mask
@@ -299,6 +300,13 @@ inline size_t cproj_u_off(const rfn_dims* d, int Bc) { return ((size_t)d->T2 * B
 int decoder_cell_core(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                       const float* U, int row_div, const float* h, const float* c, float* h_next, float* c_next,
                       float* hp, float* al, float* z, float* g, const GemmCtx& gx, RfnSeed seed, int step, void* st);
+
+// rfn_decoder_fwd_begin / rfn_decoder_fwd_step with n rows per image (rfn_decoder_fwd_sampled_ex queues them)
+int decoder_fwd_begin_n(const rfn_dims* d, int B, int S, int n, const float* const* prm, const float* comb, const float* h0,
+                        const float* c0, void* ws, size_t ws_bytes, int train, void* st);
+int decoder_fwd_step_n(const rfn_dims* d, int B, int S, int n, int s, const float* const* prm, const float* comb,
+                       const int64_t* ids_s, int64_t ld_ids, float* log_prob, void* ws, size_t ws_bytes, int train,
+                       uint64_t seed_arg, void* st);
 
 }  // namespace rfn_path
 using namespace rfn_path;

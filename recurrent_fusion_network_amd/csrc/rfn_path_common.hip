@@ -236,14 +236,15 @@ PrefixLayout prefix_layout(const rfn_dims* d, int B, int train) {
     return L;
 }
 
-DecoderLayout decoder_layout(const rfn_dims* d, int B, int S, int train) {
+DecoderLayout decoder_layout(const rfn_dims* d, int B, int S, int train, int n) {
     const size_t GD = (size_t)gate_width(d->decoder_maxout, d->R);
     DecoderLayout L;
     memset(&L, 0, sizeof(L));
     Bump b;
     const size_t R = d->R, A = d->A, E = d->E, T2 = d->T2, V1 = d->V1, Bz = B, Sz = S;
-    L.Pd = b.take(T2 * Bz * A);
-    L.Ud = b.take(T2 * Bz * GD);      // U = thought vectors . W_z^T (z2h hoisted through the attention, rfn_deccell.hip)
+    const size_t Bi = B / n;          // images: what is computed from the thought vectors alone is kept once per image
+    L.Pd = b.take(T2 * Bi * A);
+    L.Ud = b.take(T2 * Bi * GD);      // U = thought vectors . W_z^T (z2h hoisted through the attention, rfn_deccell.hip)
     L.xs = b.take(Sz * Bz * E);
     L.gd = b.take(Sz * Bz * GD);
     L.hd = b.take((Sz + 1) * Bz * R);
@@ -263,8 +264,9 @@ DecoderLayout decoder_layout(const rfn_dims* d, int B, int S, int train) {
         L.dal = b.take(Bz * T2);
         L.dwp = b.take(Sz * Bz * A);
         L.dhpd = b.take(Sz * Bz * A);
-        L.dPd = b.take(T2 * Bz * A);
-        L.dUd = b.take(T2 * Bz * GD);
+        L.dPd = b.take(T2 * Bz * A);      // per ROW: no two rows of an image accumulate into one address
+        if (n > 1) L.dPi = b.take(T2 * Bi * A);   // ... and summed onto the image after the sweep
+        L.dUd = b.take(T2 * Bi * GD);
         L.dxs = b.take(Sz * Bz * E);
     }
     L.total = b.off;

@@ -176,24 +176,31 @@ extern "C" int rfn_decoder_loop(const rfn_dims* d, int B, int steps, const float
 // grad :623-631), queued by one call: begin, then for every step s >= 1 rows whose coin u_coin[s][b] < ss_prob get a
 // token drawn from step s-1's distribution (uniform u_draw[s][b]), then rfn_decoder_fwd_step.  Leaves workspace, ids and
 // log_prob exactly as the host loop over rfn_multinomial_pick / rfn_decoder_fwd_step does.
-extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
-                                       const float* h0, const float* c0, int64_t* ids, int64_t ld_ids, float ss_prob,
-                                       float inv_temperature, const float* u_draw, const float* u_coin, float* log_prob,
-                                       void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
+extern "C" int rfn_decoder_fwd_sampled_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                          const float* h0, const float* c0, int64_t* ids, int64_t ld_ids, float ss_prob,
+                                          float inv_temperature, const float* u_draw, const float* u_coin, float* log_prob,
+                                          void* ws, size_t ws_bytes, int train, uint64_t seed, int rows_per_image, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed_checked;
     RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
     if (!prm || !comb || !h0 || !c0 || !ids || !u_draw || !u_coin || !log_prob || !ws) return RFN_ERR_ARG;
-    RFN_TRY(rfn_decoder_fwd_begin(d, B, S, prm, comb, h0, c0, ws, ws_bytes, train, st));
+    RFN_TRY(decoder_fwd_begin_n(d, B, S, rows_per_image, prm, comb, h0, c0, ws, ws_bytes, train, st));
     const long ld_b = (long)S * d->V1;
     for (int s = 0; s < S; ++s) {
         if (s >= 1)
             RFN_TRY(rfn_multinomial_pick(log_prob + (long)(s - 1) * d->V1, ld_b, B, d->V1, inv_temperature, u_draw + (long)s * B,
                                          u_coin + (long)s * B, ss_prob, ids + s, ld_ids, st));
-        RFN_TRY(rfn_decoder_fwd_step(d, B, S, s, prm, comb, ids + s, ld_ids, log_prob, ws, ws_bytes, train, seed, st));
+        RFN_TRY(decoder_fwd_step_n(d, B, S, rows_per_image, s, prm, comb, ids + s, ld_ids, log_prob, ws, ws_bytes, train, seed, st));
     }
     return RFN_OK;
+}
+extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                       const float* h0, const float* c0, int64_t* ids, int64_t ld_ids, float ss_prob,
+                                       float inv_temperature, const float* u_draw, const float* u_coin, float* log_prob,
+                                       void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
+    return rfn_decoder_fwd_sampled_ex(d, B, S, prm, comb, h0, c0, ids, ld_ids, ss_prob, inv_temperature, u_draw, u_coin, log_prob, ws,
+                                      ws_bytes, train, seed, 1, st);
 }
 
 // sample_beam's search (misc/RecurrentFusionModel.py:451-531) for all images at once, queued by one call: per step the

@@ -18,9 +18,18 @@ static int attn1_bwd(const float* proj, long psb, long psl, const float* hp, con
                               acc, &dhp, &dwp, &dx, st);
 }
 
+// rows_per_image = n > 1 (rfn.h "multi-sample self-critical"): the rows k * n .. k * n + n - 1 are n draws of image k and read
+// its thought vectors; comb, Pd, U, dU and d_comb count the Bc = B / n images, everything else the B rows.  Hoisted cell only.
+static int rows_per_image_ok(const rfn_dims* d, int B, int n) {
+    if (n < 1 || B % n) return RFN_ERR_SHAPE;
+    return (n > 1 && !dec_hoisted(d)) ? RFN_ERR_UNSUPPORTED : RFN_OK;
+}
+extern "C" size_t rfn_decoder_ws_bytes_ex(const rfn_dims* d, int B, int S, int train, int rows_per_image) {
+    if (check_dims(d) != RFN_OK || B < 1 || S < 1 || rows_per_image < 1 || B % rows_per_image) return 0;
+    return decoder_layout(d, B, S, train, rows_per_image).total * sizeof(float);
+}
 extern "C" size_t rfn_decoder_ws_bytes(const rfn_dims* d, int B, int S, int train) {
-    if (check_dims(d) != RFN_OK || B < 1 || S < 1) return 0;
-    return decoder_layout(d, B, S, train).total * sizeof(float);
+    return rfn_decoder_ws_bytes_ex(d, B, S, train, 1);
 }
 
 // One decoder cell call on given buffers (g already holds i2h(x)): h_2_att_h(h), attention over the fused thoughts,
@@ -107,11 +116,11 @@ struct DecStepBufs {
 };
 // The decoder cell of step s: h_2_att_h, attention over the fused thoughts, h2h + z2h accumulated onto the gates, LSTM
 // epilogue with the dropout mask of (seed, s).
-static int decoder_fwd_cell(const rfn_dims* d, int B, int s, const float* const* prm, const float* comb, float* W,
+static int decoder_fwd_cell(const rfn_dims* d, int B, int n, int s, const float* const* prm, const float* comb, float* W,
                             const DecoderLayout& Lo, const GemmCtx& gx, RfnSeed seed, void* st) {
     const DecStepBufs b(d, B, s, W, Lo);
     const long BR = (long)B * d->R;
-    return decoder_cell_core(d, B, prm, comb, W + Lo.Pd, W + Lo.Ud, 1, b.h, b.c, b.h + BR, b.c + BR, b.hp, b.al, b.z, b.g, gx, seed, s, st);
+    return decoder_cell_core(d, B, prm, comb, W + Lo.Pd, W + Lo.Ud, n, b.h, b.c, b.h + BR, b.c + BR, b.hp, b.al, b.z, b.g, gx, seed, s, st);
 }
 // its three-launch form prepared instead of launched; false: the cell GEMM cannot take the step
 static bool decoder_fwd_cell_prepare(const rfn_dims* d, int B, int s, const float* const* prm, const float* comb, float* W,
@@ -127,28 +136,31 @@ static bool decoder_fwd_cell_prepare(const rfn_dims* d, int B, int s, const floa
 // compute the same products for one step's rows with the same unsplit k order, so log-probs of the same tokens are
 // bit-identical across all three whatever the batch size (split-K choices depend on the row count).  The per-step
 // products (h_2_att_h, h2h + z2h) have the same shape everywhere and take the same split.
-static int decoder_fwd_begin(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* h0,
+static int decoder_fwd_begin(const rfn_dims* d, int B, int n, const float* const* prm, const float* comb, const float* h0,
                              const float* c0, float* W, const DecoderLayout& Lo, void* st) {
     const PIdx P(d);
-    const int R = d->R, A = d->A, T2 = d->T2;
+    const int R = d->R, A = d->A, T2 = d->T2, Bc = B / n;   // the projections: once per image
     const GemmCtx gx_whole{st, nullptr, 0, d->gemm_flags};
-    RFN_TRY(gemm1(T2 * B, A, seg_lin(comb, R, prm[P.dec(6)], R, R, prm[P.dec(7)]), W + Lo.Pd, A, 0, gx_whole));
+    RFN_TRY(gemm1(T2 * Bc, A, seg_lin(comb, R, prm[P.dec(6)], R, R, prm[P.dec(7)]), W + Lo.Pd, A, 0, gx_whole));
     if (dec_hoisted(d)) {   // U = comb . W_z^T, no bias: z2h of every thought vector, once (misc/LSTMSoftAttentionCore.py:78-81)
         const int GD = gate_width(d->decoder_maxout, R);
-        RFN_TRY(gemm1(T2 * B, GD, seg_lin(comb, R, prm[P.dec(4)], R, R, nullptr), W + Lo.Ud, GD, 0, gx_whole));
+        RFN_TRY(gemm1(T2 * Bc, GD, seg_lin(comb, R, prm[P.dec(4)], R, R, nullptr), W + Lo.Ud, GD, 0, gx_whole));
     }
     return mem_batch({{W + Lo.hd, h0, (long)B * R}, {W + Lo.cd, c0, (long)B * R}}, st);
 }
 
-extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
-                               const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
-                               void* ws, size_t ws_bytes, int train, uint64_t seed_arg, void* st) {
+extern "C" int rfn_decoder_fwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
+                                  void* ws, size_t ws_bytes, int train, uint64_t seed_arg, int rows_per_image, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
     if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
-    const DecoderLayout Lo = decoder_layout(d, B, S, train);
+    if (n > 1 && !log_prob) return RFN_ERR_ARG;   // the logits-only form is found through rfn_decoder_logits: one row per image
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     const PIdx P(d);
     const int R = d->R, E = d->E, V1 = d->V1;
@@ -156,12 +168,12 @@ extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* con
     float* W = (float*)ws;
     const GemmCtx gx{st, W + Lo.gws, GEMM_WS_FLOATS * sizeof(float), d->gemm_flags};
     const GemmCtx gx_whole{st, nullptr, 0, d->gemm_flags};
-    RFN_TRY(decoder_fwd_begin(d, B, prm, comb, h0, c0, W, Lo, st));
+    RFN_TRY(decoder_fwd_begin(d, B, n, prm, comb, h0, c0, W, Lo, st));
     // all token embeddings and their i2h projections in one go (teacher forcing: ids are known)
     RFN_TRY(rfn_embed_fwd(prm[P.embed()], E, V1, ids, B, ld_ids, 1, S * B, W + Lo.xs, E, st));
     RFN_TRY(gemm1(S * B, GD, seg_lin(W + Lo.xs, E, prm[P.dec(0)], E, E, prm[P.dec(1)]), W + Lo.gd, GD, 0, gx_whole));
     if (dec_hoisted(d)) {   // the S cell steps, two launches each (rfn_deccell.hip)
-        for (int s = 0; s < S; ++s) RFN_TRY(decoder_fwd_cell(d, B, s, prm, comb, W, Lo, gx, seed, st));
+        for (int s = 0; s < S; ++s) RFN_TRY(decoder_fwd_cell(d, B, n, s, prm, comb, W, Lo, gx, seed, st));
     } else {   // three-launch form: one persistent launch (rfn_chain.hip) when every step takes the fused form, else step by step
         std::vector<ChainStep> steps((size_t)S);
         bool fused = true;
@@ -169,13 +181,18 @@ extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* con
         if (fused) {
             RFN_TRY(rfn_chain_run(steps.data(), S, chain_persist(d, RFN_PATH_OPT_PERSIST_DEC_FWD), (uint32_t*)(W + Lo.bar), st));
         } else {
-            for (int s = 0; s < S; ++s) RFN_TRY(decoder_fwd_cell(d, B, s, prm, comb, W, Lo, gx, seed, st));
+            for (int s = 0; s < S; ++s) RFN_TRY(decoder_fwd_cell(d, B, 1, s, prm, comb, W, Lo, gx, seed, st));
         }
     }
     // logits of all steps, then log-softmax written in the reference's (B, S, V+1) layout
     RFN_TRY(gemm_logits(S * B, V1, W + Lo.hd + (long)B * R, R, prm[P.logit_w()], prm[P.logit_b()], W + Lo.logits, gx_whole));
     if (log_prob) RFN_TRY(rfn_log_softmax_fwd(W + Lo.logits, V1, S * B, V1, B, (long)S * V1, V1, log_prob, st));
     return RFN_OK;      // log_prob == NULL: the logits stay in the workspace for rfn_xe_logits_fwd (rfn_decoder_logits)
+}
+extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                               const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
+                               void* ws, size_t ws_bytes, int train, uint64_t seed_arg, void* st) {
+    return rfn_decoder_fwd_ex(d, B, S, prm, comb, h0, c0, ids, ld_ids, log_prob, ws, ws_bytes, train, seed_arg, 1, st);
 }
 
 extern "C" float* rfn_decoder_logits(const rfn_dims* d, int B, int S, int train, void* ws) {
@@ -187,25 +204,36 @@ extern "C" float* rfn_decoder_logits(const rfn_dims* d, int B, int S, int train,
 // step s may be drawn from the distribution of step s-1, so the host interleaves its draws with the steps.  begin +
 // S steps leave the workspace and log_prob exactly as rfn_decoder_fwd on the final ids does (bit for bit), so
 // rfn_decoder_bwd runs on it unchanged -- the sampled pass IS the differentiated pass, nothing is computed twice.
-extern "C" int rfn_decoder_fwd_begin(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
-                                     const float* h0, const float* c0, void* ws, size_t ws_bytes, int train, void* st) {
+int rfn_path::decoder_fwd_begin_n(const rfn_dims* d, int B, int S, int n, const float* const* prm, const float* comb,
+                                  const float* h0, const float* c0, void* ws, size_t ws_bytes, int train, void* st) {
     RFN_TRY(check_dims(d));
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    RFN_TRY(rows_per_image_ok(d, B, n));
     if (!prm || !comb || !h0 || !c0 || !ws) return RFN_ERR_ARG;
-    const DecoderLayout Lo = decoder_layout(d, B, S, train);
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
-    return decoder_fwd_begin(d, B, prm, comb, h0, c0, (float*)ws, Lo, st);
+    return decoder_fwd_begin(d, B, n, prm, comb, h0, c0, (float*)ws, Lo, st);
+}
+extern "C" int rfn_decoder_fwd_begin(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                     const float* h0, const float* c0, void* ws, size_t ws_bytes, int train, void* st) {
+    return decoder_fwd_begin_n(d, B, S, 1, prm, comb, h0, c0, ws, ws_bytes, train, st);
 }
 
 extern "C" int rfn_decoder_fwd_step(const rfn_dims* d, int B, int S, int s, const float* const* prm, const float* comb,
                                     const int64_t* ids_s, int64_t ld_ids, float* log_prob, void* ws, size_t ws_bytes,
                                     int train, uint64_t seed_arg, void* st) {
+    return decoder_fwd_step_n(d, B, S, 1, s, prm, comb, ids_s, ld_ids, log_prob, ws, ws_bytes, train, seed_arg, st);
+}
+int rfn_path::decoder_fwd_step_n(const rfn_dims* d, int B, int S, int n, int s, const float* const* prm, const float* comb,
+                                 const int64_t* ids_s, int64_t ld_ids, float* log_prob, void* ws, size_t ws_bytes,
+                                 int train, uint64_t seed_arg, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1 || s < 0 || s >= S) return RFN_ERR_SHAPE;
+    RFN_TRY(rows_per_image_ok(d, B, n));
     if (!prm || !comb || !ids_s || !log_prob || !ws) return RFN_ERR_ARG;
-    const DecoderLayout Lo = decoder_layout(d, B, S, train);
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     const PIdx P(d);
     const int R = d->R, E = d->E, V1 = d->V1;
@@ -217,7 +245,7 @@ extern "C" int rfn_decoder_fwd_step(const rfn_dims* d, int B, int S, int s, cons
     float* lg = W + Lo.logits + (long)s * B * V1;
     RFN_TRY(rfn_embed_fwd(prm[P.embed()], E, V1, ids_s, B, ld_ids, 1, B, xs, E, st));
     RFN_TRY(gemm1(B, GD, seg_lin(xs, E, prm[P.dec(0)], E, E, prm[P.dec(1)]), W + Lo.gd + (long)s * B * GD, GD, 0, gx_whole));
-    RFN_TRY(decoder_fwd_cell(d, B, s, prm, comb, W, Lo, gx, seed, st));
+    RFN_TRY(decoder_fwd_cell(d, B, n, s, prm, comb, W, Lo, gx, seed, st));
     RFN_TRY(gemm_logits(B, V1, W + Lo.hd + (long)(s + 1) * B * R, R, prm[P.logit_w()], prm[P.logit_b()], lg, gx_whole));
     return rfn_log_softmax_fwd(lg, V1, B, V1, B, (long)S * V1, V1, log_prob + (long)s * V1, st);
 }
@@ -227,7 +255,7 @@ namespace {
 struct DecBwd {
     const rfn_dims* d;
     const PIdx P;
-    int B, S, R, A, E, T2, V1, GD;
+    int B, n, Bc, S, R, A, E, T2, V1, GD;   // n rows per image, Bc = B / n images (rfn.h "multi-sample self-critical")
     long BR, BA;
     const float* const* prm;
     const float* comb;
@@ -262,12 +290,13 @@ struct DecBwd {
             cell_lstm_bwd(kb2, gd + (long)(s - 1) * B * GD, GD, cd + (s - 1) * BR, R, cd + s * BR, R, dhe + (s - 1) * BR, R,
                           dc, R, dc, R, OFF_DECODER + (uint64_t)(s - 1));
     }
-    // the hoisted attention backward of step s from that step's gate gradients: f = rfn_dec_attn_bwd (last = the stream) or
+    // the hoisted attention backward of step s from that step's gate gradients: f = rfn_dec_attn_bwd_ex (last = the stream) or
     // rfn_dec_attn_bwd_args (last = the argument block, nothing launched)
     template <class F, class Last>
     int attn_bwd_hoisted(F f, int s, Last last) const {
-        return f(W + Lo.Pd, A, BA, W + Lo.hpd + s * BA, prm[P.dec(10)], W + Lo.ald + (long)s * B * T2, W + Lo.Ud, GD, (long)B * GD,
-                 gd + (long)s * B * GD, GD, B, T2, A, GD, dPd, A, BA, 1, W + Lo.dhpd + s * BA, W + Lo.dwp + s * BA, last);
+        return f(W + Lo.Pd, A, (long)Bc * A, W + Lo.hpd + s * BA, prm[P.dec(10)], W + Lo.ald + (long)s * B * T2, W + Lo.Ud, GD,
+                 (long)Bc * GD, gd + (long)s * B * GD, GD, B, n, T2, A, GD, dPd, A, BA, 1, W + Lo.dhpd + s * BA, W + Lo.dwp + s * BA,
+                 last);
     }
     int attn_bwd_unhoisted(int s) const {
         return attn1_bwd(W + Lo.Pd, A, BA, W + Lo.hpd + s * BA, prm[P.dec(10)], W + Lo.ald + (long)s * B * T2, comb, R, BR, dz, R, B, T2,
@@ -307,7 +336,7 @@ int DecBwd::sweep_hoisted() const {
         if (!fused) {
             if (s < S - 1) RFN_TRY(rfn_axpby_2d(1.f, dhrec, R, 1.f, dhe + s * BR, R, B, R, st));
             RFN_TRY(lstm_bwd_of(s));
-            RFN_TRY(attn_bwd_hoisted(rfn_dec_attn_bwd, s, st));
+            RFN_TRY(attn_bwd_hoisted(rfn_dec_attn_bwd_ex, s, st));
             rfn_gemm_seg sg[2] = {seg_dx(g, GD, prm[P.dec(2)], R, GD), seg_dx(dhp, A, prm[P.dec(8)], R, A)};
             RFN_TRY(gemm_segs(B, R, 2, sg, dhrec, R, 0, gx));
             continue;
@@ -319,7 +348,7 @@ int DecBwd::sweep_hoisted() const {
         RFN_TRY(attn_bwd_hoisted(rfn_dec_attn_bwd_args, s, &da));
         const int rc = rfn_cg_launch_with_rows(px, da, B, st);
         if (rc == RFN_ERR_UNSUPPORTED) {   // shapes the fused grid does not take: the same two bodies as two launches
-            RFN_TRY(attn_bwd_hoisted(rfn_dec_attn_bwd, s, st));
+            RFN_TRY(attn_bwd_hoisted(rfn_dec_attn_bwd_ex, s, st));
             RFN_TRY(rfn_cg_launch(px, st));
         } else {
             RFN_TRY(rc);
@@ -397,16 +426,19 @@ int DecBwd::sweep_unhoisted() const {
 // and d z2h.bias is copied from d h2h.bias (b_z enters every step's gates as b_h2h does: the same column sums).
 int DecBwd::tail(bool hoisted) const {
     float* dUd = W + Lo.dUd;
+    float* dPi = n > 1 ? W + Lo.dPi : dPd;   // d Pd per image
     RFN_TRY(mem_batch({{d_h0, dhrec, BR}, {d_c0, dc, BR}, {grd[P.dec(11)], nullptr, 1}}, st));
     if (hoisted) {   // d U = sum_s alpha_s (x) d gates_s; d thoughts = dPd . W_att + dU . W_z (one product, two K segments)
-        RFN_TRY(rfn_dec_du(W + Lo.ald, gd, S, B, T2, GD, dUd, GD, (long)B * GD, st));
-        rfn_gemm_seg sg[2] = {seg_dx(dPd, A, prm[P.dec(6)], R, A), seg_dx(dUd, GD, prm[P.dec(4)], R, GD)};
-        RFN_TRY(gemm_segs(T2 * B, R, 2, sg, d_comb, R, 0, gx));
+        // n rows per image: dU sums them (rfn_dec_du_ex), the per-row d Pd slabs are summed onto the image (j ascending) first
+        RFN_TRY(rfn_dec_du_ex(W + Lo.ald, gd, S, B, T2, GD, n, dUd, GD, (long)Bc * GD, st));
+        if (n > 1) RFN_TRY(rfn_rowgroup_sum(dPd, A, n, dPi, A, (long)T2 * Bc, A, st));
+        rfn_gemm_seg sg[2] = {seg_dx(dPi, A, prm[P.dec(6)], R, A), seg_dx(dUd, GD, prm[P.dec(4)], R, GD)};
+        RFN_TRY(gemm_segs(T2 * Bc, R, 2, sg, d_comb, R, 0, gx));
     } else {         // the sweep accumulated the attention's share of d thoughts; add the projection's (shared by all steps)
         RFN_TRY(gemm1(T2 * B, R, seg_dx(dPd, A, prm[P.dec(6)], R, A), d_comb, R, 1, gx));
     }
-    RFN_TRY(gemm_dw(A, R, grd[P.dec(6)], R, grd[P.dec(7)], dPd, A, comb, R, T2 * B, gx));
-    if (hoisted) RFN_TRY(gemm_dw(GD, R, grd[P.dec(4)], R, nullptr, dUd, GD, comb, R, T2 * B, gx));   // d z2h.weight = dU^T . thoughts
+    RFN_TRY(gemm_dw(A, R, grd[P.dec(6)], R, grd[P.dec(7)], dPi, A, comb, R, T2 * Bc, gx));
+    if (hoisted) RFN_TRY(gemm_dw(GD, R, grd[P.dec(4)], R, nullptr, dUd, GD, comb, R, T2 * Bc, gx));   // d z2h.weight = dU^T . thoughts
     RFN_TRY(rfn_colsum_f32(W + Lo.dwp, A, S * B, A, grd[P.dec(10)], 0, st));
     RFN_TRY(gemm_dw(A, R, grd[P.dec(8)], R, grd[P.dec(9)], W + Lo.dhpd, A, hd, R, S * B, gx));
     RFN_TRY(gemm_dw(GD, R, grd[P.dec(2)], R, grd[P.dec(3)], gd, GD, hd, R, S * B, gx));
@@ -423,17 +455,26 @@ extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* con
                                const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids,
                                const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0,
                                float* d_c0, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg, void* st) {
+    return rfn_decoder_bwd_ex(d, B, S, prm, comb, h0, c0, ids, ld_ids, log_prob, d_log_prob, d_comb, d_h0, d_c0, grd, ws, ws_bytes,
+                              seed_arg, 1, st);
+}
+extern "C" int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids,
+                                  const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0, float* d_c0,
+                                  float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg, int rows_per_image, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1 || S < 1) return RFN_ERR_SHAPE;
-    if (!prm || !comb || !ids || (!log_prob != !d_log_prob) || !d_comb || !d_h0 || !d_c0 || !grd || !ws)
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !ids || (!log_prob != !d_log_prob) || !d_comb || !d_h0 || !d_c0 || !grd || !ws || (n > 1 && !log_prob))
         return RFN_ERR_ARG;
     (void)h0; (void)c0;
-    const DecoderLayout Lo = decoder_layout(d, B, S, 1);
+    const DecoderLayout Lo = decoder_layout(d, B, S, 1, n);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     float* W = (float*)ws;
-    DecBwd c{d, PIdx(d), B, S, d->R, d->A, d->E, d->T2, d->V1, gate_width(d->decoder_maxout, d->R), (long)B * d->R, (long)B * d->A,
+    DecBwd c{d, PIdx(d), B, n, B / n, S, d->R, d->A, d->E, d->T2, d->V1, gate_width(d->decoder_maxout, d->R), (long)B * d->R, (long)B * d->A,
              prm, comb, ids, ld_ids, d_comb, d_h0, d_c0, grd, W, Lo, seed, st, GemmCtx{},
              W + Lo.hd, W + Lo.cd, W + Lo.gd, W + Lo.dhe, W + Lo.dhrec, W + Lo.dc, W + Lo.dz, W + Lo.dPd};
     RFN_TRY(phase_gemm(d, W, Lo.gws, Lo.tk, true, st, &c.gx));

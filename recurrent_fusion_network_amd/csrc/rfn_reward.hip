@@ -586,6 +586,34 @@ __global__ void rw_reward_k(const double* __restrict__ cider, double cider_weigh
     if (out64) out64[g] = v;
 }
 
+// ---- the grouped reward (rfn.h "multi-sample self-critical"): row r = k * n + j is draw j of image k; the baseline of a draw is
+// the mean of the image's other n - 1 scores, summed from 0.0 in ascending order and divided once; then rw_reward_k's mix
+__device__ __forceinline__ double rw_loo_diff(const double* __restrict__ s, long stride, int r, int n, int baseline) {
+#pragma clang fp contract(off)
+    const double mine = s[(long)r * stride];
+    if (!baseline) return mine;
+    const int k0 = r - r % n;
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i)
+        if (k0 + i != r) sum = sum + s[(long)(k0 + i) * stride];
+    const double base = sum / (double)(n - 1);
+    return mine - base;
+}
+__global__ void rw_reward_group_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu,
+                                  double bleu4_weight, int B, int n, int T, int baseline, float* __restrict__ out,
+                                  double* __restrict__ out64) {
+#pragma clang fp contract(off)
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long)B * T) return;
+    const int r = (int)(g / T);
+    const double sb = bleu ? rw_loo_diff(bleu + 3, RW_N, r, n, baseline) : 0.0;
+    const double sc = cider ? rw_loo_diff(cider, 1, r, n, baseline) : 0.0;
+    const double tb = sb * bleu4_weight, tc = sc * cider_weight;
+    const double v = (tb + tc) + 0.0;
+    if (out) out[g] = (float)v;
+    if (out64) out64[g] = v;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------
 namespace {
 const size_t kAlign = 256;
@@ -805,6 +833,17 @@ extern "C" int rfn_scst_reward_mix(const double* cider, double cider_weight, con
     const long n = (long)B * T;
     rw_reward_k<<<rfn_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, T, use_baseline, out,
                                                                    out64);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+extern "C" int rfn_scst_reward_group(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int n,
+                                     int T, int baseline, float* out, double* out64, void* stream) {
+    if (B < 1 || T < 1 || n < 1 || B % n || (baseline != 0 && baseline != 1) || (baseline == 1 && n == 1)) return RFN_ERR_SHAPE;
+    if ((!cider && !bleu) || (!out && !out64)) return RFN_ERR_ARG;
+    const long cnt = (long)B * T;
+    rw_reward_group_k<<<rfn_cdiv(cnt, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, n, T, baseline,
+                                                                          out, out64);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -192,18 +192,25 @@ class _DecoderFn(torch.autograd.Function):
     probability ss_prob by a draw from the distribution the step just produced.  The step-wise pass leaves the
     workspace exactly as the batched pass on the final ids would (bit for bit), so backward is the same call: the pass
     that is sampled IS the pass that is differentiated -- dropout masks included -- and nothing is computed twice.  No
-    host read-back: the draw is made for every row and kept where the row's coin says so."""
+    host read-back: the draw is made for every row and kept where the row's coin says so.
+
+    n > 1 (rfn.h "multi-sample self-critical"): the B rows are n draws per image, image-major; comb and its gradient are
+    (T2, B / n, R), h0 / c0 stay per row.  n = 1 is the calls and the bits of the plain entry points, which forward to these."""
 
     @staticmethod
-    def forward(ctx, model, save_bwd, drop, seed, ids, comb, h0, c0, ss_prob, inv_temp, *params):
+    def forward(ctx, model, save_bwd, drop, seed, ids, comb, h0, c0, ss_prob, inv_temp, n, *params):
         d = model._dims_for(drop)
         train = bool(save_bwd)
         B, S = ids.shape
         dev = comb.device
+        n = int(n)
+        if n < 1 or B % n or comb.size(1) * n != B or h0.size(0) != B or c0.size(0) != B:
+            raise N.RfnError('%d decoder rows, %d rows per image: comb holds %d images, h0 / c0 %d / %d rows'
+                             % (B, n, comb.size(1), h0.size(0), c0.size(0)))
         comb, h0, c0 = comb.contiguous(), h0.contiguous(), c0.contiguous()
         ids = ids.contiguous()
         table = model._param_table(params, model._decoder_slots)
-        ws_bytes = N.lib.rfn_decoder_ws_bytes(C.byref(d), B, S, int(train))
+        ws_bytes = N.lib.rfn_decoder_ws_bytes_ex(C.byref(d), B, S, int(train), n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         log_prob = torch.empty(B, S, d.V1, device=dev)
         if ss_prob > 0.0 and S > 1:
@@ -214,18 +221,18 @@ class _DecoderFn(torch.autograd.Function):
                 r = torch.rand(2, S, B, device=dev)
             elif tuple(r.shape) != (2, S, B) or r.device != dev:
                 raise N.RfnError('scheduled-sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S, B)))
-            N.check(N.lib.rfn_decoder_fwd_sampled(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
-                                                  ids.data_ptr(), ids.stride(0), float(ss_prob), float(inv_temp),
-                                                  r[0].data_ptr(), r[1].data_ptr(), log_prob.data_ptr(), ws.data_ptr(),
-                                                  ws_bytes, int(train), seed, N.stream_ptr()), 'rfn_decoder_fwd_sampled')
+            N.check(N.lib.rfn_decoder_fwd_sampled_ex(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                                     ids.data_ptr(), ids.stride(0), float(ss_prob), float(inv_temp),
+                                                     r[0].data_ptr(), r[1].data_ptr(), log_prob.data_ptr(), ws.data_ptr(),
+                                                     ws_bytes, int(train), seed, n, N.stream_ptr()), 'rfn_decoder_fwd_sampled')
             if getattr(model, '_trace_ss', False):
                 model._ss_ids = ids.clone()      # test hook: the token matrix the pass ended up feeding
         else:
-            N.check(N.lib.rfn_decoder_fwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
-                                          ids.data_ptr(), ids.stride(0), log_prob.data_ptr(), ws.data_ptr(), ws_bytes,
-                                          int(train), seed, N.stream_ptr()), 'rfn_decoder_fwd')
+            N.check(N.lib.rfn_decoder_fwd_ex(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                             ids.data_ptr(), ids.stride(0), log_prob.data_ptr(), ws.data_ptr(), ws_bytes,
+                                             int(train), seed, n, N.stream_ptr()), 'rfn_decoder_fwd')
         if train:
-            ctx.model, ctx.seed, ctx.B, ctx.S, ctx.drop = model, seed, B, S, drop
+            ctx.model, ctx.seed, ctx.B, ctx.S, ctx.drop, ctx.n = model, seed, B, S, drop, n
             ctx.ids, ctx.params, ctx.consumed, ctx.snapshot = ids, params, False, None
             ctx.save_for_backward(comb, h0, c0, log_prob, ws)     # ws: freed with the graph (see _PrefixFn.forward)
         ctx.mark_non_differentiable(ids)
@@ -249,20 +256,20 @@ class _DecoderFn(torch.autograd.Function):
             # second backward over the same graph: recompute phase 2 first (see _PrefixFn.backward), log-probs included,
             # so the pass differentiated is self-consistent at the current weights
             log_prob = torch.empty_like(log_prob)
-            N.check(N.lib.rfn_decoder_fwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
-                                          ctx.ids.data_ptr(), ctx.ids.stride(0), log_prob.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), 1, ctx.seed, N.stream_ptr()),
+            N.check(N.lib.rfn_decoder_fwd_ex(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                             ctx.ids.data_ptr(), ctx.ids.stride(0), log_prob.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), 1, ctx.seed, ctx.n, N.stream_ptr()),
                     'rfn_decoder_fwd (recompute)')
         elif getattr(model, 'retain_activations', False):
             ctx.snapshot = ws.clone()
         ctx.consumed = True
-        N.check(N.lib.rfn_decoder_bwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
-                                      ctx.ids.data_ptr(), ctx.ids.stride(0), log_prob.data_ptr(),
-                                      d_log_prob.data_ptr(), d_comb.data_ptr(), d_h0.data_ptr(), d_c0.data_ptr(),
-                                      gtable, ws.data_ptr(), ws.numel(), ctx.seed, N.stream_ptr()),
+        N.check(N.lib.rfn_decoder_bwd_ex(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                         ctx.ids.data_ptr(), ctx.ids.stride(0), log_prob.data_ptr(),
+                                         d_log_prob.data_ptr(), d_comb.data_ptr(), d_h0.data_ptr(), d_c0.data_ptr(),
+                                         gtable, ws.data_ptr(), ws.numel(), ctx.seed, ctx.n, N.stream_ptr()),
                 'rfn_decoder_bwd')
         model._bucket_done('decoder', flats['decoder'])
-        return (None, None, None, None, None, d_comb, d_h0, d_c0, None, None) + (None,) * len(ctx.params)
+        return (None, None, None, None, None, d_comb, d_h0, d_c0, None, None, None) + (None,) * len(ctx.params)
 
 
 class _DecoderLossFn(torch.autograd.Function):
@@ -602,17 +609,18 @@ class RecurrentFusionModel(nn.Module):
             self._prefix_cache = ([weakref.ref(t) for t in ins], stamp, tuple(o.detach() for o in out))
         return out
 
-    def _decode_teacher_forced(self, ids, comb, h, c, drop, seed, ss_prob=0.0):
+    def _decode_teacher_forced(self, ids, comb, h, c, drop, seed, ss_prob=0.0, n=1):
         params = self._params_of(self._decoder_slots)
-        return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids, comb, h, c, float(ss_prob), 1.0,
+        return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids, comb, h, c, float(ss_prob), 1.0, n,
                                 *params)[0]
 
-    def _decode_sampled(self, comb, h, c, drop, seed, steps, inv_temp):
+    def _decode_sampled(self, comb, h, c, drop, seed, steps, inv_temp, n=1):
         """Free-running multinomial decode as ONE step-wise pass of the training decoder (every row's next token is
-        drawn from the distribution the step just produced): -> (log_prob (B, steps, V+1), ids (B, steps) fed)."""
+        drawn from the distribution the step just produced): -> (log_prob (B, steps, V+1), ids (B, steps) fed).
+        n > 1: h, c hold n rows per image, comb one (rfn.h "multi-sample self-critical")."""
         params = self._params_of(self._decoder_slots)
         ids0 = torch.zeros(h.size(0), steps, dtype=torch.long, device=h.device)     # column 0 = BOS
-        return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids0, comb, h, c, 1.0, float(inv_temp),
+        return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids0, comb, h, c, 1.0, float(inv_temp), n,
                                 *params)
 
     def _step_seed(self, train):
@@ -803,7 +811,37 @@ class RecurrentFusionModel(nn.Module):
             out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp)
         return (*out, reason_pred)
 
-    def _sample_replayed(self, comb, h, c, train, seed, want_grad, temperature, force):
+    def sample_group(self, fc_feats, att_feats, n, opt={}):
+        """The RL trainer's sampled pass (train_rl.py:160, misc/RecurrentFusionModel.py:623-631) with n draws per image ->
+        (seq (B*n, <= S), seqLogprobs, logprobs_all, reason_pred) with rows image-major (row k * n + j is draw j of image k) and
+        reason_pred per image.  Stages I and II run once per image; ONE decoder node carries the n rows of every image, reads
+        the image's thought vectors and sums their gradient back (rfn.h "multi-sample self-critical").  Works under grad and
+        under no_grad.  opt: 'temperature', and 'force_ids' (B*n, S) to replay given tokens teacher-forced; every other
+        decoding key is refused.  n = 1 is sample(..., {'sample_max': 0}) bit for bit.  The uniforms hook `_ss_uniforms` is
+        (2, S+1, B*n)."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('sample_group draws n >= 1 captions per image (got %d)' % n)
+        bad = sorted(k for k in opt if k not in ('temperature', 'force_ids'))
+        if bad:
+            raise ValueError('sample_group is the differentiated multinomial pass: it takes temperature and force_ids, not %s'
+                             % ', '.join(map(repr, bad)))
+        force = opt.get('force_ids', None)
+        B = self._check_inputs(fc_feats, att_feats)
+        if force is not None and (force.dim() != 2 or force.size(0) != B * n or force.size(1) < self.seq_length):
+            raise ValueError('force_ids must be (%d, >= %d), got %s' % (B * n, self.seq_length, tuple(force.shape)))
+        if n > 1 and int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
+            raise N.RfnError('n draws per image need the hoisted decoder cell (path_flags select another form)')
+        train = bool(self.training)
+        seed = self._step_seed(train)
+        want_grad = torch.is_grad_enabled()
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
+        if n > 1:      # the state fans out to the rows (autograd sums it back); the thought vectors stay per image
+            h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
+        out = self._sample_replayed(comb, h, c, train, seed, want_grad, opt.get('temperature', 1.0), force, n)
+        return (*out, list(reason.unbind(0)))
+
+    def _sample_replayed(self, comb, h, c, train, seed, want_grad, temperature, force, n=1):
         """Multinomial (:623-631) or replayed ids -> (seq, seq_lp, logp).  ONE pass of the training decoder is both the pass
         that is sampled and, under grad, the pass that is differentiated (train_rl.py:160-166): step-wise with a device-side
         inverse-CDF draw between steps, or -- when the ids are given -- simply teacher-forced."""
@@ -813,14 +851,14 @@ class RecurrentFusionModel(nn.Module):
                 raw = torch.zeros(B, S + 1, dtype=torch.long, device=dev)      # column t = token fed at step t
                 raw[:, 1:] = force[:, :S].to(dev)
             else:
-                logp_full, raw = self._decode_sampled(comb, h, c, train, seed, S + 1, 1.0 / float(temperature))
+                logp_full, raw = self._decode_sampled(comb, h, c, train, seed, S + 1, 1.0 / float(temperature), n)
             tok = raw[:, 1:]
             unf = torch.cumprod((tok > 0).long(), 1)                           # a row is finished after its first 0
             seq = tok * unf
             t_stop = early_exit(unf.sum(0).tolist(), S)                        # one read-back
             n_seq = t_stop - 1
             if force is not None:
-                logp = self._decode_teacher_forced(raw[:, :t_stop].contiguous(), comb, h, c, train, seed)
+                logp = self._decode_teacher_forced(raw[:, :t_stop].contiguous(), comb, h, c, train, seed, n=n)
             else:
                 logp = logp_full[:, :t_stop]
             seq_lp = logp[:, :n_seq].gather(2, tok[:, :n_seq].unsqueeze(2)).squeeze(2)

@@ -366,6 +366,49 @@ def scst_reward(scorer, gen_result, greedy_res, gts, n_refs, seq_per_img, cider_
     return out
 
 
+_GROUP_CACHE = {}
+_BASELINES = {'none': 0, 'loo': 1}
+
+
+def _group_row_img(rows, n, dev):
+    key = (rows, n, str(dev))
+    if key not in _GROUP_CACHE:
+        _GROUP_CACHE[key] = torch.tensor([r // n for r in range(rows)], dtype=torch.int32, device=dev)
+    return _GROUP_CACHE[key]
+
+
+def scst_group_reward(scorer, gen_result, gts, n_refs, n, cider_weight=1.0, baseline='loo', out64=None, bleu_scorer=None,
+                      bleu4_weight=0.0):
+    """The multi-sample self-critical reward on the device (rfn.h "multi-sample self-critical"): gen_result (B*n, T) holds n
+    draws per image, image-major (row r is a draw of image r // n, as RecurrentFusionModel.sample_group returns them); gts
+    (B, R, Tg) padded references, n_refs (B,).  The rows are scored once, then ONE launch forms the (B*n, T) float32 reward:
+    baseline 'loo': a draw's score minus the mean score of the image's other n - 1 draws (n >= 2); 'none': the score itself.
+    Weights, bleu_scorer and out64 as scst_reward.  After the first call at a shape nothing is allocated but the results and
+    nothing synchronises."""
+    if baseline not in _BASELINES:
+        raise ValueError("baseline is 'loo' or 'none', got %r" % (baseline,))
+    n = int(n)
+    rows, T = gen_result.shape
+    if n < 1 or rows % n:
+        raise ValueError('%d rows are not n = %d draws per image' % (rows, n))
+    if baseline == 'loo' and n < 2:
+        raise ValueError("the leave-one-out baseline needs n >= 2 draws per image (baseline='none' takes n = 1)")
+    if gts.shape[0] * n != rows:
+        raise ValueError('%d rows of %d draws per image need %d images of references, got %d' % (rows, n, rows // n, gts.shape[0]))
+    if scorer is None and bleu_scorer is None:
+        raise ValueError('scst_group_reward needs a CIDEr-D scorer, a BLEU-D scorer or both')
+    dev = gen_result.device
+    res = gen_result.to(torch.int64)
+    row_img = _group_row_img(rows, n, dev)
+    scores = None if scorer is None else scorer.score_ids(res, row_img, gts, n_refs)
+    bleu = None if bleu_scorer is None else bleu_scorer.score_ids(res, row_img, gts, n_refs)
+    out = torch.empty(rows, T, dtype=torch.float32, device=dev)
+    N.check(N.lib.rfn_scst_reward_group(N.ptr(scores), C.c_double(cider_weight), N.ptr(bleu),
+                                        C.c_double(0.0 if bleu is None else bleu4_weight), rows, n, T, _BASELINES[baseline],
+                                        out.data_ptr(), N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward_group')
+    return out
+
+
 _DEFAULT = {}
 
 
@@ -376,7 +419,8 @@ def default_scorer():
     return _DEFAULT['scorer']
 
 
-def _reward(model_sample, data, gen_result, opt, device, scorer, bleu_scorer):
+def _reward_terms(opt, scorer, bleu_scorer):
+    """opt's reward weights as compute_reward reads them -> (scorer, bleu_scorer, cider_weight, bleu4_weight, use_baseline)."""
     if getattr(opt, 'spice_weight', 0) > 0:
         raise NotImplementedError('the SPICE-D reward is not ported (of BLEU-D and SPICE-D only BLEU-D is); set spice_weight = 0')
     w_b = getattr(opt, 'bleu4_weight', 0)
@@ -388,6 +432,11 @@ def _reward(model_sample, data, gen_result, opt, device, scorer, bleu_scorer):
     w, base = getattr(opt, 'cider_weight', 1.0), getattr(opt, 'use_baseline', 1)
     if scorer is None and not (bleu_scorer is not None and w == 0):
         scorer = default_scorer()      # not with cider_weight == 0 beside BLEU-D: that mix needs no df pickle
+    return scorer, bleu_scorer, w, w_b, base
+
+
+def _reward(model_sample, data, gen_result, opt, device, scorer, bleu_scorer):
+    scorer, bleu_scorer, w, w_b, base = _reward_terms(opt, scorer, bleu_scorer)
     with torch.no_grad():
         greedy_res = model_sample()[0]
     B, T = gen_result.shape
@@ -414,3 +463,23 @@ def get_self_critical_reward(idx_to_word, model, fc_feats, att_feats, data, gen_
                              bleu_scorer=None):
     """get_rewards.py:132-140 (single-feature models): as get_self_critical_reward_feat_array."""
     return _reward(lambda: model.sample(fc_feats, att_feats), data, gen_result, opt, device, scorer, bleu_scorer)
+
+
+def get_self_critical_reward_group(data, gen_result, n, opt, device=False, scorer=None, bleu_scorer=None):
+    """The reward of a multi-sample self-critical step: gen_result (B*n, T) are RecurrentFusionModel.sample_group's n draws per
+    image and data['gts'] holds the B images' references.  No greedy pass: with opt.use_baseline (the default) a draw's baseline
+    is the mean score of the image's other draws, with opt.use_baseline = 0 there is none.  opt.cider_weight, opt.bleu4_weight
+    and opt.spice_weight are honoured exactly as by get_self_critical_reward_feat_array.  -> numpy (B*n, T) float64, or the
+    device (B*n, T) float32 tensor with device=True."""
+    scorer, bleu_scorer, w, w_b, base = _reward_terms(opt, scorer, bleu_scorer)
+    rows, T = gen_result.shape
+    if len(data['gts']) * int(n) != rows:
+        raise ValueError('%d rows of %d draws per image need %d images in data[\'gts\'], got %d'
+                         % (rows, n, rows // max(1, int(n)), len(data['gts'])))
+    gts, n_refs = pad_gts(data['gts'], gen_result.device)
+    how = 'loo' if base else 'none'
+    if device:
+        return scst_group_reward(scorer, gen_result, gts, n_refs, n, w, how, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
+    out64 = torch.empty(rows, T, dtype=torch.float64, device=gen_result.device)
+    scst_group_reward(scorer, gen_result, gts, n_refs, n, w, how, out64=out64, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
+    return out64.cpu().numpy()
