@@ -1223,6 +1223,45 @@ int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* para
 int rfn_scst_reward_group(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int n, int T,
                           int baseline, float* out, double* out64, void* stream);
 
+/* ---- consensus reranking (minimum-Bayes-risk decoding under CIDEr-D; off by default, the reference has none) ---------------------
+ * Of the n candidate captions of an image, keep the one that agrees most with the others under CIDEr-D (csrc/rfn_reward.hip).
+ * Inputs: cands (n_img, n, T) int64 ids; n_cand (n_img) int32, only the first n_cand[k] candidates of image k are valid (NULL:
+ * all n); weights (n_img, n) fp64 (NULL: every weight is 1); the df source, sigma, vocab and flags as rfn_ciderd_score_ex takes
+ * them (RFN_CAPTION_END_EXCLUDED is honoured).
+ *   Pairwise utility: U[k][i][j] is what rfn_ciderd_score_ex returns for the one row cands[k][i] against the single reference
+ *   cands[k][j]: the per-order clipped similarity, divided by both norms only when both are non-zero, times the Gaussian length
+ *   penalty, then ((((0 + s0) + s1) + s2) + s3) / 4 * 10, fp64 in that scorer's summation orders (both kernels run one device
+ *   function per pair).  The diagonal is computed like any other entry; U is not symmetric (min(w_h, w_r) * w_r).
+ *   df source: table mode as rfn_ciderd_score_ex, with the caller's ref_docs.  Corpus mode (table == NULL): a document is an
+ *   image, df(g) = the sum of n_cand[k] over the images whose valid candidates hold g, ref_docs = the sum of all n_cand[k] --
+ *   exactly what rfn_ciderd_score_ex computes in corpus mode when the compacted valid candidates are passed as `res` and the
+ *   candidates as `gts`.  So in both modes the mean over the valid j of U[k][i][j] is that call's score of candidate i (up to the
+ *   last rounding).  An image whose n_cand is outside [1, n] adds nothing to either sum; an image that is bad for another reason
+ *   adds its n_cand to ref_docs and nothing to df, as a bad image's rows do there.
+ *   Consensus score: c[k][i] = (sum_{j != i, j < n_cand[k]} w_j * U[k][i][j]) / (sum_{j != i} w_j), j ascending, each product, each
+ *   sum and the quotient rounded on its own (no contraction).  A weight sum of 0 (which includes n_cand[k] = 1) gives c = 0.
+ *   Pick: best[k] = the lowest i with c[k][i] equal to the maximum.
+ *   Bad inputs: a valid candidate holding an id outside [0, vocab], a negative or NaN weight on a valid candidate, n_cand[k]
+ *   outside [1, n], or (under RFN_CAPTION_END_EXCLUDED) an empty valid candidate make all of image k's c and U NaN and best[k] = -1;
+ *   other images are unaffected.  Entries of c and U at or beyond n_cand[k] are NaN.
+ *   Limits (RFN_ERR_SHAPE otherwise; rfn_consensus_ws_bytes: 0): 1 <= T <= 64, 1 <= n <= 32, 0 <= vocab <= 32767 -- the reward's,
+ *   whose n-gram packing is shared.  Checks in rfn_ciderd_score_ex's precedence: shape, then arg (unknown flag bits; cands, c,
+ *   best or ws NULL, ws not 16-B aligned), then workspace.
+ * Launches: the candidate counts, [clear the corpus df], cook the candidates once (as references), their tf-idf vectors and norms,
+ * the pairs (one workgroup per (image, candidate)), the pick (one wave per image): 5 in table mode, 6 in corpus mode.  No
+ * floating-point atomics, fixed orders: bitwise repeatable.  No allocation, no synchronisation (capturable in a graph).
+ * U: NULL or n_img * n * n doubles; c: n_img * n doubles; best: n_img int64. */
+size_t rfn_consensus_ws_bytes(int n_img, int n, int T, int corpus);
+int rfn_consensus_ciderd(const int64_t* cands, int n_img, int n, int T, const int32_t* n_cand, const double* weights,
+                         const void* table, int64_t slots, double ref_docs, int vocab, double sigma, unsigned flags, double* U,
+                         double* c, int64_t* best, void* ws, size_t ws_bytes, void* stream);
+/* The pick's gather as a launch of its own: row best[k] of image k's n rows goes to row k of the output, for each array pair
+ * given: seq (n_img, n, S) int64 -> (n_img, S), lp (n_img, n, S) f32 -> (n_img, S), p (n_img, n) f32 -> (n_img).  best[k] outside
+ * [0, n) (a bad image's -1) writes zeros.  RFN_ERR_SHAPE: n_img, n or S < 1; RFN_ERR_ARG: best NULL, no pair given, or a pair
+ * with only one side. */
+int rfn_consensus_gather(const int64_t* best, int n_img, int n, int S, const int64_t* seq_in, int64_t* seq_out, const float* lp_in,
+                         float* lp_out, const float* p_in, float* p_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

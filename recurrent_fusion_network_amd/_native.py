@@ -237,6 +237,10 @@ def _load():
         'rfn_dec_du_ex': (C.c_int, [P, P, I, I, I, I, I, P, L, L, P]),
         'rfn_rowgroup_sum': (C.c_int, [P, L, I, P, L, L, I, P]),
         'rfn_scst_reward_group': (C.c_int, [P, C.c_double, P, C.c_double, I, I, I, I, P, P, P]),
+        # consensus reranking (rfn.h)
+        'rfn_consensus_ws_bytes': (SZ, [I, I, I, I]),
+        'rfn_consensus_ciderd': (C.c_int, [P, I, I, I, P, P, P, L, C.c_double, I, C.c_double, C.c_uint, P, P, P, P, SZ, P]),
+        'rfn_consensus_gather': (C.c_int, [P, I, I, I, P, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

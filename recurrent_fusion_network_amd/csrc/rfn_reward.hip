@@ -20,6 +20,10 @@
 // Everything after the df counts is fp64 in fixed summation orders, so scores are bitwise reproducible; the only
 // atomics are the integer df counts.
 //
+// Consensus reranking (cs_, cd_pair_k; rfn.h "consensus reranking"): an image's n candidates are cooked once as its references;
+// cd_pair_k (one workgroup per (image, candidate)) fills a row of the pairwise utility with cd_pair_term, the device function
+// cd_hyp_k's reference loop runs too, and forms the leave-one-out consensus score; cs_pick_k picks and gathers.
+//
 // BLEU-D (bd_): launches of one call: refs, hyp (clip every distinct n-gram of the row against the maximum count over
 // the image's references, reduce correct[4], pick the closest reference length, write the row's four scores and its
 // integer components) and, when asked for, corpus (the same formula over the sums of the components).  Everything
@@ -221,9 +225,11 @@ __device__ __forceinline__ V rw_lookup(const uint64_t* __restrict__ ref_key, con
 // ---- CIDEr-D reference vectors: one thread per (image, ref, n) -------------------------------------------
 __global__ void cd_ref_vec_k(const int32_t* __restrict__ n_refs, const int32_t* __restrict__ img_bad, int n_img, int max_refs,
                              int Tg, const uint64_t* __restrict__ rkey, const int32_t* __restrict__ rcnt,
-                             double* __restrict__ rval, double* __restrict__ rnorm, CdDf df, double ref_docs) {
+                             double* __restrict__ rval, double* __restrict__ rnorm, CdDf df, double ref_docs,
+                             const double* __restrict__ ref_docs_dev /* NULL, or where the count lives (consensus, corpus mode) */) {
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (long)n_img * max_refs * RW_N) return;
+    if (ref_docs_dev) ref_docs = *ref_docs_dev;
     const int n = (int)(g % RW_N);
     const long ij = g / RW_N;
     const int i = (int)(ij / max_refs), j = (int)(ij % max_refs);
@@ -239,6 +245,36 @@ __global__ void cd_ref_vec_k(const int32_t* __restrict__ n_refs, const int32_t* 
         nrm += v * v;
     }
     rnorm[g] = sqrt(nrm);
+}
+
+// ---- CIDEr-D, one (hypothesis, reference) pair: what cd_hyp_k's reference loop and cd_pair_k's candidate loop both run ----
+// Block-wide.  key: the caller's n-gram (thread t owns slot t of the hypothesis, T ids wide); hk / hv: the hypothesis' keys and
+// tf-idf values (LDS), hnorm its four norms, hlen its bigram count; ref_*: the cooked reference (Tg ids wide).  Thread t < RW_N
+// returns the order-(t + 1) term: the clipped similarity, divided by both norms when both are non-zero, times the Gaussian length
+// penalty, added to `a` (cd_hyp_k's running sum over references; 0.0 gives the term itself); the others return `a`.  All threads
+// must call it, and pass a barrier before the next call.
+__device__ __forceinline__ double cd_pair_term(double a, uint64_t key, int T, const uint64_t* hk, const double* hv, const double* hnorm, int hlen,
+                                               const uint64_t* __restrict__ ref_key, const double* __restrict__ ref_val,
+                                               const double* __restrict__ ref_norm, int ref_words, int Tg, double sigma, uint64_t* rk,
+                                               double* rv, double* contrib) {
+    const int t = threadIdx.x;
+    const double vr = rw_lookup(ref_key, ref_val, Tg, key, t / T, rk, rv);
+    if (key) {
+        const double vh = hv[t];
+        contrib[t] = (vr < vh ? vr : vh) * vr;
+    }
+    __syncthreads();
+    if (t < RW_N) {   // the reference's order: n-grams of one n in first-occurrence order
+        double s = 0.0;
+        for (int p = 0; p < T; ++p)
+            if (hk[t * T + p]) s += contrib[t * T + p];
+        const double nh = hnorm[t], nrf = ref_norm[t];
+        if (nh != 0.0 && nrf != 0.0) s /= nh * nrf;
+        const double delta = (double)(hlen - (ref_words > 1 ? ref_words - 1 : 0));
+        s *= exp(-(delta * delta) / (2.0 * sigma * sigma));
+        a += s;
+    }
+    return a;
 }
 
 // ---- CIDEr-D hypotheses: one workgroup per score row ---------------------------------------------------
@@ -277,26 +313,10 @@ __global__ __launch_bounds__(RW_THREADS) void cd_hyp_k(const int64_t* __restrict
         hnorm[t] = sqrt(s);
     }
     const int hlen = words > 1 ? words - 1 : 0;
-    const int n = t / T;
     for (int j = 0; j < nr; ++j) {
         const long ij = (long)i * max_refs + j;
-        const double vr = rw_lookup(rkey + ij * Sg, rval + ij * Sg, Tg, key, n, rk, rv);
-        if (key) {
-            const double vh = hv[t];
-            contrib[t] = (vr < vh ? vr : vh) * vr;
-        }
-        __syncthreads();
-        if (t < RW_N) {
-            double s = 0.0;
-            for (int p = 0; p < T; ++p)
-                if (hk[t * T + p]) s += contrib[t * T + p];
-            const double nh = hnorm[t], nrf = rnorm[ij * RW_N + t];
-            if (nh != 0.0 && nrf != 0.0) s /= nh * nrf;
-            const int rw = rwords[ij];
-            const double delta = (double)(hlen - (rw > 1 ? rw - 1 : 0));
-            s *= exp(-(delta * delta) / (2.0 * sigma * sigma));
-            a += s;
-        }
+        a = cd_pair_term(a, key, T, hk, hv, hnorm, hlen, rkey + ij * Sg, rval + ij * Sg, rnorm + ij * RW_N, rwords[ij], Tg, sigma, rk,
+                         rv, contrib);
         __syncthreads();
     }
     if (t < RW_N) acc[t] = a;
@@ -614,6 +634,141 @@ __global__ void rw_reward_group_k(const double* __restrict__ cider, double cider
     if (out64) out64[g] = v;
 }
 
+// ---- consensus (minimum-Bayes-risk) reranking (rfn.h "consensus reranking") ---------------------------------------------------
+// The n candidates of an image are cooked ONCE as that image's "references" (rw_refs_k, cd_ref_vec_k); cd_pair_k then walks
+// candidate i against every candidate j with cd_pair_term, the loop body of cd_hyp_k, so a pair is cd_hyp_k's bits.
+//
+// cs_prep_k (one workgroup): the per-image candidate counts the cooking reads (n where the caller passed none), the score rows of
+// the corpus df (entry k * n + j points at image k when candidate j is valid, at -1 otherwise, so rw_refs_k<true> adds n_cand[k]
+// per image) and their number, the corpus document count.  Integer counting only.
+__global__ __launch_bounds__(RW_THREADS) void cs_prep_k(const int32_t* __restrict__ n_cand, int n_img, int n, int32_t* __restrict__ nc_eff,
+                                                        int32_t* __restrict__ row_img, double* __restrict__ ref_docs) {
+    __shared__ int total;
+    const int t = threadIdx.x;
+    if (t == 0) total = 0;
+    __syncthreads();
+    for (long x = t; x < (long)n_img * n; x += RW_THREADS) {
+        const int k = (int)(x / n), j = (int)(x - (long)k * n);
+        const int nc = n_cand ? n_cand[k] : n;
+        const bool ok = nc >= 1 && nc <= n;
+        row_img[x] = (ok && j < nc) ? k : -1;
+        if (j == 0) {
+            nc_eff[k] = nc;
+            if (ok) atomicAdd(&total, nc);
+        }
+    }
+    __syncthreads();
+    if (t == 0) *ref_docs = (double)total;
+}
+
+// c[i] = (sum_{j != i} w_j U[i][j]) / (sum_{j != i} w_j), j ascending, every product, sum and the quotient rounded on its own
+__device__ __forceinline__ double cs_leave_one_out(const double* u, const double* __restrict__ w, int nc, int i) {
+#pragma clang fp contract(off)
+    double num = 0.0, den = 0.0;
+    for (int j = 0; j < nc; ++j) {
+        if (j == i) continue;
+        const double wj = w ? w[j] : 1.0;
+        const double prod = wj * u[j];
+        num = num + prod;
+        den = den + wj;
+    }
+    return den == 0.0 ? 0.0 : num / den;
+}
+
+// One workgroup per (image k, candidate i): row i of U[k] and c[k][i].  Grid choice: DESIGN.md section 9.
+__global__ __launch_bounds__(RW_THREADS) void cd_pair_k(const int32_t* __restrict__ n_cand, const int32_t* __restrict__ img_bad, int n,
+                                                        int T, const uint64_t* __restrict__ rkey, const double* __restrict__ rval,
+                                                        const double* __restrict__ rnorm, const int32_t* __restrict__ rwords,
+                                                        const double* __restrict__ weights, double sigma, double* __restrict__ U,
+                                                        double* __restrict__ c) {
+    __shared__ uint64_t hk[RW_THREADS], rk[RW_THREADS];
+    __shared__ double hv[RW_THREADS], rv[RW_THREADS], contrib[RW_THREADS];
+    __shared__ double sn[RW_N], su[RW_MAX_REFS];
+    __shared__ int swbad;
+    const int k = blockIdx.x / n, i = blockIdx.x - k * n, t = threadIdx.x, S = RW_N * T;
+    const long ki = (long)k * n + i;
+    const double nan = __builtin_nan("");
+    const int nc = n_cand[k];
+    int bad = img_bad[k];   // block-uniform; covers n_cand outside [1, n]
+    if (!bad && weights) {
+        if (t == 0) swbad = 0;
+        __syncthreads();
+        if (t < nc && !(weights[(long)k * n + t] >= 0.0)) swbad = 1;   // negative or NaN
+        __syncthreads();
+        bad = swbad;
+    }
+    if (bad || i >= nc) {
+        if (U)
+            for (int j = t; j < n; j += RW_THREADS) U[ki * n + j] = nan;
+        if (t == 0) c[ki] = nan;
+        return;
+    }
+    uint64_t key = 0;
+    if (t < S) key = rkey[ki * S + t];
+    hk[t] = key;
+    hv[t] = key ? rval[ki * S + t] : 0.0;   // a value exists only under a key
+    __syncthreads();
+    const int words = rwords[ki];
+    const int hlen = words > 1 ? words - 1 : 0;
+    for (int j = 0; j < nc; ++j) {
+        const long kj = (long)k * n + j;
+        const double s = cd_pair_term(0.0, key, T, hk, hv, rnorm + ki * RW_N, hlen, rkey + kj * S, rval + kj * S, rnorm + kj * RW_N,
+                                      rwords[kj], T, sigma, rk, rv, contrib);
+        if (t < RW_N) sn[t] = s;
+        __syncthreads();
+        if (t == 0) {   // cd_hyp_k's closing formula with one reference
+            double m = (((0.0 + sn[0]) + sn[1]) + sn[2]) + sn[3];
+            m /= (double)RW_N;
+            su[j] = m * 10.0;
+        }
+    }
+    __syncthreads();
+    if (U)
+        for (int j = t; j < n; j += RW_THREADS) U[ki * n + j] = j < nc ? su[j] : nan;
+    if (t == 0) c[ki] = cs_leave_one_out(su, weights ? weights + (long)k * n : nullptr, nc, i);
+}
+
+// One wave per image.  c != NULL: best[k] = the lowest i < n_cand[k] whose c[k][i] is the maximum (-1 when one of them is NaN:
+// a bad image).  Then, for every array pair given, row best[k] of the image's n rows goes to row k of the output (zeros for -1).
+__global__ __launch_bounds__(64) void cs_pick_k(const double* __restrict__ c, const int32_t* __restrict__ n_cand, int n,
+                                                int64_t* __restrict__ best, int S, const int64_t* __restrict__ seq_in,
+                                                int64_t* __restrict__ seq_out, const float* __restrict__ lp_in, float* __restrict__ lp_out,
+                                                const float* __restrict__ p_in, float* __restrict__ p_out) {
+    __shared__ long long sb;
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (lane == 0) {
+        long long b = -1;
+        if (c) {
+            const int nc = min(max(n_cand[k], 0), n);
+            double m = 0.0;
+            for (int i = 0; i < nc; ++i) {
+                const double v = c[(long)k * n + i];
+                if (v != v) {
+                    b = -1;
+                    break;
+                }
+                if (b < 0 || v > m) {
+                    m = v;
+                    b = i;
+                }
+            }
+            best[k] = b;
+        } else {
+            b = best[k];
+            if (b < 0 || b >= n) b = -1;
+        }
+        sb = b;
+    }
+    __syncthreads();
+    const long long b = sb;
+    const long src = ((long)k * n + (b < 0 ? 0 : b));
+    if (seq_in)
+        for (int s = lane; s < S; s += 64) seq_out[(long)k * S + s] = b < 0 ? 0 : seq_in[src * S + s];
+    if (lp_in)
+        for (int s = lane; s < S; s += 64) lp_out[(long)k * S + s] = b < 0 ? 0.0f : lp_in[src * S + s];
+    if (p_in && lane == 0) p_out[k] = b < 0 ? 0.0f : p_in[src];
+}
+
 // ---- host side --------------------------------------------------------------------------------------------
 namespace {
 const size_t kAlign = 256;
@@ -749,7 +904,8 @@ extern "C" int rfn_ciderd_score_ex(const int64_t* res, int n_rows, int T_res, co
     }
     RFN_CHECK_LAUNCH();
     const long nvec = (long)n_img * max_refs * RW_N;
-    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rcnt, rval, rnorm, df, ref_docs);
+    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(n_refs, bad, n_img, max_refs, T_gt, rkey, rcnt, rval, rnorm, df, ref_docs,
+                                                      nullptr);
     RFN_CHECK_LAUNCH();
     cd_hyp_k<<<n_rows, RW_THREADS, 0, st>>>(res, T_res, row_img, n_img, n_refs, bad, max_refs, T_gt, rkey, rval, rnorm, rwords, vocab,
                                             excl, df, ref_docs, sigma, scores);
@@ -844,6 +1000,97 @@ extern "C" int rfn_scst_reward_group(const double* cider, double cider_weight, c
     const long cnt = (long)B * T;
     rw_reward_group_k<<<rfn_cdiv(cnt, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, n, T, baseline,
                                                                           out, out64);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- consensus reranking -----------------------------------------------------------------------------------------------------
+namespace {
+// The candidates cooked as references (the scorer's layout with one score row per candidate), then cs_prep_k's three outputs.
+struct ConsensusLayout {
+    Layout L;
+    size_t ncand, row_img, ref_docs, total;
+};
+ConsensusLayout consensus_layout(int n_img, int n, int T, bool corpus) {
+    ConsensusLayout C{};
+    C.L = layout(corpus ? CIDER_CORPUS : CIDER_TABLE, n_img * n, n_img, n, T);
+    size_t o = C.L.total;
+    C.ncand = o;    o = up(o + (size_t)n_img * 4);
+    C.row_img = o;  o = up(o + (size_t)n_img * n * 4);
+    C.ref_docs = o; o = up(o + 8);
+    C.total = o;
+    return C;
+}
+bool consensus_dims_ok(int n_img, int n, int T) {
+    return n_img >= 1 && n >= 1 && n <= RW_MAX_REFS && T >= 1 && T <= RW_MAX_T && (long)n_img * n <= 0x7fffffffL;
+}
+}  // namespace
+
+extern "C" size_t rfn_consensus_ws_bytes(int n_img, int n, int T, int corpus) {
+    if (!consensus_dims_ok(n_img, n, T)) return 0;
+    return consensus_layout(n_img, n, T, corpus != 0).total;
+}
+
+extern "C" int rfn_consensus_ciderd(const int64_t* cands, int n_img, int n, int T, const int32_t* n_cand, const double* weights,
+                                    const void* table, int64_t slots, double ref_docs, int vocab, double sigma, unsigned flags,
+                                    double* U, double* c, int64_t* best, void* ws, size_t ws_bytes, void* stream) {
+    const int excl = (flags & RFN_CAPTION_END_EXCLUDED) != 0;
+    const bool corpus = table == nullptr;
+    const bool table_ok = corpus || (slots >= 2 && !(slots & (slots - 1)) && ref_docs > 0.0);
+    if (!consensus_dims_ok(n_img, n, T) || vocab < 0 || vocab > RW_MAX_ID || !table_ok) return RFN_ERR_SHAPE;
+    if (flags & ~RFN_CAPTION_END_EXCLUDED) return RFN_ERR_ARG;
+    if (!cands || !c || !best || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
+    const ConsensusLayout CL = consensus_layout(n_img, n, T, corpus);
+    if (ws_bytes < CL.total) return RFN_ERR_WORKSPACE;
+    const Layout& L = CL.L;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    uint64_t* rkey = (uint64_t*)(w + L.rkey);
+    int32_t* rcnt = (int32_t*)(w + L.rcnt);
+    int32_t* rwords = (int32_t*)(w + L.rwords);
+    int32_t* bad = (int32_t*)(w + L.bad);
+    double* rval = (double*)(w + L.rval);
+    double* rnorm = (double*)(w + L.rnorm);
+    int32_t* nc = (int32_t*)(w + CL.ncand);
+    int32_t* row_img = (int32_t*)(w + CL.row_img);
+    double* docs = (double*)(w + CL.ref_docs);
+    cs_prep_k<<<1, RW_THREADS, 0, st>>>(n_cand, n_img, n, nc, row_img, docs);
+    RFN_CHECK_LAUNCH();
+    CdDf df;
+    if (corpus) {
+        uint64_t* dkeys = (uint64_t*)(w + L.dkeys);
+        uint32_t* dcnt = (uint32_t*)(w + L.dcnt);
+        df = CdDf{dkeys, dcnt, nullptr, L.dslots};
+        cd_clear_k<<<(int)std::min<long>(rfn_cdiv(L.dslots, 256), 4096), 256, 0, st>>>(dkeys, dcnt, L.dslots);
+        RFN_CHECK_LAUNCH();
+        const size_t lds = (size_t)n * RW_N * T * 8;   // <= 64 KiB
+        if (lds > 48 * 1024)
+            hipFuncSetAttribute((const void*)rw_refs_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(cands, nc, n, T, vocab, excl, rkey, rcnt, rwords, bad, row_img, n_img * n, dkeys,
+                                                        dcnt, L.dslots);
+    } else {
+        df = CdDf{(const uint64_t*)table, nullptr, (const double*)((const uint64_t*)table + slots), slots};
+        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(cands, nc, n, T, vocab, excl, rkey, rcnt, rwords, bad, nullptr, 0, nullptr, nullptr,
+                                                       0);
+    }
+    RFN_CHECK_LAUNCH();
+    const long nvec = (long)n_img * n * RW_N;
+    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(nc, bad, n_img, n, T, rkey, rcnt, rval, rnorm, df, ref_docs,
+                                                      corpus ? docs : nullptr);
+    RFN_CHECK_LAUNCH();
+    cd_pair_k<<<n_img * n, RW_THREADS, 0, st>>>(nc, bad, n, T, rkey, rval, rnorm, rwords, weights, sigma, U, c);
+    RFN_CHECK_LAUNCH();
+    cs_pick_k<<<n_img, 64, 0, st>>>(c, nc, n, best, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+extern "C" int rfn_consensus_gather(const int64_t* best, int n_img, int n, int S, const int64_t* seq_in, int64_t* seq_out,
+                                    const float* lp_in, float* lp_out, const float* p_in, float* p_out, void* stream) {
+    if (n_img < 1 || n < 1 || S < 1) return RFN_ERR_SHAPE;
+    if (!best || (!seq_in && !lp_in && !p_in) || !seq_in != !seq_out || !lp_in != !lp_out || !p_in != !p_out) return RFN_ERR_ARG;
+    cs_pick_k<<<n_img, 64, 0, (hipStream_t)stream>>>(nullptr, nullptr, n, const_cast<int64_t*>(best), S, seq_in, seq_out, lp_in,
+                                                     lp_out, p_in, p_out);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -97,6 +97,17 @@ class GreedyBuffers:
         t_stop = early_exit(self.unf[1:].sum(1).tolist(), self.S)
         return self.seq[:, :t_stop - 1], self.seq_lp[:, :t_stop - 1], self.logp_all[:, :t_stop].contiguous()
 
+    def read_back_picked(self, best, n):
+        """read_back for one picked row per image (best (B / n,) int64, row best[k] of image k's n rows; a pick of -1 gives
+        zeros): the rows are gathered on the device (one launch for seq and seq_lp) and cut at THEIR early exit, with the same
+        single synchronisation."""
+        from . import rewards as RW
+        rows = torch.arange(best.numel(), device=best.device) * n + best.clamp(min=0)
+        seq, seq_lp, _ = RW.consensus_gather(best, n, self.seq, self.seq_lp)
+        logp, unf = self.logp_all.index_select(0, rows), self.unf.index_select(1, rows)
+        t_stop = early_exit(unf[1:].sum(1).tolist(), self.S)
+        return seq[:, :t_stop - 1], seq_lp[:, :t_stop - 1], logp[:, :t_stop].contiguous()
+
 
 def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
     """The whole free-running loop (pick, embed, cell, logit, log-softmax) in one call.  mode 0: greedy; 1: draw with the
@@ -282,6 +293,93 @@ class _Diversity:
                                         b.done_group.data_ptr(), b.active.data_ptr(), N.stream_ptr()), 'rfn_beam_step_div')
 
 
+class _Consensus:
+    """Consensus reranking of one call (rfn.h "consensus reranking"): opt['consensus'] = a rewards.CiderD scorer keeps, of an
+    image's candidates, the one that agrees most with the others under CIDEr-D.  sample: the candidates are the sample_n draws,
+    uniformly weighted.  sample_beam: opt['consensus_n'] = m (default beam_size, at most 32) ranked done beams -- or, with
+    group_size = G > 1, the G group bests -- weighted by opt['consensus_weights'] = 'uniform' (default) or 'prob' (w_j =
+    exp(p_j - max_j p_j)).  `parse` returns None without the key, so such a call issues exactly the launches it always did."""
+
+    KEYS = ('consensus', 'consensus_n', 'consensus_weights')
+    MAX_N = 32
+
+    @classmethod
+    def parse(cls, opt, V1, S, default_n):
+        scorer = opt.get('consensus', None)
+        if scorer is None:
+            stray = [k for k in cls.KEYS[1:] if opt.get(k, None) is not None]
+            if stray:
+                raise ValueError('%s without a \'consensus\' scorer' % ' / '.join(stray))
+            return None
+        from . import rewards as RW
+        if not isinstance(scorer, RW.CiderD):
+            raise NotImplementedError('consensus reranking is implemented for the CiderD scorer only, got %s'
+                                      % type(scorer).__name__)
+        if V1 > RW.MAX_ID + 1 or S > RW.MAX_T:
+            raise N.RfnError('consensus reranking supports vocab_size + 1 <= %d and seq_length <= %d' % (RW.MAX_ID + 1, RW.MAX_T))
+        m = opt.get('consensus_n', None)
+        m = int(default_n if m is None else m)
+        if not 1 <= m <= cls.MAX_N:
+            raise ValueError('consensus_n must be in 1 .. %d, got %d' % (cls.MAX_N, m))
+        how = opt.get('consensus_weights', None) or 'uniform'
+        if how not in ('uniform', 'prob'):
+            raise ValueError("consensus_weights is 'uniform' or 'prob', got %r" % (how,))
+        c = cls()
+        c.scorer, c.n, c.how, c.result = scorer, m, how, None
+        return c
+
+    @classmethod
+    def parse_sample(cls, opt, V1, S, samp, sample_max):
+        """sample's form of the keys: the candidates are the call's sample_n > 1 multinomial draws."""
+        if opt.get('consensus', None) is None:
+            return cls.parse(opt, V1, S, 1)
+        if sample_max:
+            raise ValueError('consensus reranks multinomial draws: it needs sample_max=0 (beam search takes it with beam_size > 1)')
+        if samp is None or samp.n < 2:
+            raise ValueError('consensus needs sample_n > 1 draws per image to choose from')
+        if opt.get('consensus_n', None) is not None or opt.get('consensus_weights', None) not in (None, 'uniform'):
+            raise ValueError('sample reranks all sample_n draws with uniform weights: consensus_n / consensus_weights are '
+                             'sample_beam keys')
+        return cls.parse(opt, V1, S, samp.n)
+
+    def pick(self, cands, n_cand=None, p=None):
+        """cands (B, n, S) int64 -> best (B,); sets self.result = {'index', 'scores'} (device tensors, nothing read back).
+        p (B, n) float32 log-probs: the weights under 'prob'."""
+        from . import rewards as RW
+        weights = None
+        if self.how == 'prob':
+            pd = p.double()
+            if n_cand is not None:
+                valid = torch.arange(cands.size(1), device=cands.device)[None, :] < n_cand[:, None]
+                pd = torch.where(valid, pd, torch.full_like(pd, float('-inf')))
+            weights = (pd - pd.max(1, keepdim=True).values).exp()
+        best, scores, _ = RW.consensus(self.scorer, cands, n_cand, weights)
+        self.result = {'index': best, 'scores': scores}
+        return best
+
+
+def _consensus_beams(cs, s_all, l_all, p_all, done_n, g_all, groups):
+    """sample_beam's pick among the ranked done beams (s_all, l_all, p_all: _sorted_done_beams' gathers) -> (seq, seq_lp) of the
+    chosen candidate per image.  groups == 1: the candidates are the first min(done_n, cs.n) ranked beams and the index is the
+    rank.  groups > 1: the G group bests -- the first ranked beam of every group, found here on the device -- and the index is
+    the group (every group has a done beam: its beams are all done after the last step)."""
+    from . import rewards as RW
+    S = s_all.size(2)
+    if groups > 1:
+        valid = torch.arange(s_all.size(1), device=s_all.device)[None, :] < done_n[:, None]
+        of_group = (g_all[:, None, :] == torch.arange(groups, device=s_all.device, dtype=g_all.dtype)[None, :, None]) & valid[:, None, :]
+        first = of_group.to(torch.int8).argmax(2)                                   # first maximum = first beam of the group
+        pick = first[:, :, None].expand(-1, -1, S)
+        cands, lps, p, n_cand, m = s_all.gather(1, pick), l_all.gather(1, pick), p_all.gather(1, first), None, groups
+    else:
+        m = min(cs.n, s_all.size(1))
+        cands, lps, p = s_all[:, :m].contiguous(), l_all[:, :m].contiguous(), p_all[:, :m].contiguous()
+        n_cand = done_n.clamp(max=m)
+    best = cs.pick(cands, n_cand, p)
+    seq, seq_lp, _ = RW.consensus_gather(best, m, cands, lps)
+    return seq, seq_lp
+
+
 def _diverse_beams(done_beams, groups):
     """Per image the G group bests: entry g is the first of the image's ranked done beams (length penalty included) that group
     g produced.  Lazy, as done_beams is."""
@@ -296,7 +394,8 @@ def _length_penalty(opt):
     return alpha
 
 
-def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None):
+def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None, consensus=None,
+                       groups=1):
     """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
     once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
@@ -309,7 +408,10 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly.
 
     done_group (a diverse search): every done beam's group goes through the same gather, and every done_beams dict gets it as
-    'group'."""
+    'group'.
+
+    consensus (a parsed _Consensus): the returned seq and its log-probs are the consensus pick among the ranked beams
+    (_consensus_beams) instead of the first of them; the lists keep their meaning and order, and nothing more is read back."""
     dev, B = done_p.device, done_p.size(0)
     score = done_p
     if length_penalty:
@@ -323,8 +425,13 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     rank = torch.sort(key, dim=1, stable=True).indices
     pick = rank[:, :, None].expand(-1, -1, S)
     s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
-    src = _BeamResults(s_all, l_all, p_all, done_n, done_group.gather(1, rank) if done_group is not None else None)
-    return (s_all[:, 0].contiguous(), l_all[:, 0].contiguous(), _LazyList(B, lambda: src.top_seq()),
+    g_all = done_group.gather(1, rank) if done_group is not None else None
+    src = _BeamResults(s_all, l_all, p_all, done_n, g_all)
+    if consensus is not None:
+        seq, seq_lp = _consensus_beams(consensus, s_all, l_all, p_all, done_n, g_all, groups)
+    else:
+        seq, seq_lp = s_all[:, 0].contiguous(), l_all[:, 0].contiguous()
+    return (seq, seq_lp, _LazyList(B, lambda: src.top_seq()),
             _LazyList(B, lambda: src.top_prob()), _LazyList(B, lambda: src.done_beams()))
 
 

@@ -17,8 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _diverse_beams, _Diversity, _length_penalty, _sorted_done_beams,
-                     _Stepper)
+from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _length_penalty,
+                     _sorted_done_beams, _Stepper)
 
 
 class EnsembleDecoder:
@@ -29,6 +29,7 @@ class EnsembleDecoder:
         if not models:
             raise ValueError('need at least one model')
         self.models = list(models)
+        self.consensus = None           # sample_beam with opt['consensus']: {'index', 'scores'} of the pick (device tensors)
         self.group = process_group
         world = dist.get_world_size(process_group) if process_group is not None else 1
         self.n_total = total_members if total_members is not None else len(self.models) * world
@@ -91,13 +92,15 @@ class EnsembleDecoder:
         """Beam search on the members' averaged distribution -> (seq (B, S), seqLogprobs (B, S), top_seq, top_prob) with
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,
         best first); `self.done_beams` as there, and with opt['group_size'] > 1 (diverse beam search) `self.diverse_beams` and the
-        'group' key as there.  A one-member ensemble IS that model's sample_beam, bit for bit."""
+        'group' key as there; opt['consensus'] (with 'consensus_n', 'consensus_weights') returns the consensus pick and fills
+        `self.consensus` as there.  A one-member ensemble IS that model's sample_beam, bit for bit."""
         W = opt.get('beam_size', 10)
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
         if W > 32 or S > 64 or W > V1:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
         cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
+        cs = _Consensus.parse(opt, V1, S, W)
         steppers = []
         for m in self.models:
             comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
@@ -133,7 +136,9 @@ class EnsembleDecoder:
                 N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
                         'rfn_log_softmax_topk')
         seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b.done_seq, b.done_lp, b.done_p, b.done_n, S,
-                                                                             b.max_done, alpha, b.done_group)
+                                                                             b.max_done, alpha, b.done_group, cs,
+                                                                             div.groups if div is not None else 1)
+        self.consensus = cs.result if cs is not None else None
         self.diverse_beams = _diverse_beams(self.done_beams, div.groups) if div is not None else None
         return seq, seq_lp, top_seq, top_prob
 

@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Sampling,
-                     _sorted_done_beams, _Stepper, early_exit, run_beam_loop, run_greedy_loop)
+from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty,
+                     _Sampling, _sorted_done_beams, _Stepper, early_exit, run_beam_loop, run_greedy_loop)
 
 _INIT = 0.1
 
@@ -449,6 +449,7 @@ class RecurrentFusionModel(nn.Module):
         self._ss_uniforms = None
         self.done_beams = []
         self.diverse_beams = None       # sample_beam with group_size > 1: per image the G group bests
+        self.consensus = None           # sample / sample_beam with opt['consensus']: {'index', 'scores'} of the pick (device)
 
     def init_weights(self):
         """misc/RecurrentFusionModel.py:188-196."""
@@ -776,7 +777,12 @@ class RecurrentFusionModel(nn.Module):
             return logits, (stepper.h.unsqueeze(0), stepper.c.unsqueeze(0))
 
     def sample(self, fc_feats, att_feats, opt={}):
-        """misc/RecurrentFusionModel.py:545-658."""
+        """misc/RecurrentFusionModel.py:545-658.
+
+        opt['consensus'] = a rewards.CiderD scorer, with sample_max = 0 and sample_n = n > 1 (rfn.h "consensus reranking"): the n
+        draws of an image are reranked on the device and the call returns B rows -- seq, seqLogprobs and logprobs of the draw that
+        agrees most with the image's other draws under CIDEr-D, cut at those rows' own early exit -- and `self.consensus` =
+        {'index': (B,), 'scores': (B, n)} (device tensors).  With beam_size > 1 the key goes to sample_beam."""
         sample_max = opt.get('sample_max', 1)
         beam_size = opt.get('beam_size', 1)
         temperature = opt.get('temperature', 1.0)
@@ -790,6 +796,8 @@ class RecurrentFusionModel(nn.Module):
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         if samp is not None and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: top_k / top_p / sample_n cannot be combined with it')
+        cs = _Consensus.parse_sample(opt, self.vocab_size + 1, self.seq_length, samp, sample_max)
+        self.consensus = None
         if samp is not None and sample_max:
             if samp.n > 1:
                 raise ValueError('sample_n > 1 with sample_max=1 would return n identical captions: sample with sample_max=0')
@@ -808,7 +816,7 @@ class RecurrentFusionModel(nn.Module):
         if (not sample_max and cons is None and samp is None) or force is not None:
             out = self._sample_replayed(comb, h, c, train, seed, want_grad, temperature, force)
         else:
-            out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp)
+            out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp, cs)
         return (*out, reason_pred)
 
     def sample_group(self, fc_feats, att_feats, n, opt={}):
@@ -867,9 +875,11 @@ class RecurrentFusionModel(nn.Module):
         return seq[:, :n_seq], seq_lp, logp.contiguous()
 
     @torch.no_grad()
-    def _sample_device_loop(self, comb, h, c, train, seed, sample_max, temperature, cons, samp=None):
+    def _sample_device_loop(self, comb, h, c, train, seed, sample_max, temperature, cons, samp=None, cs=None):
         """Greedy, or constrained / truncated multinomial: the whole free-running loop in one call -> (seq, seq_lp, logp).
-        samp.n > 1: n rows per image, image-major, all reading the image's thought vectors (comb stays per image)."""
+        samp.n > 1: n rows per image, image-major, all reading the image's thought vectors (comb stays per image).
+        cs (a parsed _Consensus): one row per image comes back, the draw that agrees most with the image's other draws, cut at
+        the chosen rows' own early exit; the pick is queued behind the loop and rides on its one read-back."""
         S, dev = self.seq_length, comb.device
         n = samp.n if samp is not None else 1
         if n > 1:
@@ -888,6 +898,10 @@ class RecurrentFusionModel(nn.Module):
                 raise N.RfnError('sampling uniforms are %s, this pass needs %s' % (tuple(r.shape), (2, S + 1, B)))
             mode, inv_temp, u = 1, 1.0 / float(temperature), r[0, 1:].contiguous()
         run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp)
+        if cs is not None:
+            best = cs.pick(bufs.seq.view(B // n, n, S))
+            self.consensus = cs.result
+            return bufs.read_back_picked(best, n)
         return bufs.read_back()        # waits for the loop: the call's one read-back
 
     def sample_beam(self, fc_feats, att_feats, opt={}):
@@ -900,7 +914,13 @@ class RecurrentFusionModel(nn.Module):
 
         opt['group_size'] = G > 1 (with opt['diversity_lambda'], default 0.5): diverse beam search (rfn.h "diverse beam
         search") -- beam_size is still the total number of beams.  Every `done_beams` dict then carries its 'group', and
-        `self.diverse_beams[k]` lists image k's G group bests under the call's ranking.  G = 1 is the plain search."""
+        `self.diverse_beams[k]` lists image k's G group bests under the call's ranking.  G = 1 is the plain search.
+
+        opt['consensus'] = a rewards.CiderD scorer (rfn.h "consensus reranking"): the returned seq / seqLogprobs are, per image,
+        the candidate that agrees most with the others under CIDEr-D -- among the first opt['consensus_n'] (default beam_size,
+        at most 32) ranked done beams, or among the G group bests of a diverse search -- with opt['consensus_weights'] 'uniform'
+        or 'prob'.  `self.consensus` = {'index': (B,) rank (or group) of the pick, 'scores': (B, n)}, device tensors; top_seq,
+        top_prob, done_beams and diverse_beams are unchanged, and the call stays lazy."""
         beam_size = opt.get('beam_size', 10)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
         assert beam_size <= V1, 'lets assume this for now'
@@ -908,6 +928,7 @@ class RecurrentFusionModel(nn.Module):
             raise N.RfnError('beam search supports beam_size <= 32 and seq_length <= 64')
         W = beam_size
         cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
+        cs = _Consensus.parse(opt, V1, S, W)
         if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         with torch.no_grad():
@@ -921,9 +942,11 @@ class RecurrentFusionModel(nn.Module):
             bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
             run_beam_loop(stepper, bufs, cons, div)
             seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
-                                                                            S, bufs.max_done, alpha, bufs.done_group)
+                                                                            S, bufs.max_done, alpha, bufs.done_group, cs,
+                                                                            div.groups if div is not None else 1)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
+        self.consensus = cs.result if cs is not None else None
         self.diverse_beams = _diverse_beams(done_beams, div.groups) if div is not None else None
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch

@@ -148,6 +148,40 @@ class CiderD(_IdScorer):
                                           ws.numel(), N.stream_ptr()), 'rfn_ciderd_score_ex')
         return out
 
+    def consensus(self, cands, n_cand=None, weights=None, end_token=True, want_pairs=False, vocab=MAX_ID):
+        """Consensus (minimum-Bayes-risk) reranking under this scorer (rfn.h "consensus reranking"): cands (B, n, T) int64 ids,
+        n_cand (B,) how many of an image's n candidates are valid (None: all), weights (B, n) float64 >= 0 (None: uniform).
+        -> (best (B,) int64, scores (B, n) float64, U (B, n, n) float64 or None): scores[k, i] is the weighted mean CIDEr-D of
+        candidate i against the image's other candidates, best[k] the lowest index of its maximum (-1, with NaN scores, for an
+        image with a bad input), U[k, i, j] the pairwise utility (want_pairs=True).  Everything stays on the device; after the
+        first call at a shape nothing is allocated but the results and nothing synchronises."""
+        dev = cands.device
+        if dev.type != 'cuda':
+            raise N.RfnError('cands must live on the GPU: the reranking has no CPU fallback')
+        if cands.dim() != 3:
+            raise ValueError('cands must be (images, candidates, T), got %s' % (tuple(cands.shape),))
+        cands = cands.to(torch.int64).contiguous()
+        B, n, T = cands.shape
+        if n_cand is not None:
+            n_cand = n_cand.to(dev, torch.int32).contiguous()
+            if n_cand.numel() != B:
+                raise ValueError('n_cand needs one entry per image')
+        if weights is not None:
+            weights = weights.to(dev, torch.float64).contiguous()
+            if tuple(weights.shape) != (B, n):
+                raise ValueError('weights must be (%d, %d), got %s' % (B, n, tuple(weights.shape)))
+        table = self._table(dev)
+        ws = self._workspace(dev, N.lib.rfn_consensus_ws_bytes(B, n, T, int(table is None)))
+        best = torch.empty(B, dtype=torch.int64, device=dev)
+        scores = torch.empty(B, n, dtype=torch.float64, device=dev)
+        U = torch.empty(B, n, n, dtype=torch.float64, device=dev) if want_pairs else None
+        N.check(N.lib.rfn_consensus_ciderd(cands.data_ptr(), B, n, T, N.ptr(n_cand) or None, N.ptr(weights) or None,
+                                           None if table is None else table.data_ptr(), 0 if table is None else self._slots,
+                                           C.c_double(self.ref_docs or 0.0), vocab, C.c_double(self._sigma), self._flags(end_token),
+                                           N.ptr(U) or None, scores.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           N.stream_ptr()), 'rfn_consensus_ciderd')
+        return best, scores, U
+
     def compute_score(self, gts, res):
         """The reference's interface: gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}], captions
         being space-separated id strings as array_to_str writes them.  -> (mean, np.ndarray of per-entry scores)."""
@@ -407,6 +441,38 @@ def scst_group_reward(scorer, gen_result, gts, n_refs, n, cider_weight=1.0, base
                                         C.c_double(0.0 if bleu is None else bleu4_weight), rows, n, T, _BASELINES[baseline],
                                         out.data_ptr(), N.ptr(out64), N.stream_ptr()), 'rfn_scst_reward_group')
     return out
+
+
+def consensus(scorer, cands, n_cand=None, weights=None, end_token=True, want_pairs=False):
+    """Consensus (minimum-Bayes-risk) reranking of decoded candidates: CiderD.consensus on `scorer` (table or corpus df).  Any
+    other scorer raises NotImplementedError (only the CIDEr-D utility is on the device)."""
+    if not isinstance(scorer, CiderD):
+        raise NotImplementedError('consensus reranking is implemented for the CiderD scorer only, got %s' % type(scorer).__name__)
+    return scorer.consensus(cands, n_cand, weights, end_token, want_pairs)
+
+
+def consensus_gather(best, n, seq=None, seq_lp=None, p=None):
+    """Row best[k] of image k's n rows, for each array given, in ONE launch (rfn_consensus_gather): seq (B*n, S) or (B, n, S)
+    int64, seq_lp the same shape float32, p (B, n) float32 -> (seq (B, S), seq_lp (B, S), p (B,)), None where none was given.
+    An image whose pick is -1 gets zeros."""
+    B = best.numel()
+    out, S = [], 1
+    for t, dtype in ((seq, torch.int64), (seq_lp, torch.float32)):
+        if t is not None:
+            if t.dtype != dtype or not t.is_contiguous() or t.numel() % (B * n) or t.device != best.device:
+                raise ValueError('consensus_gather takes contiguous (images * n, S) int64 / float32 tensors on the picks\' device')
+            S = t.numel() // (B * n)
+    if seq is not None and seq_lp is not None and seq.numel() != seq_lp.numel():
+        raise ValueError('seq and seq_lp must have the same shape')
+    if p is not None and (p.dtype != torch.float32 or not p.is_contiguous() or p.numel() != B * n or p.device != best.device):
+        raise ValueError('p must be a contiguous (images, n) float32 tensor on the picks\' device')
+    for t in (seq, seq_lp):
+        out.append(None if t is None else torch.empty(B, S, dtype=t.dtype, device=t.device))
+    out.append(None if p is None else torch.empty(B, dtype=torch.float32, device=p.device))
+    N.check(N.lib.rfn_consensus_gather(best.data_ptr(), B, n, S, N.ptr(seq) or None, N.ptr(out[0]) or None, N.ptr(seq_lp) or None,
+                                       N.ptr(out[1]) or None, N.ptr(p) or None, N.ptr(out[2]) or None, N.stream_ptr()),
+            'rfn_consensus_gather')
+    return tuple(out)
 
 
 _DEFAULT = {}

@@ -199,7 +199,69 @@ def diverse_ab(out_path, parent_tree, rounds=7):
         json.dump(res, f, indent=1)
         f.write('\n')
 
+def consensus_ab(out_path, rounds=7):
+    """--consensus [--out FILE]: config 5, sample(sample_n = 5) and sample_beam(beam_size = 5), each without and with
+    'consensus' (a corpus-df CiderD), windows of 3 calls after a warm-up call, the settings alternating, medians of `rounds`;
+    kernel launches per call by the profiler; and the pick's own launches (rewards.consensus on the 128 x 5 candidates) next to
+    one CiderD.score_ids call on the same 640 rows, by device events around each."""
+    import statistics
+    from recurrent_fusion_network_amd import rewards as RW
+    S, V1 = cfg.seq_length, cfg.vocab_size + 1
+    model.eval()
+    sc = RW.CiderD()
+    settings = [('sample_n_5', {'sample_max': 0, 'sample_n': 5}), ('sample_n_5_consensus', {'sample_max': 0, 'sample_n': 5, 'consensus': sc}),
+                ('beam_5', {'beam_size': 5}), ('beam_5_consensus', {'beam_size': 5, 'consensus': sc})]
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=%d, seq=%d, B=%d' % (V1, S, B), 'rounds': rounds, 'calls_per_window': 3,
+           'what': 'ms per sample() call (one read-back each), calls alternating; consensus scorer: CiderD(df=\'corpus\')'}
+
+    def call(o):
+        with torch.no_grad():
+            return model.sample(fc, att, o)
+
+    ms = {k: [] for k, _ in settings}
+    for k, o in settings:
+        call(o)
+    for _ in range(rounds):
+        for k, o in settings:
+            ms[k].append(timed(lambda: call(o), 3)[0] * 1e3)
+    for k, o in settings:
+        res[k] = {'ms': round(statistics.median(ms[k]), 3), 'min': round(min(ms[k]), 3), 'max': round(max(ms[k]), 3),
+                  'launches_per_call': HB.count_launches(lambda: call(o))}
+        print(json.dumps({k: res[k]}), flush=True)
+    res['added_ms'] = {'sample_n_5': round(res['sample_n_5_consensus']['ms'] - res['sample_n_5']['ms'], 3),
+                       'beam_5': round(res['beam_5_consensus']['ms'] - res['beam_5']['ms'], 3)}
+    # the pick alone, on the draws of one call
+    with torch.no_grad():
+        seq = call({'sample_max': 0, 'sample_n': 5})[0]
+    cands = torch.zeros(B, 5, S, dtype=torch.long, device=dev)
+    cands[:, :, :seq.size(1)] = seq.view(B, 5, -1)
+    rows, row_img, n_refs = cands.view(B * 5, S), torch.arange(B * 5, device=dev, dtype=torch.int32) // 5, torch.full((B,), 5, dtype=torch.int32, device=dev)
+
+    def one(fn, reps=50):
+        t = []
+        for _ in range(reps + 5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) * 1e3)
+        return round(sorted(t[5:])[reps // 2], 2)
+
+    pick, score = (lambda: RW.consensus(sc, cands)), (lambda: sc.score_ids(rows, row_img, cands, n_refs))
+    res['pick_alone_us'] = {'shape': [B, 5, S], 'note': 'median of 50, device events around the call\'s launches (launch gaps included)',
+                            'rewards.consensus (6 launches, corpus df)': one(pick), 'launches': HB.count_launches(pick),
+                            'CiderD.score_ids on the same 640 rows against the 5 candidates': one(score),
+                            'score_ids_launches': HB.count_launches(score)}
+    print(json.dumps(res['pick_alone_us']), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
 PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
+if '--consensus' in sys.argv:
+    consensus_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'decode_consensus.json'))
+    sys.exit(0)
 if '--diverse-child' in sys.argv:
     diverse_child(int(sys.argv[sys.argv.index('--diverse-child') + 1]))
     sys.exit(0)
