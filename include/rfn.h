@@ -1262,6 +1262,49 @@ int rfn_consensus_ciderd(const int64_t* cands, int n_img, int n, int T, const in
 int rfn_consensus_gather(const int64_t* best, int n_img, int n, int S, const int64_t* seq_in, int64_t* seq_out, const float* lp_in,
                          float* lp_out, const float* p_in, float* p_out, void* stream);
 
+/* ---- caption-set diversity (how different an image's n captions are from each other; the reference has nothing of the kind) -------
+ * Div-m, mBLEU and Self-CIDEr of caption sets, from the candidates cooked once as consensus reranking cooks them
+ * (csrc/rfn_reward.hip).  Inputs: cands (n_img, n, T) int64 ids, n_cand (n_img) int32 (NULL: all n), the df source, sigma, vocab and
+ * flags exactly as rfn_consensus_ciderd takes them (corpus mode counts the df from the candidates as that call does).
+ *   Bad images: n_cand[k] outside [1, n], a valid candidate holding an id outside [0, vocab], or (RFN_CAPTION_END_EXCLUDED) an empty
+ *   valid candidate -- rfn_consensus_ciderd's conditions.  Every double output of a bad image is NaN, every integer output 0; other
+ *   images are unaffected (in corpus mode a bad image changes the df, as there).
+ *   Div-m, m = 1..4: distinct[k][m-1] = the number of distinct m-grams over image k's valid candidates; words[k] = the sum of their
+ *   word counts (a caption's words as the flags define them); div[k][m-1] = distinct / (1e-6 + words), one fp64 add and one
+ *   division.  Defined for n_cand[k] = 1.
+ *   mBLEU: row (k, i) is BLEU-D of candidate i against the references {cands[k][j] : j != i, j < n_cand[k]} by rfn_bleud_score's
+ *   rules (clip each n-gram count against the largest count in any one reference; the closest reference length, the shorter on a
+ *   tie; the same formula).  mbleu (n_img, n, 4); mbleu_comps (n_img, n, 10) int32 in rfn_bleud_score's component layout (zeros
+ *   for a NaN row); mbleu_corpus (n, 4): row i is that formula over the integer sums of slot i's components across the images whose
+ *   row (k, i) is not NaN, NaN when there is none.  Rows at or beyond n_cand[k], and the one row of an image with n_cand[k] = 1
+ *   (nothing to compare with), are NaN and left out of the sums.  The reported mBleu_m is the mean of mbleu_corpus[:, m-1] over the
+ *   slots that are not NaN.
+ *   Self-CIDEr: U[k] is rfn_consensus_ciderd's pairwise utility with unit weights, the same bits.  K = (U + U^T) / 2 / 10 over the
+ *   valid candidates ((U_ij + U_ji) / 2, then / 10; CIDEr-D clips, so U itself is not symmetric, and a number read off one triangle
+ *   would change when the candidates are permuted).  eig (n_img, n): the eigenvalues of K ascending (fp64 cyclic Jacobi, fixed
+ *   rotation order and stopping rule), NaN at or beyond n_cand[k].  Eigenvalues below 1e-12 * lambda_max count as 0 -- part of the
+ *   definition: duplicate captions give exact zero eigenvalues that a solver returns as +-1e-16, whose square root would be 1e-8 of
+ *   noise.  With s_i = sqrt(lambda_i) of what is left, summed ascending, self_cider[k] = -log(max_i s_i / sum_i s_i) / log(n_cand[k]);
+ *   NaN when n_cand[k] = 1 or lambda_max <= 0.
+ *   Limits and checks: rfn_consensus_ciderd's (RFN_ERR_SHAPE outside 1 <= T <= 64, 1 <= n <= 32, 0 <= vocab <= 32767, and
+ *   rfn_capset_ws_bytes returns 0; then RFN_ERR_ARG for unknown flag bits, cands or ws NULL, ws not 16-B aligned; then
+ *   RFN_ERR_WORKSPACE).  Every output pointer may be NULL, and a NULL output skips its launches: distinct / words / div need the
+ *   cooking and one launch (one workgroup per image); the mbleu outputs one launch (one workgroup per (image, candidate)) plus one
+ *   for mbleu_corpus; U the tf-idf vectors and the pairs; eig / self_cider U (kept in the workspace when U is NULL) and one launch
+ *   (one wave per image).  Integer outputs are exact; fp64 in fixed orders, no floating-point atomics: bitwise repeatable, and in
+ *   table mode an image's outputs do not depend on the batch around it.  No allocation, no synchronisation (capturable). */
+size_t rfn_capset_ws_bytes(int n_img, int n, int T, int corpus);
+int rfn_capset_diversity(const int64_t* cands, int n_img, int n, int T, const int32_t* n_cand, const void* table, int64_t slots,
+                         double ref_docs, int vocab, double sigma, unsigned flags, int32_t* distinct, int32_t* words, double* div,
+                         double* mbleu, int32_t* mbleu_comps, double* mbleu_corpus, double* U, double* eig, double* self_cider,
+                         void* ws, size_t ws_bytes, void* stream);
+/* Best-of-n, its lowest index and mean-of-n of a score column: scores[(k * n + j) * stride] is the score of candidate j of image k;
+ * over j < n_cand[k] (NULL: n) best[k] = the maximum, arg[k] = its lowest index, mean[k] = the sum (ascending, from 0.0) divided
+ * once by n_cand[k].  One NaN among an image's valid entries, or n_cand[k] outside [1, n], gives NaN, -1, NaN.  Any output may be
+ * NULL.  One launch.  RFN_ERR_SHAPE: n_img, n or stride < 1; RFN_ERR_ARG: scores NULL or every output NULL. */
+int rfn_score_group_stats(const double* scores, int64_t stride, int n_img, int n, const int32_t* n_cand, double* best, int64_t* arg,
+                          double* mean, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,10 @@ def _load():
         'rfn_consensus_ws_bytes': (SZ, [I, I, I, I]),
         'rfn_consensus_ciderd': (C.c_int, [P, I, I, I, P, P, P, L, C.c_double, I, C.c_double, C.c_uint, P, P, P, P, SZ, P]),
         'rfn_consensus_gather': (C.c_int, [P, I, I, I, P, P, P, P, P, P, P]),
+        # caption-set diversity (rfn.h)
+        'rfn_capset_ws_bytes': (SZ, [I, I, I, I]),
+        'rfn_capset_diversity': (C.c_int, [P, I, I, I, P, P, L, C.c_double, I, C.c_double, C.c_uint] + [P] * 9 + [P, SZ, P]),
+        'rfn_score_group_stats': (C.c_int, [P, L, I, I, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

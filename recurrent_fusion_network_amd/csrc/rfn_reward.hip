@@ -24,6 +24,10 @@
 // cd_pair_k (one workgroup per (image, candidate)) fills a row of the pairwise utility with cd_pair_term, the device function
 // cd_hyp_k's reference loop runs too, and forms the leave-one-out consensus score; cs_pick_k picks and gathers.
 //
+// Caption-set diversity (cs_div_k, cs_loo_bleu_k, cs_bleu_corpus_k, cs_eig_k; rfn.h "caption-set diversity"): the same cooked
+// candidates and the same U, read for Div-m (distinct n-grams over the set), mBLEU (each candidate against the others) and
+// Self-CIDEr (the spectrum of the symmetrised U).  rw_group_stats_k: best / argmax / mean of a score column per image.
+//
 // BLEU-D (bd_): launches of one call: refs, hyp (clip every distinct n-gram of the row against the maximum count over
 // the image's references, reduce correct[4], pick the closest reference length, write the row's four scores and its
 // integer components) and, when asked for, corpus (the same formula over the sums of the components).  Everything
@@ -769,6 +773,299 @@ __global__ __launch_bounds__(64) void cs_pick_k(const double* __restrict__ c, co
     if (p_in && lane == 0) p_out[k] = b < 0 ? 0.0f : p_in[src];
 }
 
+// ---- caption-set diversity (rfn.h "caption-set diversity") ---------------------------------------------------------------------
+// Every kernel below reads what the consensus cooking left in the workspace: rkey / rcnt / rwords per (image, candidate), img_bad
+// per image (which covers n_cand outside [1, n]) and cs_prep_k's candidate counts.
+//
+// Div-m.  One workgroup per image.  The image's n_cand * 4 * T first-occurrence keys are staged in dynamic LDS (the layout
+// rw_refs_k<true> stages: 64 KiB at n = 32, T = 64, inside the 160 KiB of a CU); a key counts when no EARLIER candidate holds it in
+// the same order's segment.  Staging and scanning was chosen over an LDS hash set: keys are already unique within a candidate, the
+// scan needs no 64-bit LDS compare-and-swap and no probe bound, its result does not depend on insertion order, and rw_refs_k<true>
+// has run the very same loop at the same limits since the corpus df exists.  Integer counting; one fp64 add and one division.
+__global__ __launch_bounds__(RW_THREADS) void cs_div_k(const int32_t* __restrict__ n_cand, const int32_t* __restrict__ img_bad, int n,
+                                                       int T, const uint64_t* __restrict__ rkey, const int32_t* __restrict__ rwords,
+                                                       int32_t* __restrict__ distinct, int32_t* __restrict__ words,
+                                                       double* __restrict__ div) {
+    extern __shared__ uint64_t all[];
+    __shared__ int cnt[RW_N];
+    const int k = blockIdx.x, t = threadIdx.x, S = RW_N * T;
+    if (img_bad[k]) {   // block-uniform
+        if (t < RW_N) {
+            if (distinct) distinct[(long)k * RW_N + t] = 0;
+            if (div) div[(long)k * RW_N + t] = __builtin_nan("");
+        }
+        if (t == 0 && words) words[k] = 0;
+        return;
+    }
+    const int nc = n_cand[k];
+    if (t < RW_N) cnt[t] = 0;
+    for (int x = t; x < nc * S; x += RW_THREADS) all[x] = rkey[(long)k * n * S + x];
+    __syncthreads();
+    int mine[RW_N] = {0, 0, 0, 0};
+    for (int x = t; x < nc * S; x += RW_THREADS) {
+        const uint64_t key = all[x];
+        if (!key) continue;
+        const int j = x / S, s = x - j * S, m = s / T;
+        bool seen = false;
+        for (int jj = 0; jj < j && !seen; ++jj)
+            for (int q = 0; q < T; ++q)
+                if (all[jj * S + m * T + q] == key) {
+                    seen = true;
+                    break;
+                }
+        if (!seen)
+            for (int o = 0; o < RW_N; ++o) mine[o] += (o == m);
+    }
+    for (int o = 0; o < RW_N; ++o)
+        if (mine[o]) atomicAdd(&cnt[o], mine[o]);
+    __syncthreads();
+    if (t < RW_N) {
+        int w = 0;
+        for (int j = 0; j < nc; ++j) w += rwords[(long)k * n + j];
+        if (distinct) distinct[(long)k * RW_N + t] = cnt[t];
+        if (div) div[(long)k * RW_N + t] = (double)cnt[t] / (1e-6 + (double)w);
+        if (t == 0 && words) words[k] = w;
+    }
+}
+
+// mBLEU.  One workgroup per (image k, candidate i), like cd_pair_k: BLEU-D of candidate i against the image's other valid
+// candidates, by bd_hyp_k's rules (clip against the largest count in any one reference, the closest reference length, the shorter
+// on a tie, bd_formula).  The hypothesis is the cooked keys and counts.  comps: the workspace copy (testlen = -1 marks a NaN row, a
+// slot behind n_cand included); scores / ucomps: NULL or the caller's (n_img, n, 4) and (n_img, n, 10).
+__global__ __launch_bounds__(RW_THREADS) void cs_loo_bleu_k(const int32_t* __restrict__ n_cand, const int32_t* __restrict__ img_bad,
+                                                            int n, int T, const uint64_t* __restrict__ rkey,
+                                                            const int32_t* __restrict__ rcnt, const int32_t* __restrict__ rwords,
+                                                            double* __restrict__ scores, int32_t* __restrict__ comps,
+                                                            int32_t* __restrict__ ucomps) {
+    __shared__ uint64_t rk[RW_THREADS];
+    __shared__ int rc[RW_THREADS], clip[RW_THREADS];
+    __shared__ int correct[RW_N];
+    const int k = blockIdx.x / n, i = blockIdx.x - k * n, t = threadIdx.x, S = RW_N * T;
+    const long ki = (long)k * n + i;
+    const int nc = img_bad[k] ? 0 : n_cand[k];   // block-uniform
+    if (i >= nc || nc < 2) {                     // a bad image, a slot behind n_cand, or nothing to compare with
+        if (scores && t < RW_N) scores[ki * RW_N + t] = __builtin_nan("");
+        if (t < BD_COMPS) {
+            comps[ki * BD_COMPS + t] = t == 0 ? -1 : 0;
+            if (ucomps) ucomps[ki * BD_COMPS + t] = 0;
+        }
+        return;
+    }
+    uint64_t key = 0;
+    int tf = 0;
+    if (t < S) {
+        key = rkey[ki * S + t];
+        tf = rcnt[ki * S + t];
+    }
+    const int m = t / T;
+    int maxc = 0;
+    for (int j = 0; j < nc; ++j) {
+        if (j == i) continue;
+        const long kj = (long)k * n + j;
+        maxc = max(maxc, rw_lookup(rkey + kj * S, rcnt + kj * S, T, key, m, rk, rc));
+        __syncthreads();
+    }
+    clip[t] = key ? min(tf, maxc) : 0;
+    __syncthreads();
+    if (t < RW_N) {
+        int s = 0;
+        for (int p = 0; p < T; ++p) s += clip[t * T + p];
+        correct[t] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int words = rwords[ki];
+        int reflen = 0, best = 0;
+        bool have = false;
+        for (int j = 0; j < nc; ++j) {
+            if (j == i) continue;
+            const int l = rwords[(long)k * n + j], d = abs(l - words);
+            if (!have || d < best || (d == best && l < reflen)) {
+                best = d;
+                reflen = l;
+                have = true;
+            }
+        }
+        int c[BD_COMPS];
+        c[0] = words;
+        c[1] = reflen;
+        double cor[RW_N], gue[RW_N], bleu[RW_N];
+        for (int o = 0; o < RW_N; ++o) {
+            c[2 + o] = words - o > 0 ? words - o : 0;
+            c[2 + RW_N + o] = correct[o];
+            gue[o] = (double)c[2 + o];
+            cor[o] = (double)correct[o];
+        }
+        bd_formula(cor, gue, (double)words, (double)reflen, bleu);
+        for (int o = 0; o < BD_COMPS; ++o) {
+            comps[ki * BD_COMPS + o] = c[o];
+            if (ucomps) ucomps[ki * BD_COMPS + o] = c[o];
+        }
+        if (scores)
+            for (int o = 0; o < RW_N; ++o) scores[ki * RW_N + o] = bleu[o];
+    }
+}
+
+// One workgroup per candidate slot i, in bd_corpus_k's shape: bd_formula over the integer sums of slot i's components across the
+// images whose row is not NaN; a slot no image scored is NaN.
+__global__ __launch_bounds__(RW_THREADS) void cs_bleu_corpus_k(const int32_t* __restrict__ comps, int n_img, int n,
+                                                               double* __restrict__ corpus) {
+    __shared__ long long part[RW_THREADS];
+    __shared__ long long tot[BD_COMPS + 1];
+    const int i = blockIdx.x, t = threadIdx.x;
+    for (int c = 0; c <= BD_COMPS; ++c) {   // c == BD_COMPS: the number of rows summed
+        long long s = 0;
+        for (int k = t; k < n_img; k += RW_THREADS) {
+            const long o = ((long)k * n + i) * BD_COMPS;
+            if (comps[o] >= 0) s += c < BD_COMPS ? comps[o + c] : 1;
+        }
+        part[t] = s;
+        __syncthreads();
+        for (int w = RW_THREADS / 2; w > 0; w >>= 1) {
+            if (t < w) part[t] += part[t + w];
+            __syncthreads();
+        }
+        if (t == 0) tot[c] = part[0];
+        __syncthreads();
+    }
+    if (t == 0) {
+        double cor[RW_N], gue[RW_N], bleu[RW_N];
+        for (int o = 0; o < RW_N; ++o) {
+            gue[o] = (double)tot[2 + o];
+            cor[o] = (double)tot[2 + RW_N + o];
+        }
+        bd_formula(cor, gue, (double)tot[0], (double)tot[1], bleu);
+        for (int o = 0; o < RW_N; ++o) corpus[(long)i * RW_N + o] = tot[BD_COMPS] > 0 ? bleu[o] : __builtin_nan("");
+    }
+}
+
+// Self-CIDEr.  One wave per image; K = (U + U^T) / 2 / 10 over the valid candidates lives in LDS (8 KiB at n = 32).  fp64 cyclic
+// Jacobi in one fixed order: sweeps over (p, q), p < q, row by row; a rotation is skipped when |K_pq| <= 2^-60 ||K||_F (the norm of
+// the matrix before the first sweep); the loop ends after the first sweep that rotated nothing, or after CS_EIG_SWEEPS.  Lane r
+// updates K_rp, K_rq and their mirror images, lane 0 the two diagonal entries; every lane computes the same c, s, t from the same
+// LDS words.  Nothing depends on another image or on the grid, so an image's bits are its own.  Then lane 0 sorts the diagonal,
+// drops what lies below 1e-12 lambda_max and forms -log(max sqrt / sum sqrt) / log(n_cand).
+#define CS_EIG_SWEEPS 30
+__global__ __launch_bounds__(64) void cs_eig_k(const int32_t* __restrict__ n_cand, const int32_t* __restrict__ img_bad, int n,
+                                               const double* __restrict__ U, double* __restrict__ eig,
+                                               double* __restrict__ self_cider) {
+#pragma clang fp contract(off)
+    __shared__ double K[RW_MAX_REFS * RW_MAX_REFS];
+    __shared__ double lam[RW_MAX_REFS];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const double nan = __builtin_nan("");
+    if (img_bad[k]) {   // block-uniform
+        if (eig)
+            for (int j = lane; j < n; j += 64) eig[(long)k * n + j] = nan;
+        if (lane == 0 && self_cider) self_cider[k] = nan;
+        return;
+    }
+    const int nc = n_cand[k];
+    const double* u = U + (long)k * n * n;
+    for (int x = lane; x < nc * nc; x += 64) {
+        const int i = x / nc, j = x - i * nc;
+        K[i * RW_MAX_REFS + j] = ((u[i * n + j] + u[j * n + i]) / 2.0) / 10.0;
+    }
+    __syncthreads();
+    double f2 = 0.0;
+    for (int i = 0; i < nc; ++i)
+        for (int j = 0; j < nc; ++j) f2 = f2 + K[i * RW_MAX_REFS + j] * K[i * RW_MAX_REFS + j];
+    const double thr = sqrt(f2) * 0x1p-60;
+    for (int sweep = 0; sweep < CS_EIG_SWEEPS; ++sweep) {
+        int rotated = 0;
+        for (int p = 0; p < nc - 1; ++p)
+            for (int q = p + 1; q < nc; ++q) {
+                const double apq = K[p * RW_MAX_REFS + q];
+                if (!(fabs(apq) > thr)) continue;   // wave-uniform: every lane read the same word
+                ++rotated;
+                const double app = K[p * RW_MAX_REFS + p], aqq = K[q * RW_MAX_REFS + q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+                double arp = 0.0, arq = 0.0;
+                const bool mine = lane < nc && lane != p && lane != q;
+                if (mine) {
+                    arp = K[lane * RW_MAX_REFS + p];
+                    arq = K[lane * RW_MAX_REFS + q];
+                }
+                __syncthreads();   // every read of this rotation is done
+                if (mine) {
+                    const double np_ = c * arp - s * arq, nq_ = s * arp + c * arq;
+                    K[lane * RW_MAX_REFS + p] = np_;
+                    K[p * RW_MAX_REFS + lane] = np_;
+                    K[lane * RW_MAX_REFS + q] = nq_;
+                    K[q * RW_MAX_REFS + lane] = nq_;
+                }
+                if (lane == 0) {
+                    K[p * RW_MAX_REFS + p] = app - tt * apq;
+                    K[q * RW_MAX_REFS + q] = aqq + tt * apq;
+                    K[p * RW_MAX_REFS + q] = 0.0;
+                    K[q * RW_MAX_REFS + p] = 0.0;
+                }
+                __syncthreads();
+            }
+        if (!rotated) break;
+    }
+    if (lane == 0) {
+        for (int i = 0; i < nc; ++i) {   // insertion sort, ascending
+            const double v = K[i * RW_MAX_REFS + i];
+            int j = i;
+            while (j > 0 && lam[j - 1] > v) {
+                lam[j] = lam[j - 1];
+                --j;
+            }
+            lam[j] = v;
+        }
+        if (self_cider) {
+            const double top = lam[nc - 1];
+            double r = nan;
+            if (nc > 1 && top > 0.0) {
+                const double cut = 1e-12 * top;
+                double sum = 0.0, big = 0.0;
+                for (int i = 0; i < nc; ++i) {
+                    if (lam[i] < cut) continue;
+                    big = sqrt(lam[i]);
+                    sum = sum + big;
+                }
+                r = -log(big / sum) / log((double)nc);
+            }
+            self_cider[k] = r;
+        }
+    }
+    __syncthreads();
+    if (eig)
+        for (int j = lane; j < n; j += 64) eig[(long)k * n + j] = j < nc ? lam[j] : nan;
+}
+
+// ---- best-of-n, its lowest index and mean-of-n of a score column: one thread per image.  scores[(k * n + j) * stride], j <
+// n_cand[k] (NULL: n); the sum runs ascending from 0.0 and is divided once.  One NaN among the valid entries, or a count outside
+// [1, n], gives NaN, -1, NaN.
+__global__ void rw_group_stats_k(const double* __restrict__ scores, long stride, int n_img, int n, const int32_t* __restrict__ n_cand,
+                                 double* __restrict__ best, int64_t* __restrict__ arg, double* __restrict__ mean) {
+#pragma clang fp contract(off)
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_img) return;
+    const int nc = n_cand ? n_cand[k] : n;
+    double m = __builtin_nan(""), sum = 0.0;
+    long long b = -1;
+    if (nc >= 1 && nc <= n)
+        for (int j = 0; j < nc; ++j) {
+            const double v = scores[(k * n + j) * stride];
+            if (v != v) {
+                b = -1;
+                break;
+            }
+            sum = sum + v;
+            if (b < 0 || v > m) {
+                m = v;
+                b = j;
+            }
+        }
+    if (best) best[k] = b < 0 ? __builtin_nan("") : m;
+    if (arg) arg[k] = b;
+    if (mean) mean[k] = b < 0 ? __builtin_nan("") : sum / (double)nc;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------
 namespace {
 const size_t kAlign = 256;
@@ -1024,6 +1321,53 @@ ConsensusLayout consensus_layout(int n_img, int n, int T, bool corpus) {
 bool consensus_dims_ok(int n_img, int n, int T) {
     return n_img >= 1 && n >= 1 && n <= RW_MAX_REFS && T >= 1 && T <= RW_MAX_T && (long)n_img * n <= 0x7fffffffL;
 }
+// The workspace of a consensus-shaped call as pointers, and the launches that fill it: cs_prep_k, then the candidates cooked as
+// their image's references ([clear], refs, and -- want_vec -- the tf-idf vectors).  Without want_vec nothing reads a df, so the
+// plain rw_refs_k runs in both df modes.
+struct Cooked {
+    uint64_t* rkey;
+    int32_t *rcnt, *rwords, *bad, *nc, *row_img;
+    double *rval, *rnorm, *docs;
+};
+Cooked cooked_of(const ConsensusLayout& CL, void* ws) {
+    char* w = (char*)ws;
+    const Layout& L = CL.L;
+    return Cooked{(uint64_t*)(w + L.rkey), (int32_t*)(w + L.rcnt),     (int32_t*)(w + L.rwords),
+                  (int32_t*)(w + L.bad),   (int32_t*)(w + CL.ncand),   (int32_t*)(w + CL.row_img),
+                  (double*)(w + L.rval),   (double*)(w + L.rnorm),     (double*)(w + CL.ref_docs)};
+}
+int consensus_cook(const int64_t* cands, int n_img, int n, int T, const int32_t* n_cand, const void* table, int64_t slots,
+                   double ref_docs, int vocab, int excl, bool want_vec, const ConsensusLayout& CL, const Cooked& K, hipStream_t st) {
+    const Layout& L = CL.L;
+    const bool corpus = table == nullptr;
+    char* w = (char*)K.rkey - L.rkey;
+    cs_prep_k<<<1, RW_THREADS, 0, st>>>(n_cand, n_img, n, K.nc, K.row_img, K.docs);
+    RFN_CHECK_LAUNCH();
+    CdDf df;
+    if (corpus && want_vec) {
+        uint64_t* dkeys = (uint64_t*)(w + L.dkeys);
+        uint32_t* dcnt = (uint32_t*)(w + L.dcnt);
+        df = CdDf{dkeys, dcnt, nullptr, L.dslots};
+        cd_clear_k<<<(int)std::min<long>(rfn_cdiv(L.dslots, 256), 4096), 256, 0, st>>>(dkeys, dcnt, L.dslots);
+        RFN_CHECK_LAUNCH();
+        const size_t lds = (size_t)n * RW_N * T * 8;   // <= 64 KiB
+        if (lds > 48 * 1024)
+            hipFuncSetAttribute((const void*)rw_refs_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(cands, K.nc, n, T, vocab, excl, K.rkey, K.rcnt, K.rwords, K.bad, K.row_img,
+                                                        n_img * n, dkeys, dcnt, L.dslots);
+    } else {
+        df = CdDf{(const uint64_t*)table, nullptr, corpus ? nullptr : (const double*)((const uint64_t*)table + slots), slots};
+        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(cands, K.nc, n, T, vocab, excl, K.rkey, K.rcnt, K.rwords, K.bad, nullptr, 0,
+                                                       nullptr, nullptr, 0);
+    }
+    RFN_CHECK_LAUNCH();
+    if (!want_vec) return RFN_OK;
+    const long nvec = (long)n_img * n * RW_N;
+    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(K.nc, K.bad, n_img, n, T, K.rkey, K.rcnt, K.rval, K.rnorm, df, ref_docs,
+                                                      corpus ? K.docs : nullptr);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
 }  // namespace
 
 extern "C" size_t rfn_consensus_ws_bytes(int n_img, int n, int T, int corpus) {
@@ -1042,42 +1386,13 @@ extern "C" int rfn_consensus_ciderd(const int64_t* cands, int n_img, int n, int 
     if (!cands || !c || !best || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
     const ConsensusLayout CL = consensus_layout(n_img, n, T, corpus);
     if (ws_bytes < CL.total) return RFN_ERR_WORKSPACE;
-    const Layout& L = CL.L;
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    uint64_t* rkey = (uint64_t*)(w + L.rkey);
-    int32_t* rcnt = (int32_t*)(w + L.rcnt);
-    int32_t* rwords = (int32_t*)(w + L.rwords);
-    int32_t* bad = (int32_t*)(w + L.bad);
-    double* rval = (double*)(w + L.rval);
-    double* rnorm = (double*)(w + L.rnorm);
-    int32_t* nc = (int32_t*)(w + CL.ncand);
-    int32_t* row_img = (int32_t*)(w + CL.row_img);
-    double* docs = (double*)(w + CL.ref_docs);
-    cs_prep_k<<<1, RW_THREADS, 0, st>>>(n_cand, n_img, n, nc, row_img, docs);
-    RFN_CHECK_LAUNCH();
-    CdDf df;
-    if (corpus) {
-        uint64_t* dkeys = (uint64_t*)(w + L.dkeys);
-        uint32_t* dcnt = (uint32_t*)(w + L.dcnt);
-        df = CdDf{dkeys, dcnt, nullptr, L.dslots};
-        cd_clear_k<<<(int)std::min<long>(rfn_cdiv(L.dslots, 256), 4096), 256, 0, st>>>(dkeys, dcnt, L.dslots);
-        RFN_CHECK_LAUNCH();
-        const size_t lds = (size_t)n * RW_N * T * 8;   // <= 64 KiB
-        if (lds > 48 * 1024)
-            hipFuncSetAttribute((const void*)rw_refs_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        rw_refs_k<true><<<n_img, RW_THREADS, lds, st>>>(cands, nc, n, T, vocab, excl, rkey, rcnt, rwords, bad, row_img, n_img * n, dkeys,
-                                                        dcnt, L.dslots);
-    } else {
-        df = CdDf{(const uint64_t*)table, nullptr, (const double*)((const uint64_t*)table + slots), slots};
-        rw_refs_k<false><<<n_img, RW_THREADS, 0, st>>>(cands, nc, n, T, vocab, excl, rkey, rcnt, rwords, bad, nullptr, 0, nullptr, nullptr,
-                                                       0);
-    }
-    RFN_CHECK_LAUNCH();
-    const long nvec = (long)n_img * n * RW_N;
-    cd_ref_vec_k<<<rfn_cdiv(nvec, 256), 256, 0, st>>>(nc, bad, n_img, n, T, rkey, rcnt, rval, rnorm, df, ref_docs,
-                                                      corpus ? docs : nullptr);
-    RFN_CHECK_LAUNCH();
+    const Cooked K = cooked_of(CL, ws);
+    const int rc = consensus_cook(cands, n_img, n, T, n_cand, table, slots, ref_docs, vocab, excl, true, CL, K, st);
+    if (rc != RFN_OK) return rc;
+    const int32_t *nc = K.nc, *bad = K.bad, *rwords = K.rwords;
+    const uint64_t* rkey = K.rkey;
+    const double *rval = K.rval, *rnorm = K.rnorm;
     cd_pair_k<<<n_img * n, RW_THREADS, 0, st>>>(nc, bad, n, T, rkey, rval, rnorm, rwords, weights, sigma, U, c);
     RFN_CHECK_LAUNCH();
     cs_pick_k<<<n_img, 64, 0, st>>>(c, nc, n, best, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1091,6 +1406,89 @@ extern "C" int rfn_consensus_gather(const int64_t* best, int n_img, int n, int S
     if (!best || (!seq_in && !lp_in && !p_in) || !seq_in != !seq_out || !lp_in != !lp_out || !p_in != !p_out) return RFN_ERR_ARG;
     cs_pick_k<<<n_img, 64, 0, (hipStream_t)stream>>>(nullptr, nullptr, n, const_cast<int64_t*>(best), S, seq_in, seq_out, lp_in,
                                                      lp_out, p_in, p_out);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- caption-set diversity ------------------------------------------------------------------------------------------------------
+namespace {
+// The consensus workspace, then U and cd_pair_k's scores (read by the eigen kernel when the caller keeps neither) and the BLEU
+// components of every (image, slot).
+struct CapsetLayout {
+    ConsensusLayout C;
+    size_t U, c, comps, total;
+};
+CapsetLayout capset_layout(int n_img, int n, int T, bool corpus) {
+    CapsetLayout P{};
+    P.C = consensus_layout(n_img, n, T, corpus);
+    size_t o = P.C.total;
+    const size_t rows = (size_t)n_img * n;
+    P.U = o;     o = up(o + rows * n * 8);
+    P.c = o;     o = up(o + rows * 8);
+    P.comps = o; o = up(o + rows * BD_COMPS * 4);
+    P.total = o;
+    return P;
+}
+}  // namespace
+
+extern "C" size_t rfn_capset_ws_bytes(int n_img, int n, int T, int corpus) {
+    if (!consensus_dims_ok(n_img, n, T)) return 0;
+    return capset_layout(n_img, n, T, corpus != 0).total;
+}
+
+extern "C" int rfn_capset_diversity(const int64_t* cands, int n_img, int n, int T, const int32_t* n_cand, const void* table,
+                                    int64_t slots, double ref_docs, int vocab, double sigma, unsigned flags, int32_t* distinct,
+                                    int32_t* words, double* div, double* mbleu, int32_t* mbleu_comps, double* mbleu_corpus, double* U,
+                                    double* eig, double* self_cider, void* ws, size_t ws_bytes, void* stream) {
+    const int excl = (flags & RFN_CAPTION_END_EXCLUDED) != 0;
+    const bool corpus = table == nullptr;
+    const bool table_ok = corpus || (slots >= 2 && !(slots & (slots - 1)) && ref_docs > 0.0);
+    if (!consensus_dims_ok(n_img, n, T) || vocab < 0 || vocab > RW_MAX_ID || !table_ok) return RFN_ERR_SHAPE;
+    if (flags & ~RFN_CAPTION_END_EXCLUDED) return RFN_ERR_ARG;
+    if (!cands || !ws || !rfn_aligned16(ws)) return RFN_ERR_ARG;
+    const CapsetLayout P = capset_layout(n_img, n, T, corpus);
+    if (ws_bytes < P.total) return RFN_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const bool want_div = distinct || words || div, want_bleu = mbleu || mbleu_comps || mbleu_corpus;
+    const bool want_eig = eig || self_cider, want_u = U || want_eig;
+    if (!want_div && !want_bleu && !want_u) return RFN_OK;
+    const Cooked K = cooked_of(P.C, ws);
+    const int rc = consensus_cook(cands, n_img, n, T, n_cand, table, slots, ref_docs, vocab, excl, want_u, P.C, K, st);
+    if (rc != RFN_OK) return rc;
+    char* w = (char*)ws;
+    if (want_div) {
+        const size_t lds = (size_t)n * RW_N * T * 8;   // <= 64 KiB
+        if (lds > 48 * 1024) hipFuncSetAttribute((const void*)cs_div_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        cs_div_k<<<n_img, RW_THREADS, lds, st>>>(K.nc, K.bad, n, T, K.rkey, K.rwords, distinct, words, div);
+        RFN_CHECK_LAUNCH();
+    }
+    if (want_bleu) {
+        int32_t* comps = (int32_t*)(w + P.comps);
+        cs_loo_bleu_k<<<n_img * n, RW_THREADS, 0, st>>>(K.nc, K.bad, n, T, K.rkey, K.rcnt, K.rwords, mbleu, comps, mbleu_comps);
+        RFN_CHECK_LAUNCH();
+        if (mbleu_corpus) {
+            cs_bleu_corpus_k<<<n, RW_THREADS, 0, st>>>(comps, n_img, n, mbleu_corpus);
+            RFN_CHECK_LAUNCH();
+        }
+    }
+    if (want_u) {
+        double* u = U ? U : (double*)(w + P.U);
+        cd_pair_k<<<n_img * n, RW_THREADS, 0, st>>>(K.nc, K.bad, n, T, K.rkey, K.rval, K.rnorm, K.rwords, nullptr, sigma, u,
+                                                    (double*)(w + P.c));
+        RFN_CHECK_LAUNCH();
+        if (want_eig) {
+            cs_eig_k<<<n_img, 64, 0, st>>>(K.nc, K.bad, n, u, eig, self_cider);
+            RFN_CHECK_LAUNCH();
+        }
+    }
+    return RFN_OK;
+}
+
+extern "C" int rfn_score_group_stats(const double* scores, int64_t stride, int n_img, int n, const int32_t* n_cand, double* best,
+                                     int64_t* arg, double* mean, void* stream) {
+    if (n_img < 1 || n < 1 || stride < 1) return RFN_ERR_SHAPE;
+    if (!scores || (!best && !arg && !mean)) return RFN_ERR_ARG;
+    rw_group_stats_k<<<rfn_cdiv(n_img, 256), 256, 0, (hipStream_t)stream>>>(scores, (long)stride, n_img, n, n_cand, best, arg, mean);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -358,26 +358,37 @@ class _Consensus:
         return best
 
 
-def _consensus_beams(cs, s_all, l_all, p_all, done_n, g_all, groups):
-    """sample_beam's pick among the ranked done beams (s_all, l_all, p_all: _sorted_done_beams' gathers) -> (seq, seq_lp) of the
-    chosen candidate per image.  groups == 1: the candidates are the first min(done_n, cs.n) ranked beams and the index is the
-    rank.  groups > 1: the G group bests -- the first ranked beam of every group, found here on the device -- and the index is
-    the group (every group has a done beam: its beams are all done after the last step)."""
-    from . import rewards as RW
+def _beam_candidates(m, s_all, l_all, p_all, done_n, g_all, groups):
+    """The candidate set of one sample_beam call, from _sorted_done_beams' gathers -> (cands (B, n, S), lps, p (B, n), n_cand or None
+    (all valid), n).  groups == 1: the first min(done_n, m) ranked beams.  groups > 1: the G group bests -- the first ranked beam of
+    every group, found here on the device (every group has a done beam: its beams are all done after the last step)."""
     S = s_all.size(2)
     if groups > 1:
         valid = torch.arange(s_all.size(1), device=s_all.device)[None, :] < done_n[:, None]
         of_group = (g_all[:, None, :] == torch.arange(groups, device=s_all.device, dtype=g_all.dtype)[None, :, None]) & valid[:, None, :]
         first = of_group.to(torch.int8).argmax(2)                                   # first maximum = first beam of the group
         pick = first[:, :, None].expand(-1, -1, S)
-        cands, lps, p, n_cand, m = s_all.gather(1, pick), l_all.gather(1, pick), p_all.gather(1, first), None, groups
-    else:
-        m = min(cs.n, s_all.size(1))
-        cands, lps, p = s_all[:, :m].contiguous(), l_all[:, :m].contiguous(), p_all[:, :m].contiguous()
-        n_cand = done_n.clamp(max=m)
+        return s_all.gather(1, pick), l_all.gather(1, pick), p_all.gather(1, first), None, groups
+    m = min(m, s_all.size(1))
+    return s_all[:, :m].contiguous(), l_all[:, :m].contiguous(), p_all[:, :m].contiguous(), done_n.clamp(max=m), m
+
+
+def _consensus_beams(cs, cands, lps, p, n_cand, m):
+    """sample_beam's pick among its candidates (_beam_candidates) -> (seq, seq_lp) of the chosen candidate per image; the index is
+    the rank (groups == 1) or the group."""
+    from . import rewards as RW
     best = cs.pick(cands, n_cand, p)
     seq, seq_lp, _ = RW.consensus_gather(best, m, cands, lps)
     return seq, seq_lp
+
+
+def keep_candidates_n(opt, beam_size):
+    """opt['keep_candidates']: None without the key, else how many ranked done beams a plain search keeps (consensus_n or
+    beam_size; a diverse search keeps its G group bests)."""
+    if not opt.get('keep_candidates', None):
+        return None
+    m = opt.get('consensus_n', None)
+    return int(beam_size if m is None else m)
 
 
 def _diverse_beams(done_beams, groups):
@@ -395,7 +406,7 @@ def _length_penalty(opt):
 
 
 def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None, consensus=None,
-                       groups=1):
+                       groups=1, keep=None):
     """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
     once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
@@ -411,7 +422,10 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     'group'.
 
     consensus (a parsed _Consensus): the returned seq and its log-probs are the consensus pick among the ranked beams
-    (_consensus_beams) instead of the first of them; the lists keep their meaning and order, and nothing more is read back."""
+    (_consensus_beams) instead of the first of them; the lists keep their meaning and order, and nothing more is read back.
+
+    keep (a dict, with keep['n'] = keep_candidates_n): it receives 'seq' (B, m, S) int64 and 'n_cand' (B,) int32, the candidate
+    set the consensus pick chooses from (_beam_candidates), on the device; with or without `consensus`."""
     dev, B = done_p.device, done_p.size(0)
     score = done_p
     if length_penalty:
@@ -427,8 +441,14 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
     g_all = done_group.gather(1, rank) if done_group is not None else None
     src = _BeamResults(s_all, l_all, p_all, done_n, g_all)
+    if consensus is not None or keep is not None:
+        cands, lps, p, n_cand, m = _beam_candidates(consensus.n if consensus is not None else keep['n'], s_all, l_all, p_all, done_n,
+                                                    g_all, groups)
+        if keep is not None:
+            keep['seq'] = cands
+            keep['n_cand'] = (torch.full((B,), m, dtype=torch.int32, device=dev) if n_cand is None else n_cand.to(torch.int32))
     if consensus is not None:
-        seq, seq_lp = _consensus_beams(consensus, s_all, l_all, p_all, done_n, g_all, groups)
+        seq, seq_lp = _consensus_beams(consensus, cands, lps, p, n_cand, m)
     else:
         seq, seq_lp = s_all[:, 0].contiguous(), l_all[:, 0].contiguous()
     return (seq, seq_lp, _LazyList(B, lambda: src.top_seq()),

@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _length_penalty,
-                     _sorted_done_beams, _Stepper)
+                     _sorted_done_beams, _Stepper, keep_candidates_n)
 
 
 class EnsembleDecoder:
@@ -30,6 +30,7 @@ class EnsembleDecoder:
             raise ValueError('need at least one model')
         self.models = list(models)
         self.consensus = None           # sample_beam with opt['consensus']: {'index', 'scores'} of the pick (device tensors)
+        self.candidates = None          # sample_beam with opt['keep_candidates']: {'seq' (B, m, S), 'n_cand' (B,)} (device tensors)
         self.group = process_group
         world = dist.get_world_size(process_group) if process_group is not None else 1
         self.n_total = total_members if total_members is not None else len(self.models) * world
@@ -93,7 +94,8 @@ class EnsembleDecoder:
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,
         best first); `self.done_beams` as there, and with opt['group_size'] > 1 (diverse beam search) `self.diverse_beams` and the
         'group' key as there; opt['consensus'] (with 'consensus_n', 'consensus_weights') returns the consensus pick and fills
-        `self.consensus` as there.  A one-member ensemble IS that model's sample_beam, bit for bit."""
+        `self.consensus` as there; opt['keep_candidates'] fills `self.candidates` as there.  A one-member ensemble IS that model's
+        sample_beam, bit for bit."""
         W = opt.get('beam_size', 10)
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
@@ -101,6 +103,8 @@ class EnsembleDecoder:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
         cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
         cs = _Consensus.parse(opt, V1, S, W)
+        keep_n = keep_candidates_n(opt, W)
+        keep = None if keep_n is None else {'n': keep_n}
         steppers = []
         for m in self.models:
             comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
@@ -137,8 +141,9 @@ class EnsembleDecoder:
                         'rfn_log_softmax_topk')
         seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b.done_seq, b.done_lp, b.done_p, b.done_n, S,
                                                                              b.max_done, alpha, b.done_group, cs,
-                                                                             div.groups if div is not None else 1)
+                                                                             div.groups if div is not None else 1, keep)
         self.consensus = cs.result if cs is not None else None
+        self.candidates = None if keep is None else {'seq': keep['seq'], 'n_cand': keep['n_cand']}
         self.diverse_beams = _diverse_beams(self.done_beams, div.groups) if div is not None else None
         return seq, seq_lp, top_seq, top_prob
 

@@ -42,16 +42,29 @@ def eval_step(model, crit, fc_feats, att_feats, labels, masks, top_words, seq_pe
 
 
 def eval_split(model, crit, batches, seq_per_img, vocab, beam_size=1, sample_max=1, reason_weight=1.0, metrics=None,
-               language_eval=None, decode_opt=None):
+               language_eval=None, decode_opt=None, diversity=None):
     """eval_utils.eval_split's loop with language_eval's Bleu / ROUGE_L / CIDEr computed on the device.
 
     batches: an iterable of dicts with the loader's 'fc_feats', 'att_feats' (lists of caption-row tensors), 'labels', 'masks',
     'top_words' on the model's device and 'gts' (per image, an (n_refs_i, T) id array; or a padded array with 'n_refs').  The
     module is put in eval mode for the loop and left in the mode it was found in.  -> (mean loss over the batches, metrics dict
     of evalcap.LanguageEval.compute()).  The losses stay on the device until the loop has ended; language_eval: a LanguageEval to
-    feed instead of a new one (its per_image() and skipped are then the caller's to read).  decode_opt: as eval_step."""
+    feed instead of a new one (its per_image() and skipped are then the caller's to read).  decode_opt: as eval_step.
+
+    diversity: an evalcap.DiversityEval to feed with every image's candidate set; the caller reads its compute().  The decoding
+    must then yield several candidates per image: decode_opt['sample_n'] > 1 with sample_max = 0 (the B * n draws; the LanguageEval
+    receives draw 0 of every image), or beam search (beam_size > 1; 'keep_candidates' is set for the call and the candidates are
+    model.candidates: the ranked done beams, or the group bests of a diverse search)."""
     from .evalcap import METRICS, LanguageEval
     lang = language_eval if language_eval is not None else LanguageEval(vocab, METRICS if metrics is None else metrics)
+    n_draws = int((decode_opt or {}).get('sample_n', None) or 1)
+    if diversity is not None:
+        if beam_size > 1:
+            decode_opt = dict(decode_opt or {}, keep_candidates=True)
+        elif n_draws < 2 or sample_max:
+            raise ValueError('diversity needs several candidates per image: sample_n > 1 with sample_max = 0, or beam_size > 1')
+        elif (decode_opt or {}).get('consensus', None) is not None:
+            raise ValueError('sample with \'consensus\' returns one draw per image: the candidates are gone')
     was_training = model.training
     model.eval()
     losses = []
@@ -60,7 +73,14 @@ def eval_split(model, crit, batches, seq_per_img, vocab, beam_size=1, sample_max
             out = eval_step(model, crit, data['fc_feats'], data['att_feats'], data['labels'], data['masks'], data['top_words'],
                             seq_per_img, reason_weight, beam_size, sample_max, decode_opt)
             losses.append(out['loss'].detach().reshape(1).to(torch.float64))
-            lang.add(out['seq'], data['gts'], data.get('n_refs'))
+            seq = out['seq']
+            if beam_size == 1 and n_draws > 1 and seq.size(0) == n_draws * len(data['gts']):
+                if diversity is not None:
+                    diversity.add(seq, data['gts'], data.get('n_refs'), n=n_draws)
+                seq = seq.view(-1, n_draws, seq.size(1))[:, 0]        # draw 0: the call's one caption per image
+            elif diversity is not None:
+                diversity.add(model.candidates['seq'], data['gts'], data.get('n_refs'), n_cand=model.candidates['n_cand'])
+            lang.add(seq, data['gts'], data.get('n_refs'))
     finally:
         model.train(was_training)
     if not losses:

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _native as N
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty,
-                     _Sampling, _sorted_done_beams, _Stepper, early_exit, run_beam_loop, run_greedy_loop)
+                     _Sampling, _sorted_done_beams, _Stepper, early_exit, keep_candidates_n, run_beam_loop, run_greedy_loop)
 
 _INIT = 0.1
 
@@ -450,6 +450,7 @@ class RecurrentFusionModel(nn.Module):
         self.done_beams = []
         self.diverse_beams = None       # sample_beam with group_size > 1: per image the G group bests
         self.consensus = None           # sample / sample_beam with opt['consensus']: {'index', 'scores'} of the pick (device)
+        self.candidates = None          # sample_beam with opt['keep_candidates']: {'seq' (B, m, S), 'n_cand' (B,)} (device)
 
     def init_weights(self):
         """misc/RecurrentFusionModel.py:188-196."""
@@ -798,6 +799,7 @@ class RecurrentFusionModel(nn.Module):
             raise ValueError('force_ids replays given tokens: top_k / top_p / sample_n cannot be combined with it')
         cs = _Consensus.parse_sample(opt, self.vocab_size + 1, self.seq_length, samp, sample_max)
         self.consensus = None
+        self.candidates = None          # a sample_n call's B * n rows are its candidates
         if samp is not None and sample_max:
             if samp.n > 1:
                 raise ValueError('sample_n > 1 with sample_max=1 would return n identical captions: sample with sample_max=0')
@@ -920,7 +922,11 @@ class RecurrentFusionModel(nn.Module):
         the candidate that agrees most with the others under CIDEr-D -- among the first opt['consensus_n'] (default beam_size,
         at most 32) ranked done beams, or among the G group bests of a diverse search -- with opt['consensus_weights'] 'uniform'
         or 'prob'.  `self.consensus` = {'index': (B,) rank (or group) of the pick, 'scores': (B, n)}, device tensors; top_seq,
-        top_prob, done_beams and diverse_beams are unchanged, and the call stays lazy."""
+        top_prob, done_beams and diverse_beams are unchanged, and the call stays lazy.
+
+        opt['keep_candidates'] = True leaves `self.candidates` = {'seq': (B, m, S) int64, 'n_cand': (B,) int32} on the device: the
+        candidate set the consensus pick chooses from (with or without 'consensus'), for evalcap.DiversityEval.  Without the key
+        `self.candidates` is None and the call issues the launches it always did."""
         beam_size = opt.get('beam_size', 10)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
         assert beam_size <= V1, 'lets assume this for now'
@@ -929,6 +935,8 @@ class RecurrentFusionModel(nn.Module):
         W = beam_size
         cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
         cs = _Consensus.parse(opt, V1, S, W)
+        keep_n = keep_candidates_n(opt, W)
+        keep = None if keep_n is None else {'n': keep_n}
         if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
         with torch.no_grad():
@@ -943,10 +951,11 @@ class RecurrentFusionModel(nn.Module):
             run_beam_loop(stepper, bufs, cons, div)
             seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
                                                                             S, bufs.max_done, alpha, bufs.done_group, cs,
-                                                                            div.groups if div is not None else 1)
+                                                                            div.groups if div is not None else 1, keep)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
         self.consensus = cs.result if cs is not None else None
+        self.candidates = None if keep is None else {'seq': keep['seq'], 'n_cand': keep['n_cand']}
         self.diverse_beams = _diverse_beams(done_beams, div.groups) if div is not None else None
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch

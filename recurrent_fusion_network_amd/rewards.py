@@ -28,6 +28,8 @@ from . import _native as N
 
 MAX_T, MAX_REFS, MAX_ID = 64, 32, 32767
 _DOC_COUNTS = (('coco-all', 123287), ('coco-train', 113287), ('coco-val', 5000))   # ciderD_scorer.compute_cider
+# rfn_capset_diversity's outputs, in its argument order
+DIVERSITY_OUTPUTS = ('distinct', 'words', 'div', 'mbleu', 'mbleu_comps', 'mbleu_corpus', 'U', 'eig', 'self_cider')
 
 
 def _ref_docs_of(mode):
@@ -181,6 +183,42 @@ class CiderD(_IdScorer):
                                            N.ptr(U) or None, scores.data_ptr(), best.data_ptr(), ws.data_ptr(), ws.numel(),
                                            N.stream_ptr()), 'rfn_consensus_ciderd')
         return best, scores, U
+
+    def diversity(self, cands, n_cand=None, end_token=False, vocab=MAX_ID, want=DIVERSITY_OUTPUTS):
+        """Caption-set diversity under this scorer's df (rfn.h "caption-set diversity"): cands (B, n, T) int64 ids, n_cand (B,)
+        valid candidates per image (None: all).  end_token=False (the default): words only, as evalcap.LanguageEval reads
+        captions.  -> dict of device tensors: 'distinct' (B, 4) int32, 'words' (B,) int32, 'div' (B, 4), 'mbleu' (B, n, 4),
+        'mbleu_comps' (B, n, 10) int32, 'mbleu_corpus' (n, 4), 'U' (B, n, n), 'eig' (B, n), 'self_cider' (B,), float64 where no
+        type is given; `want` names the ones to compute (the others' launches are skipped).  A bad image (n_cand outside [1, n],
+        an id outside [0, vocab], an empty candidate under end_token=False) has NaN / 0 there.  Uses the scorer's workspace;
+        nothing is read back and nothing synchronises."""
+        dev = cands.device
+        if dev.type != 'cuda':
+            raise N.RfnError('cands must live on the GPU: the diversity metrics have no CPU fallback')
+        if cands.dim() != 3:
+            raise ValueError('cands must be (images, candidates, T), got %s' % (tuple(cands.shape),))
+        unknown = [w for w in want if w not in DIVERSITY_OUTPUTS]
+        if unknown:
+            raise ValueError('unknown diversity outputs %s: choose from %s' % (unknown, ', '.join(DIVERSITY_OUTPUTS)))
+        cands = cands.to(torch.int64).contiguous()
+        B, n, T = cands.shape
+        if n_cand is not None:
+            n_cand = n_cand.to(dev, torch.int32).contiguous()
+            if n_cand.numel() != B:
+                raise ValueError('n_cand needs one entry per image')
+        table = self._table(dev)
+        ws = self._workspace(dev, N.lib.rfn_capset_ws_bytes(B, n, T, int(table is None)))
+        shapes = {'distinct': ((B, 4), torch.int32), 'words': ((B,), torch.int32), 'div': ((B, 4), torch.float64),
+                  'mbleu': ((B, n, 4), torch.float64), 'mbleu_comps': ((B, n, 10), torch.int32),
+                  'mbleu_corpus': ((n, 4), torch.float64), 'U': ((B, n, n), torch.float64), 'eig': ((B, n), torch.float64),
+                  'self_cider': ((B,), torch.float64)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in DIVERSITY_OUTPUTS if k in want}
+        N.check(N.lib.rfn_capset_diversity(cands.data_ptr(), B, n, T, N.ptr(n_cand) or None,
+                                           None if table is None else table.data_ptr(), 0 if table is None else self._slots,
+                                           C.c_double(self.ref_docs or 0.0), vocab, C.c_double(self._sigma), self._flags(end_token),
+                                           *[N.ptr(out.get(k)) or None for k in DIVERSITY_OUTPUTS], ws.data_ptr(), ws.numel(),
+                                           N.stream_ptr()), 'rfn_capset_diversity')
+        return out
 
     def compute_score(self, gts, res):
         """The reference's interface: gts {image_id: [caption, ...]}, res [{'image_id': id, 'caption': [caption]}], captions
@@ -473,6 +511,37 @@ def consensus_gather(best, n, seq=None, seq_lp=None, p=None):
                                        N.ptr(out[1]) or None, N.ptr(p) or None, N.ptr(out[2]) or None, N.stream_ptr()),
             'rfn_consensus_gather')
     return tuple(out)
+
+
+def diversity(scorer, cands, n_cand=None, end_token=False, want=DIVERSITY_OUTPUTS):
+    """Div-m, mBLEU and Self-CIDEr of decoded caption sets: CiderD.diversity on `scorer` (table or corpus df).  Any other scorer
+    raises NotImplementedError (Self-CIDEr is built on the CIDEr-D utility)."""
+    if not isinstance(scorer, CiderD):
+        raise NotImplementedError('the diversity metrics are implemented for the CiderD scorer only, got %s' % type(scorer).__name__)
+    return scorer.diversity(cands, n_cand, end_token, want=want)
+
+
+def group_stats(scores, n, n_cand=None):
+    """Best-of-n, its lowest index and mean-of-n of a score column (rfn_score_group_stats): scores a contiguous float64 (B*n,) or
+    (B*n, k) device tensor (the first column is read), rows image-major; n_cand (B,) valid candidates per image (None: all).
+    -> (best (B,) float64, arg (B,) int64, mean (B,) float64); NaN, -1, NaN for an image one of whose valid scores is NaN.  One
+    launch, no synchronisation."""
+    if scores.dtype != torch.float64 or scores.dim() not in (1, 2) or not scores.is_contiguous() or scores.device.type != 'cuda':
+        raise ValueError('scores must be a contiguous float64 (N,) or (N, k) tensor on the GPU')
+    n = int(n)
+    if n < 1 or scores.shape[0] % n or scores.shape[0] == 0:
+        raise ValueError('%d rows are not n = %d scores per image' % (scores.shape[0], n))
+    dev, B = scores.device, scores.shape[0] // n
+    if n_cand is not None:
+        n_cand = n_cand.to(dev, torch.int32).contiguous()
+        if n_cand.numel() != B:
+            raise ValueError('n_cand needs one entry per image')
+    best = torch.empty(B, dtype=torch.float64, device=dev)
+    arg = torch.empty(B, dtype=torch.int64, device=dev)
+    mean = torch.empty(B, dtype=torch.float64, device=dev)
+    N.check(N.lib.rfn_score_group_stats(scores.data_ptr(), 1 if scores.dim() == 1 else scores.shape[1], B, n, N.ptr(n_cand) or None,
+                                        best.data_ptr(), arg.data_ptr(), mean.data_ptr(), N.stream_ptr()), 'rfn_score_group_stats')
+    return best, arg, mean
 
 
 _DEFAULT = {}

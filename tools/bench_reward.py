@@ -12,7 +12,14 @@
   - --eval: instead, one whole-split evalcap.LanguageEval.compute() (Bleu, ROUGE_L, CIDEr; 5000 images x 5 references, T = 16, the
     split tools/make_evalcap_golden.py --time scores with the reference's scorers) including its one host read, per call and per
     metric.
-Usage: python tools/bench_reward.py [--steps 50] [--warmup 5] | --bleu [--block 2000] [--rounds 7] | --rouge | --eval
+  - --diversity: instead, one full rewards.diversity call (Div-m, mBLEU, Self-CIDEr; every output) next to one
+    rewards.consensus(want_pairs=True) call on the same candidates (B = 128 images x n = 5 x T = 16, corpus df), alternating call
+    by call, each between two device events; the launches of either call as its entry point lists them (include/rfn.h); and the
+    worst eigenvalue error of the call against numpy.linalg.eigvalsh in units of n * 2^-52 * ||K||_F
+    (profiles/diversity_metrics.json; --json PATH also writes the line there).  Both calls are chains of small dependent
+    launches: the figures are launch gaps, and nothing gates them.
+Usage: python tools/bench_reward.py [--steps 50] [--warmup 5] | --bleu [--block 2000] [--rounds 7] | --rouge | --eval |
+       --diversity [--json PATH]
 """
 import argparse
 import json
@@ -134,6 +141,54 @@ def eval_legs(args):
     print(json.dumps(out), flush=True)
 
 
+def diversity_legs(args):
+    from recurrent_fusion_network_amd import rewards as RW
+    dev = torch.device('cuda:0')
+    B, n, T = 128, 5, 16
+    rng = np.random.default_rng(5)
+    pool = rng.integers(1, 9488, (B, 24))                      # an image's candidates draw from one small pool, so they overlap
+    cands = np.take_along_axis(pool[:, None, :].repeat(n, 1), rng.integers(0, 24, (B, n, T)), 2)
+    cands[:, :, -1] = 0
+    for k, j in zip(*np.nonzero(rng.random((B, n)) < 0.7)):
+        cands[k, j, rng.integers(5, T)] = 0
+    cands_d = torch.from_numpy(cands).to(dev)
+    sc = RW.CiderD()
+    legs = {'diversity': lambda: RW.diversity(sc, cands_d), 'consensus_pairs': lambda: RW.consensus(sc, cands_d, want_pairs=True)}
+    for fn in legs.values():
+        for _ in range(args.warmup + 5):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.steps):                                # alternating, call by call
+        for k, fn in legs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            times[k].append(a.elapsed_time(b))
+    d = {k: v.cpu().numpy() for k, v in legs['diversity']().items()}
+    worst = 0.0
+    for k in range(B):
+        K = (d['U'][k] + d['U'][k].T) / 2 / 10
+        unit = n * 2.0 ** -52 * np.linalg.norm(K)
+        worst = max(worst, float(np.abs(d['eig'][k] - np.linalg.eigvalsh(K)).max() / unit))
+    out = {'metric': 'caption-set diversity, ms per rewards.diversity call (every output) next to rewards.consensus(want_pairs=True) '
+                     'on the same candidates: B = 128 images x n = 5 x T = 16, corpus df; device events around one call, '
+                     'alternating', 'unit': 'ms', 'calls': args.steps, 'device': torch.cuda.get_device_name(0),
+           'diversity': spread(times['diversity']), 'consensus_pairs': spread(times['consensus_pairs']),
+           # include/rfn.h: counts, clear, cook, vectors, Div, mBLEU rows, mBLEU corpus, pairs, eigen / ..., pairs, pick
+           'launches': {'diversity': 9, 'consensus_pairs': 6, 'how': 'the entry points\' launch lists (include/rfn.h), corpus df'},
+           'eig_worst_over_n_eps_normK': round(worst, 3),
+           'scores': {'Div_1': round(float(d['div'][:, 0].mean()), 6), 'mBleu_4': round(float(d['mbleu_corpus'][:, 3].mean()), 6),
+                      'Self_CIDEr': round(float(d['self_cider'].mean()), 6)}}
+    line = json.dumps(out)
+    if args.json:
+        with open(args.json, 'w') as f:
+            f.write(line + '\n')
+    print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -143,7 +198,11 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--rouge', action='store_true', help='time the ROUGE-L call')
     ap.add_argument('--eval', action='store_true', help='time a whole-split LanguageEval.compute() at 5000 x 5')
+    ap.add_argument('--diversity', action='store_true', help='time rewards.diversity next to rewards.consensus(want_pairs=True)')
+    ap.add_argument('--json', default=None, help='--diversity: also write the result line to this file')
     args = ap.parse_args()
+    if args.diversity:
+        return diversity_legs(args)
     if args.bleu:
         return bleu_legs(args)
     if args.rouge:
