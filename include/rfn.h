@@ -1305,6 +1305,52 @@ int rfn_capset_diversity(const int64_t* cands, int n_img, int n, int T, const in
 int rfn_score_group_stats(const double* scores, int64_t stride, int n_img, int n, const int32_t* n_cand, double* best, int64_t* arg,
                           double* mean, void* stream);
 
+/* ---- caption scoring (how likely the model finds a caption it is GIVEN; the reference has nothing of the kind) ------------------
+ * The decoding entry points produce captions; these score given ones: per position the log-prob of the given token, its rank in
+ * the step's distribution and the distribution's entropy, per caption the sum and the length -- straight from the logits rows, so
+ * the (rows, S, V+1) log-prob tensor that rfn_decoder_fwd + a gather would write and read back is never materialised
+ * (csrc/rfn_score.hip; one block of 256 per row, the row read once).
+ *   logits: time-major rows r = i * B + b (i < T) of V1 floats, row stride ldl >= V1: steps t0 .. t0+T-1 of B captions.
+ *   target (B, ld_target) int64: column t is the token scored at step t.  An id outside [0, V1) reads as 0, everywhere below.
+ *   Live rule: position (b, t) is LIVE iff target[b, t'] != 0 for every t' < t, and (include_end != 0 or target[b, t] != 0).
+ *   include_end = 1 covers a caption's words and its first 0 (the positions the XE criterion's mask covers); 0 the words only
+ *   (eval_utils' sum(seqLogprobs * (seq > 0))).  Whatever follows the first 0 is never live.
+ *   Outputs at [b * ld_out + t], t = t0 + i, with x the row and tg = target[b, t]:
+ *     tok_lp   = x[tg] - lse, lse the row's log-sum-exp: the bits rfn_log_softmax_fwd writes for that entry       dead: 0
+ *     tok_rank = #{v : x[v] > x[tg] or (x[v] == x[tg] and v < tg)}  (may be NULL)                                   dead: -1
+ *                Tie rule: the position of tg in a stable descending sort of the row, 0 = the argmax -- the order of
+ *                rfn_log_softmax_topk's lists.
+ *     tok_ent  = -sum_v p_v * (x[v] - lse), p_v = exp(x[v] - lse), entries with p_v == 0 count 0  (may be NULL)    dead: 0
+ *   A dead position's block returns before it reads its logits row.  Reductions run in a fixed order (no float atomics): the
+ *   outputs are a function of the row alone, whatever B, T or t0 -- one step at a time (T = 1, t0 = t) gives the bits of one call.
+ *   A row holding a NaN gives NaN tok_lp / tok_ent and a rank that counts only the comparisons that are true; other rows are
+ *   unaffected.  A -inf target gives tok_lp = -inf; -inf entries leave the entropy finite.
+ *   RFN_ERR_SHAPE: B, T or V1 <= 0, t0 < 0, ldl < V1, ld_out < t0 + T.  RFN_ERR_ARG: logits, target or tok_lp NULL. */
+int rfn_score_logits(const float* logits, int64_t ldl, int B, int T, int t0, int V1, const int64_t* target,
+                     int64_t ld_target, int include_end, float* tok_lp, int32_t* tok_rank, float* tok_ent,
+                     int64_t ld_out, void* stream);
+/* Summation order: cap_lp[b] = ((0.0 + tok_lp[b,0]) + tok_lp[b,1]) + ... over the LIVE positions t < T ascending, in fp64, one IEEE
+ * add each (a host loop over the same floats reproduces it exactly); cap_len[b] (may be NULL) = the number of live positions.  One
+ * thread per caption.  RFN_ERR_SHAPE: B, T or V1 <= 0, ld_lp < T.  RFN_ERR_ARG: tok_lp, target or cap_lp NULL. */
+int rfn_score_captions(const float* tok_lp, int64_t ld_lp, const int64_t* target, int64_t ld_target, int B, int T, int V1,
+                       int include_end, double* cap_lp, int32_t* cap_len, void* stream);
+/* The whole pass: rfn_decoder_fwd_ex's teacher-forced pass with train = 0 -- no dropout, whatever d->drop_lm says -- and
+ * rows_per_image = n as far as the time-major logits, rfn_score_logits over all S * B rows (T = S, t0 = 0), and rfn_score_captions
+ * when cap_lp is given.  Log-probs are never written; a position's tok_lp is the bits rfn_decoder_fwd_ex's log_prob holds there.
+ *   ids (B, ld_ids): column s is the token fed at step s (column 0 = BOS); target (B, ld_target): column s is scored at step s.  The
+ *   two may be views of one matrix M (B, S + 1) with column 0 = BOS: ids = M, target = M + 1, the same stride.
+ *   comb (T2, B / n, R), h0 / c0 (B, R), rows image-major, as rfn_decoder_fwd_ex; n > 1 needs the hoisted cell
+ *   (RFN_ERR_UNSUPPORTED otherwise); n < 1 or B % n != 0: RFN_ERR_SHAPE (rfn_decoder_score_ws_bytes: 0).
+ *   tok_lp (B, ld_out >= S); tok_rank, tok_ent, cap_lp, cap_len may be NULL (cap_len needs cap_lp).
+ *   The workspace is rfn_decoder_ws_bytes_ex(d, B, S, 0, n): its logits slab is S * B * V1 floats, so a host bounds it by
+ *   splitting the rows between images -- no bit changes, the batched products are never split along K. */
+size_t rfn_decoder_score_ws_bytes(const rfn_dims* d, int B, int S, int rows_per_image);
+int rfn_decoder_score(const rfn_dims* d, int B, int S, const float* const* params, const float* comb /* (T2, B/n, R) */,
+                      const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids /* column s feeds step s */,
+                      const int64_t* target, int64_t ld_target /* column s is scored at step s */, int include_end,
+                      float* tok_lp, int32_t* tok_rank, float* tok_ent, int64_t ld_out, double* cap_lp, int32_t* cap_len,
+                      void* ws, size_t ws_bytes, int rows_per_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,11 @@ def _load():
         'rfn_capset_ws_bytes': (SZ, [I, I, I, I]),
         'rfn_capset_diversity': (C.c_int, [P, I, I, I, P, P, L, C.c_double, I, C.c_double, C.c_uint] + [P] * 9 + [P, SZ, P]),
         'rfn_score_group_stats': (C.c_int, [P, L, I, I, P, P, P, P, P]),
+        # caption scoring (rfn.h)
+        'rfn_score_logits': (C.c_int, [P, L, I, I, I, I, P, L, I, P, P, P, L, P]),
+        'rfn_score_captions': (C.c_int, [P, L, P, L, I, I, I, I, P, P, P]),
+        'rfn_decoder_score_ws_bytes': (SZ, [DP, I, I, I]),
+        'rfn_decoder_score': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, L, I, P, P, P, L, P, P, P, SZ, I, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

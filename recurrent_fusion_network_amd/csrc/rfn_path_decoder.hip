@@ -149,23 +149,14 @@ static int decoder_fwd_begin(const rfn_dims* d, int B, int n, const float* const
     return mem_batch({{W + Lo.hd, h0, (long)B * R}, {W + Lo.cd, c0, (long)B * R}}, st);
 }
 
-extern "C" int rfn_decoder_fwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
-                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
-                                  void* ws, size_t ws_bytes, int train, uint64_t seed_arg, int rows_per_image, void* st) {
-    RFN_TRY(check_dims(d));
-    RfnSeed seed;
-    RFN_TRY(path_seed(d, seed_arg, &seed));
-    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
-    const int n = rows_per_image;
-    RFN_TRY(rows_per_image_ok(d, B, n));
-    if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
-    if (n > 1 && !log_prob) return RFN_ERR_ARG;   // the logits-only form is found through rfn_decoder_logits: one row per image
-    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
-    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+// The teacher-forced pass on a checked call: everything rfn_decoder_fwd_ex launches, on the workspace laid out as `Lo`.  log_prob
+// == NULL stops at the time-major logits (W + Lo.logits), with any n: rfn_decoder_score reads them there.
+static int decoder_fwd_body(const rfn_dims* d, int B, int S, int n, const float* const* prm, const float* comb, const float* h0,
+                            const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob, float* W,
+                            const DecoderLayout& Lo, RfnSeed seed, void* st) {
     const PIdx P(d);
     const int R = d->R, E = d->E, V1 = d->V1;
     const int GD = gate_width(d->decoder_maxout, R);
-    float* W = (float*)ws;
     const GemmCtx gx{st, W + Lo.gws, GEMM_WS_FLOATS * sizeof(float), d->gemm_flags};
     const GemmCtx gx_whole{st, nullptr, 0, d->gemm_flags};
     RFN_TRY(decoder_fwd_begin(d, B, n, prm, comb, h0, c0, W, Lo, st));
@@ -188,6 +179,46 @@ extern "C" int rfn_decoder_fwd_ex(const rfn_dims* d, int B, int S, const float* 
     RFN_TRY(gemm_logits(S * B, V1, W + Lo.hd + (long)B * R, R, prm[P.logit_w()], prm[P.logit_b()], W + Lo.logits, gx_whole));
     if (log_prob) RFN_TRY(rfn_log_softmax_fwd(W + Lo.logits, V1, S * B, V1, B, (long)S * V1, V1, log_prob, st));
     return RFN_OK;      // log_prob == NULL: the logits stay in the workspace for rfn_xe_logits_fwd (rfn_decoder_logits)
+}
+extern "C" int rfn_decoder_fwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
+                                  void* ws, size_t ws_bytes, int train, uint64_t seed_arg, int rows_per_image, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
+    if (n > 1 && !log_prob) return RFN_ERR_ARG;   // the logits-only form is found through rfn_decoder_logits: one row per image
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
+    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    return decoder_fwd_body(d, B, S, n, prm, comb, h0, c0, ids, ld_ids, log_prob, (float*)ws, Lo, seed, st);
+}
+
+// ---- caption scoring (rfn.h): the inference pass as far as the logits, then rfn_score_logits over all S * B rows -------------
+// train = 0 and no dropout whatever d->drop_lm says (the key is never read); n rows per image reach the logits-only form here.
+extern "C" size_t rfn_decoder_score_ws_bytes(const rfn_dims* d, int B, int S, int rows_per_image) {
+    return rfn_decoder_ws_bytes_ex(d, B, S, 0, rows_per_image);
+}
+extern "C" int rfn_decoder_score(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb, const float* h0,
+                                 const float* c0, const int64_t* ids, int64_t ld_ids, const int64_t* target, int64_t ld_target,
+                                 int include_end, float* tok_lp, int32_t* tok_rank, float* tok_ent, int64_t ld_out,
+                                 double* cap_lp, int32_t* cap_len, void* ws, size_t ws_bytes, int rows_per_image, void* st) {
+    RFN_TRY(check_dims(d));
+    if (B < 1 || S < 1 || ld_out < S) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !h0 || !c0 || !ids || !target || !tok_lp || !ws || (cap_len && !cap_lp)) return RFN_ERR_ARG;
+    rfn_dims dn = *d;
+    dn.drop_lm = 0.f;
+    const DecoderLayout Lo = decoder_layout(&dn, B, S, 0, n);
+    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    float* W = (float*)ws;
+    RFN_TRY(decoder_fwd_body(&dn, B, S, n, prm, comb, h0, c0, ids, ld_ids, nullptr, W, Lo, rfn_seed_value(0), st));
+    RFN_TRY(rfn_score_logits(W + Lo.logits, dn.V1, B, S, 0, dn.V1, target, ld_target, include_end, tok_lp, tok_rank, tok_ent, ld_out, st));
+    if (cap_lp) RFN_TRY(rfn_score_captions(tok_lp, ld_out, target, ld_target, B, S, dn.V1, include_end, cap_lp, cap_len, st));
+    return RFN_OK;
 }
 extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
                                const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,

@@ -1,5 +1,5 @@
 // Device helpers of the kernels that give one block of 256 threads to a row of the vocabulary (rfn_logsoftmax.hip,
-// rfn_criteria.hip, rfn_beam.hip): the block reductions, the row's log-sum-exp, the (value, token) order of a
+// rfn_criteria.hip, rfn_beam.hip, rfn_score.hip): the block reductions, the row's log-sum-exp, the (value, token) order of a
 // descending sort, and a lane's sorted top-W list.  Reductions run in a fixed order (wave shuffles, then four LDS slots): no
 // float atomics, results are bitwise reproducible.  A helper that one file uses stays in that file.
 #pragma once

@@ -1,5 +1,6 @@
 """Free-running decoding, shared by RecurrentFusionModel.sample / sample_beam / one_time_step and the EnsembleDecoder: the
-decoder state, the decoding constraints, the loops' buffers, the two device-loop calls and the done-beam ranking.  The model
+decoder state, the decoding constraints, the loops' buffers, the two device-loop calls and the done-beam ranking -- and, for
+captions that are given instead of decoded, the option parse and buffers of score() and n-best rescoring.  The model
 is an argument (its `_dims_for`, `_param_table`, `_params_of` and `_decoder_slots` are used); it is never imported here."""
 from __future__ import annotations
 
@@ -356,6 +357,128 @@ class _Consensus:
         best, scores, _ = RW.consensus(self.scorer, cands, n_cand, weights)
         self.result = {'index': best, 'scores': scores}
         return best
+
+
+class _Scoring:
+    """Caption scoring of one call (rfn.h "caption scoring"; RecurrentFusionModel.score / EnsembleDecoder.score): opt['n'] (int >= 1
+    captions per image when seq is (B * n, T); a (B, n, T) seq carries its own), opt['length_penalty'] = alpha >= 0 ('score' =
+    logprob / length^alpha), opt['outputs'] (names among 'rank', 'entropy': the optional per-token outputs), opt['include_end']
+    (bool, default True: the caption's END is scored with its words) and opt['max_rows'] (int >= 1: caption rows per native call).
+    Unknown keys and bad values raise ValueError; nothing here touches a device."""
+
+    KEYS = ('n', 'length_penalty', 'outputs', 'include_end', 'max_rows')
+    OUTPUTS = ('rank', 'entropy')
+    SLAB_BYTES = 1 << 30           # default max_rows: the (steps * rows, V+1) logits of one native call stay under this
+
+    @classmethod
+    def parse(cls, opt):
+        bad = sorted(k for k in opt if k not in cls.KEYS)
+        if bad:
+            raise ValueError('score takes %s, not %s' % (', '.join(cls.KEYS), ', '.join(map(repr, bad))))
+        s = cls()
+        s.n = cls._count(opt, 'n')
+        s.alpha = _length_penalty(opt)
+        outs = opt.get('outputs', None)
+        outs = () if outs is None else ((outs,) if isinstance(outs, str) else tuple(outs))
+        unknown = [o for o in outs if o not in cls.OUTPUTS]
+        if unknown:
+            raise ValueError("outputs names 'rank' and / or 'entropy', got %r" % (unknown,))
+        s.rank, s.entropy = 'rank' in outs, 'entropy' in outs
+        end = opt.get('include_end', True)
+        if not isinstance(end, (bool, int)) or end not in (0, 1):
+            raise ValueError('include_end is True or False, got %r' % (end,))
+        s.include_end = bool(end)
+        s.max_rows = cls._count(opt, 'max_rows')
+        return s
+
+    @staticmethod
+    def _count(opt, key):
+        v = opt.get(key, None)
+        if v is None:
+            return None
+        try:
+            ok = not isinstance(v, bool) and int(v) == v and int(v) >= 1
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('%s must be an integer >= 1, got %r' % (key, v))
+        return int(v)
+
+    def layout(self, shape, B, seq_length):
+        """seq of `shape` for B images -> (rows, n, T): (B, T), (B, n, T), or (B * n, T) with opt['n']."""
+        shape = tuple(int(x) for x in shape)
+        if len(shape) == 3:
+            if shape[0] != B or shape[1] < 1 or (self.n is not None and self.n != shape[1]):
+                raise ValueError('seq %s does not hold n%s captions for each of %d images'
+                                 % (shape, '' if self.n is None else ' = %d' % self.n, B))
+            n, T = shape[1], shape[2]
+        elif len(shape) == 2:
+            n, T = (1 if self.n is None else self.n), shape[1]
+            if shape[0] != B * n:
+                raise ValueError('seq %s does not hold %d x %d caption rows' % (shape, B, n))
+        else:
+            raise ValueError('seq must be (B, T), (B, n, T) or (B * n, T), got %s' % (shape,))
+        if not 1 <= T <= seq_length + 1:
+            raise ValueError('seq holds %d columns, 1 .. seq_length + 1 = %d are scored' % (T, seq_length + 1))
+        return B * n, n, T
+
+    def rows_per_call(self, n, steps, V1):
+        """max_rows rounded down to a multiple of n, at least n."""
+        mr = self.max_rows if self.max_rows is not None else self.SLAB_BYTES // (4 * steps * V1)
+        return max(n, mr // n * n)
+
+
+class ScoreBuffers:
+    """What a scoring pass over `rows` captions reads and writes: `feed` (rows, steps + 1) int64 with column 0 = BOS, the words
+    behind it and zeros to the end -- column s feeds step s, column s + 1 is scored there -- and the outputs."""
+
+    def __init__(self, so, seq, rows, T, seq_length, dev):
+        L = min(T, seq_length)
+        self.so, self.rows, self.steps = so, rows, L + 1
+        self.feed = torch.zeros(rows, L + 2, dtype=torch.long, device=dev)
+        self.feed[:, 1:L + 1] = seq.reshape(rows, T)[:, :L].to(dev)
+        self.target = self.feed[:, 1:]
+        self.tok_lp = torch.empty(rows, L + 1, device=dev)
+        self.rank = torch.empty(rows, L + 1, dtype=torch.int32, device=dev) if so.rank else None
+        self.ent = torch.empty(rows, L + 1, device=dev) if so.entropy else None
+        self.cap_lp = torch.empty(rows, dtype=torch.float64, device=dev)
+        self.cap_len = torch.empty(rows, dtype=torch.int32, device=dev)
+
+    def result(self):
+        """The dict score() returns.  'score' = logprob / length^alpha, one IEEE division in fp64 by the host table
+        _sorted_done_beams ranks with (length 0 divides by 1)."""
+        if self.so.alpha == 0.0:
+            score = self.cap_lp.clone()                     # every divisor is 1.0
+        else:
+            # pinned and non-blocking: a pageable upload would make the host wait here for everything queued so far
+            table = torch.tensor([1.0] + [float(k) ** self.so.alpha for k in range(1, self.steps + 1)], dtype=torch.float64)
+            score = self.cap_lp / table.pin_memory().to(self.cap_lp.device, non_blocking=True)[self.cap_len.long()]
+        out = {'token_logprobs': self.tok_lp, 'logprob': self.cap_lp, 'length': self.cap_len, 'score': score}
+        if self.rank is not None:
+            out['rank'] = self.rank
+        if self.ent is not None:
+            out['entropy'] = self.ent
+        return out
+
+
+def rescore(scorer, fc_feats, att_feats, cands, n_cand=None, opt={}):
+    """n-best rescoring: score an image's m candidates with `scorer` (anything with .score: a RecurrentFusionModel, an
+    EnsembleDecoder) -> (best (B,) int64, scores (B, m) f64).  cands (B, m, T) int64 as `model.candidates['seq']` after
+    keep_candidates, or a sample_n call's rows viewed per image; n_cand (B,) counts the valid ones (None: all m).  scores[k, j] is
+    the scorer's 'score' (opt['length_penalty'] applies), -inf for j >= n_cand[k]; best[k] is the first maximum, -1 where
+    n_cand[k] == 0 (rewards.consensus_gather writes zeros for it).  Nothing is read back."""
+    if cands.dim() != 3:
+        raise ValueError('cands must be (B, m, T), got %s' % (tuple(cands.shape),))
+    B, m = cands.size(0), cands.size(1)
+    scores = scorer.score(fc_feats, att_feats, cands, opt)['score'].view(B, m)
+    if n_cand is not None:
+        valid = torch.arange(m, device=scores.device)[None, :] < n_cand.to(scores.device)[:, None]
+        scores = torch.where(valid, scores, torch.full_like(scores, float('-inf')))
+    top = scores.max(1, keepdim=True).values
+    best = (scores == top).to(torch.int8).argmax(1)                               # first maximum
+    if n_cand is not None:
+        best = torch.where(n_cand.to(best.device) > 0, best, torch.full_like(best, -1))
+    return best, scores
 
 
 def _beam_candidates(m, s_all, l_all, p_all, done_n, g_all, groups):

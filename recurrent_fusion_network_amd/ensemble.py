@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _length_penalty,
-                     _sorted_done_beams, _Stepper, keep_candidates_n)
+                     _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, keep_candidates_n)
 
 
 class EnsembleDecoder:
@@ -87,6 +87,40 @@ class EnsembleDecoder:
             out = logp_all[:, t]
             N.check(N.lib.rfn_log_softmax_fwd(logit_sum.data_ptr(), V1, B, V1, B, out.stride(0), 0, out.data_ptr(), st))
         return bufs.read_back()        # nothing is read back before this: the call synchronises here, once
+
+    @torch.no_grad()
+    def score(self, fc_feats, att_feats, seq, opt={}):
+        """RecurrentFusionModel.score under the members' averaged distribution: the same arguments, the same dict.  The members
+        step teacher-forced on the given tokens, each step's mean logits go through rfn_score_logits (T = 1, t0 = t) and the
+        captions are summed at the end; only one step's (rows, V+1) logits exist at a time, so opt['max_rows'] has nothing to
+        bound here.  With n > 1 captions per image every member's thought vectors are repeated physically (a stepper's rows do
+        not share them).  A one-member ensemble IS that model's score, bit for bit."""
+        m0 = self.models[0]
+        so = _Scoring.parse(opt)
+        B = m0._check_inputs(fc_feats, att_feats)
+        rows, n, T = so.layout(seq.shape, B, m0.seq_length)
+        V1 = m0.vocab_size + 1
+        steppers = []
+        for m in self.models:
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            if n > 1:
+                comb, h, c = comb.repeat_interleave(n, dim=1), h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
+            steppers.append(_Stepper(m, comb.contiguous(), h.clone(), c.clone()))
+        dev = steppers[0].h.device
+        st = N.stream_ptr()
+        bufs = ScoreBuffers(so, seq, rows, T, m0.seq_length, dev)
+        logit_sum = torch.empty(rows, V1, device=dev)
+        logit_m = torch.empty(rows, V1, device=dev)
+        feed = bufs.feed.t().contiguous()                  # row t = the tokens fed at step t
+        for t in range(bufs.steps):
+            self._averaged_step(steppers, feed[t], logit_sum, logit_m)
+            N.check(N.lib.rfn_score_logits(logit_sum.data_ptr(), V1, rows, 1, t, V1, bufs.target.data_ptr(), bufs.target.stride(0),
+                                           int(so.include_end), bufs.tok_lp.data_ptr(), N.ptr(bufs.rank), N.ptr(bufs.ent),
+                                           bufs.tok_lp.stride(0), st), 'rfn_score_logits')
+        N.check(N.lib.rfn_score_captions(bufs.tok_lp.data_ptr(), bufs.tok_lp.stride(0), bufs.target.data_ptr(), bufs.target.stride(0),
+                                         rows, bufs.steps, V1, int(so.include_end), bufs.cap_lp.data_ptr(), bufs.cap_len.data_ptr(),
+                                         st), 'rfn_score_captions')
+        return bufs.result()
 
     @torch.no_grad()
     def sample_beam(self, fc_feats, att_feats, opt={}):

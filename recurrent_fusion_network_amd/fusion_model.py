@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from . import _native as N
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty,
-                     _Sampling, _sorted_done_beams, _Stepper, early_exit, keep_candidates_n, run_beam_loop, run_greedy_loop)
+                     _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit, keep_candidates_n, run_beam_loop,
+                     run_greedy_loop)
 
 _INIT = 0.1
 
@@ -905,6 +906,51 @@ class RecurrentFusionModel(nn.Module):
             self.consensus = cs.result
             return bufs.read_back_picked(best, n)
         return bufs.read_back()        # waits for the loop: the call's one read-back
+
+    @torch.no_grad()
+    def score(self, fc_feats, att_feats, seq, opt={}):
+        """How likely the model finds the captions it is GIVEN (rfn.h "caption scoring"; the reference has nothing of the kind) ->
+        a dict of device tensors over the caption rows (image-major):
+            'token_logprobs' (rows, steps) f32   log-prob of each given token, 0 at positions that are not scored
+            'logprob' (rows,) f64                their sum, ascending, in fp64
+            'length' (rows,) int32               how many positions were scored
+            'score' (rows,) f64                  logprob / length^alpha, alpha = opt['length_penalty'] (default 0)
+            'rank' (rows, steps) int32, 'entropy' (rows, steps) f32   when opt['outputs'] names them: the given token's place in
+                                                 the step's distribution (0 = the argmax, -1 where not scored) and that
+                                                 distribution's entropy in nats
+        seq: word ids as sample() returns them (no BOS column, zeros after the caption): (B, T), (B, n, T), or (B * n, T) with
+        opt['n'], T <= seq_length + 1; the first min(T, seq_length) columns are read as words (labels[:, 1:] of the loader is a
+        valid argument) and steps = min(T, seq_length) + 1 -- nothing is read back to trim them.  A caption's words and its END are
+        scored (the XE criterion's mask); opt['include_end'] = False scores the words only (eval_utils' sum(seqLogprobs * (seq >
+        0))).  Always runs under no_grad with dropout off, whatever the module's mode.  Stages I / II run once per image; with n > 1
+        the n rows of an image read its thought vectors.  The (rows, steps, V+1) log-probs are never materialised: the logits of
+        at most opt['max_rows'] rows (default: 1 GiB of them) exist at a time, and the chunking changes no bit."""
+        so = _Scoring.parse(opt)
+        B = self._check_inputs(fc_feats, att_feats)
+        rows, n, T = so.layout(seq.shape, B, self.seq_length)
+        if n > 1 and int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
+            raise N.RfnError('n captions per image need the hoisted decoder cell (path_flags select another form)')
+        comb, h, c, _ = self._prefix(fc_feats, att_feats, False, 0)
+        dev = comb.device
+        if n > 1:
+            h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
+        h, c = h.contiguous(), c.contiguous()
+        bufs = ScoreBuffers(so, seq, rows, T, self.seq_length, dev)
+        S, V1 = bufs.steps, self.vocab_size + 1
+        d = self._dims_for(False)
+        table = self._param_table(self._params_of(self._decoder_slots), self._decoder_slots)
+        per_call = so.rows_per_call(n, S, V1)
+        ws_bytes = N.lib.rfn_decoder_score_ws_bytes(C.byref(d), min(rows, per_call), S, n)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        for r0 in range(0, rows, per_call):
+            r1 = min(rows, r0 + per_call)
+            cb = comb if (r0 == 0 and r1 == rows) else comb[:, r0 // n:r1 // n].contiguous()
+            sl = lambda t: N.ptr(None if t is None else t[r0:r1])  # noqa: E731
+            N.check(N.lib.rfn_decoder_score(C.byref(d), r1 - r0, S, table, cb.data_ptr(), sl(h), sl(c), sl(bufs.feed),
+                                            bufs.feed.stride(0), sl(bufs.target), bufs.target.stride(0), int(so.include_end),
+                                            sl(bufs.tok_lp), sl(bufs.rank), sl(bufs.ent), bufs.tok_lp.stride(0), sl(bufs.cap_lp),
+                                            sl(bufs.cap_len), ws.data_ptr(), ws_bytes, n, N.stream_ptr()), 'rfn_decoder_score')
+        return bufs.result()
 
     def sample_beam(self, fc_feats, att_feats, opt={}):
         """misc/RecurrentFusionModel.py:352-543, batched and device-resident.
