@@ -913,6 +913,80 @@ typedef struct rfn_beam_diversity {
     float lambda;             /* >= 0 */
     int32_t* done_group;      /* (NB, max_done), device; may be NULL when groups == 1 */
 } rfn_beam_diversity;
+/* ---- lexically constrained beam search: required words (off by default; the reference has none) -----------------------------
+ * After Anderson et al. 2017, "Guided open vocabulary image captioning with constrained beam search".  Per image there are C
+ * constraint sets, 0 <= C <= RFN_LEX_MAX_SETS; a set is a disjunction of token ids in [1, V1) (token 0, END, is never in one)
+ * and is satisfied once the caption holds any of its ids.  The host hands over the image's unique ids, want (NB, NW) int32
+ * padded with -1, and want_bits (NB, NW) int32 with bit i set when the id is in set i (an id in two sets carries two bits);
+ * NW <= RFN_LEX_MAX_IDS.  init_state (NB) int32 holds the bits of the image's EMPTY sets: an image with fewer than C sets has its
+ * missing sets satisfied from the start.
+ *
+ * Search state.  G = 2^C states (bit masks of satisfied sets), each owning a beam of Wb rows: state s owns rows s*Wb ..
+ * s*Wb+Wb-1 of the image's W = G * Wb <= 32 rows.  state_n (NB, G) int32 counts the occupied rows of every state; occupied rows
+ * are packed at the front.  Before step 1 only the first row of state init_state[k] is occupied (at t == 1 the step takes the
+ * occupancy from init_state and does not read state_n).  Unoccupied rows are inert: order = identity, next_ids = 0, no
+ * candidates; their beam_seq / beam_lp / beam_sum entries are whatever an earlier step left there and mean nothing.
+ *
+ * One step t (1 .. S) of one image visits the target states in ascending order s = 0 .. G-1, every one reading the beams as they
+ * were BEFORE the step:
+ *   - a live row is an occupied row whose last token is not 0 (at t == 1 the single occupied row is live);
+ *   - a stay candidate of live row q in state s' is an entry (local, v) of the row's top list whose destination s' | bits(v)
+ *     equals s' (bits(v) = 0 for a token that is not wanted), taken in (column outer, row inner) order;
+ *   - a move candidate of row q is a want entry j with bits_j & ~s' != 0: local = wantv[q][j], destination s' | bits_j, taken in
+ *     (want index outer, row inner) order.  A want token whose sets are all satisfied already is only ever a stay candidate, so
+ *     no token is offered twice;
+ *   - a candidate whose local is -inf is dropped: a blocked or absent token cannot occupy a row;
+ *   - the candidates of target s are listed by source state ascending; within a source state come its stay candidates when
+ *     s' == s and its move candidates with destination s otherwise;
+ *   - p = fp32(beam_sum[q] + local); the order is stable and descending by p; the first min(Wb, candidates) become rows 0 .. of
+ *     state s and state_n[k, s] is that count.  DEPARTURE from rfn_beam_step: a state with fewer candidates than Wb does not keep
+ *     stale rows -- the rest of its rows are unoccupied;
+ *   - a selected candidate that emits 0, or any selected candidate at t == S, is appended to the done beams in construction order
+ *     (state, then rank), done_state[k, slot] = s beside it; max_done = W * S bounds them as before; beam_lp, beam_sum, done_lp
+ *     and done_p are handled exactly as in rfn_beam_step_topk;
+ *   - active[k] becomes 0 when no state has a candidate.
+ * Keys that are NaN are not ordered; the step then stays in bounds but selects no defined set (as the diverse search).
+ *
+ * Why the W best entries of a row suffice.  Define the search on full rows (every row's V1 entries sorted descending by value,
+ * then token id).  Move candidates come from the want values, not from the lists.  Of a row's first W columns at most NW change
+ * the state, so at least W - NW stay; a row can place at most Wb candidates in its own state, and a stay candidate beyond column
+ * W has at least W - NW stay candidates of the same row before it, with p not smaller (the fp32 add is monotone) and earlier in
+ * construction order.  With NW <= W - Wb that candidate is never among the first Wb, and a stable sort keeps the relative order
+ * of the rest: the search on the W-wide lists equals the search on full rows.  With V1 < W the list is the whole row.  The entry
+ * points refuse NW > W - Wb.
+ *
+ * The returned caption (host, torch ops on the device): done beams ordered by the number of satisfied sets descending, within
+ * that by p (or p / len^alpha) descending, ties in construction order.
+ *
+ * rfn_log_softmax_topk_want: rfn_log_softmax_topk_masked plus wantv (rows, NW): wantv[r, j] = the log-prob of token
+ * want[r / row_div, j] (want has row stride ld_want >= NW) in the bits rfn_log_softmax_fwd writes, -inf for an id outside
+ * [0, V1) (the -1 padding) or a blocked token.  topv / topi are bit for bit rfn_log_softmax_topk_masked's.  want == NULL forwards
+ * to rfn_log_softmax_topk_masked.  RFN_ERR_SHAPE: as there, NW < 1, NW > RFN_LEX_MAX_IDS, ld_want < NW, row_div < 1.
+ *
+ * rfn_beam_step_lex: one block per image, the target states in a serial loop, every candidate computing its own rank.  C == 0
+ * forwards to rfn_beam_step_topk.  RFN_ERR_SHAPE: C < 0 or > RFN_LEX_MAX_SETS, W % 2^C != 0, NW < 0 or > RFN_LEX_MAX_IDS,
+ * NW > W - Wb, W > 32, S > 64. */
+#define RFN_LEX_MAX_SETS 3
+#define RFN_LEX_MAX_IDS 16
+int rfn_log_softmax_topk_want(const float* logits, int64_t ldl, int rows, int V1, int W, int row_div, const int32_t* want,
+                              int64_t ld_want, int NW, const int32_t* blk, int64_t ld_blk, const int32_t* blk_n, float* topv,
+                              int32_t* topi, float* wantv, void* stream);
+int rfn_beam_step_lex(const float* topv, const int32_t* topi, const float* wantv, const int32_t* want, const int32_t* want_bits,
+                      int NW, int C, int V1, int W, int S, int t, int NB, int max_done, int64_t* beam_seq, float* beam_lp,
+                      float* beam_sum, int32_t* order, int64_t* next_ids, int64_t* done_seq, float* done_lp, float* done_p,
+                      int32_t* done_n, int32_t* state_n, int32_t* done_state, const int32_t* init_state, int32_t* active,
+                      void* stream);
+/* What rfn_beam_loop_ex3 takes besides the constraints and the diversity. */
+typedef struct rfn_beam_lexical {
+    int32_t n_sets;               /* C in 1 .. RFN_LEX_MAX_SETS; W % 2^C == 0 */
+    int32_t n_want;               /* NW in 1 .. RFN_LEX_MAX_IDS, NW <= W - W / 2^C */
+    const int32_t* want;          /* (NB, n_want), device, padded with -1 */
+    const int32_t* want_bits;     /* (NB, n_want), device */
+    const int32_t* init_state;    /* (NB), device */
+    float* wantv;                 /* (NB * W, n_want) scratch */
+    int32_t* state_n;             /* (NB, 2^C) */
+    int32_t* done_state;          /* (NB, max_done) */
+} rfn_beam_lexical;
 /* dst[r,:] = src[order[r],:]  (src != dst) */
 int rfn_gather_rows(const float* src, float* dst, const int32_t* order, int rows, int R, void* stream);
 
@@ -1090,6 +1164,17 @@ int rfn_beam_loop_ex2(const rfn_dims* d, int NB, int W, int S, const float* cons
                       float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
                       float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
                       const rfn_decode_constraints* cons, const rfn_beam_diversity* div, void* stream);
+/* rfn_beam_loop_ex2 as a lexically constrained search (above): per step rfn_log_softmax_topk_want in place of
+ * rfn_log_softmax_topk_masked and rfn_beam_step_lex in place of rfn_beam_step_topk; W counts all rows of an image (2^C states of
+ * W / 2^C beams).  cons composes: a blocked token is -inf in the lists and in the want values.  lex == NULL: the calls and the bits
+ * of rfn_beam_loop_ex2, which forwards here.  RFN_ERR_UNSUPPORTED: lex with div->groups > 1.  RFN_ERR_SHAPE as rfn_beam_step_lex
+ * (and n_sets < 1, n_want < 1); RFN_ERR_ARG: a NULL member of lex. */
+int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const float* const* params, const float* comb,
+                      const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp, int64_t* beam_seq,
+                      float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
+                      float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
+                      const rfn_decode_constraints* cons, const rfn_beam_diversity* div, const rfn_beam_lexical* lex,
+                      void* stream);
 
 /* ---- self-critical reward: CIDEr-D of token-id captions (get_rewards.py:39-112, cider/pyciderevalcap/ciderD) ---------
  * CiderD(n=4, sigma) as compute_reward calls it (csrc/rfn_reward.hip).  A caption is the ids of its row up to and including

@@ -96,7 +96,14 @@ class BeamDiversity(C.Structure):
     _fields_ = [('groups', C.c_int32), ('lambda_', C.c_float), ('done_group', C.c_void_p)]
 
 
+class BeamLexical(C.Structure):
+    """rfn_beam_lexical (rfn.h)."""
+    _fields_ = [('n_sets', C.c_int32), ('n_want', C.c_int32), ('want', C.c_void_p), ('want_bits', C.c_void_p),
+                ('init_state', C.c_void_p), ('wantv', C.c_void_p), ('state_n', C.c_void_p), ('done_state', C.c_void_p)]
+
+
 DECODE_MAX_IDS = 64
+LEX_MAX_SETS, LEX_MAX_IDS = 3, 16
 
 
 def _load():
@@ -110,7 +117,7 @@ def _load():
     lib.rfn_error_string.restype = C.c_char_p
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
     DP, CP, SP = C.POINTER(Dims), C.POINTER(DecodeConstraints), C.POINTER(DecodeSampling)
-    BDP = C.POINTER(BeamDiversity)
+    BDP, BLP = C.POINTER(BeamDiversity), C.POINTER(BeamLexical)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -205,6 +212,9 @@ def _load():
         'rfn_decoder_loop_ex2': (C.c_int, [DP, I, I, P, P, P, P, P, I, F, P, P, L, L, P, L, P, L, P, P, P, SZ, U64, CP, SP, P]),
         'rfn_beam_loop_ex': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, P]),
         'rfn_beam_loop_ex2': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, P]),
+        'rfn_beam_loop_ex3': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, BLP, P]),
+        'rfn_log_softmax_topk_want': (C.c_int, [P, L, I, I, I, I, P, L, I, P, L, P, P, P, P, P]),
+        'rfn_beam_step_lex': (C.c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I] + [P] * 14),
         'rfn_decoder_fwd_sampled': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, P]),
         'rfn_beam_loop': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, P]),
         'rfn_decoder_step_ws_bytes': (SZ, [DP, I]),

@@ -11,7 +11,8 @@
 //   * done beams appended in construction order when END is emitted or t == seq_length (:508-514);
 //   * an image with no candidate left stops (:480-481).
 // Nothing is read back per step; the host sorts the (few) done beams once at the end.
-// The diverse search (beam groups with a Hamming penalty, which the reference does not have) is the second kernel below.
+// The diverse search (beam groups with a Hamming penalty, which the reference does not have) is the second kernel below, the
+// lexically constrained search (required words: one beam per subset of satisfied sets) the third.
 #include "rfn_rows.h"
 
 #define BEAM_MAX_W 32     /* beams per image; the full-row form (rfn_beam_step: phase 1 below) serves up to BEAM_WAVES of them */
@@ -396,6 +397,194 @@ extern "C" int rfn_beam_step_div(const float* topv, const int32_t* topi, int V1,
     hipLaunchKernelGGL(beam_step_div_k, dim3(NB), dim3(BEAM_DIV_THREADS), 0, (hipStream_t)stream, topv, topi, V1, W, G, lambda, S,
                        t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids, done_seq, done_lp, done_p, done_n,
                        done_group, active);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// =============================================================================================
+// lexically constrained beam search: 2^C states of Wb = W / 2^C beams (rfn.h "lexically constrained beam search")
+// =============================================================================================
+#define BEAM_LEX_THREADS 256
+#define BEAM_LEX_MAXG (1 << RFN_LEX_MAX_SETS)
+// Candidate slots of one target state: its own rows' list columns (cols * Wb <= 32 * Wb) and the other states' rows' want entries
+// (NW * (W - Wb)).  With W <= 32, Wb <= W / 2 and NW <= min(16, W - Wb) the largest is Wb = 16, W = 32, NW = 16: 512 + 256.
+#define BEAM_LEX_MAXC (BEAM_MAX_W * (BEAM_MAX_W / 2) + RFN_LEX_MAX_IDS * (BEAM_MAX_W / 2))
+// Static LDS: ys + ix 8 KiB, prev_seq + prev_lp 16 KiB, four candidate arrays 12 KiB, the want values 2 KiB, small change: about
+// 38.5 KiB of the 64 KiB a block may declare.
+
+// One block per image, the target states one after the other, all of them reading the LDS snapshot of the beams before the step
+// (a target reads rows of the states below it, which this step has already rewritten in memory).  Per target: every slot of the
+// construction order (source states ascending; a source's want entries j outer / row inner when it moves here, its list columns
+// c outer / row inner when it is the target itself) is filled or marked invalid (row not live, another destination, -inf); every
+// valid slot counts the valid slots that precede it in the stable descending order of p -- its rank, as beam_step_div_k; thread
+// 0 hands out the done slots; all threads write the forks (beam_fork_write) and the inert rest of the state's rows.
+__global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
+    const float* __restrict__ topv, const int32_t* __restrict__ topi, const float* __restrict__ wantv,
+    const int32_t* __restrict__ want, const int32_t* __restrict__ want_bits, int NW, int C, int V1, int W, int S, int t, int NB,
+    int MAXD, int64_t* __restrict__ bs, float* __restrict__ bl, float* __restrict__ bsum, int32_t* __restrict__ order,
+    int64_t* __restrict__ nxt, int64_t* __restrict__ done_seq, float* __restrict__ done_lp, float* __restrict__ done_p,
+    int32_t* __restrict__ done_n, int32_t* __restrict__ state_n, int32_t* __restrict__ done_state,
+    const int32_t* __restrict__ init_state, int32_t* __restrict__ active) {
+    __shared__ float ys[BEAM_MAX_W][BEAM_MAX_W];
+    __shared__ int ix[BEAM_MAX_W][BEAM_MAX_W];
+    __shared__ float wv[BEAM_MAX_W][RFN_LEX_MAX_IDS];
+    __shared__ int wid[RFN_LEX_MAX_IDS], wb[RFN_LEX_MAX_IDS];
+    __shared__ int prev_seq[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ float prev_lp[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ float prev_sum[BEAM_MAX_W];
+    __shared__ int prev_n[BEAM_LEX_MAXG];
+    __shared__ float cand_p[BEAM_LEX_MAXC], cand_r[BEAM_LEX_MAXC];
+    __shared__ int cand_c[BEAM_LEX_MAXC], cand_q[BEAM_LEX_MAXC];      // cand_q < 0: an invalid slot
+    __shared__ int sel_ci[BEAM_MAX_W], slot_s[BEAM_MAX_W];
+    __shared__ int nvalid_s, first_s, nnew_s;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const int G = 1 << C, Wb = W / G, cols = min(W, V1);
+    if (!active[k]) {  // this image's search has ended: keep its rows inert
+        if (tid < W) {
+            order[k * W + tid] = k * W + tid;
+            nxt[k * W + tid] = 0;
+        }
+        return;
+    }
+    for (int i = tid; i < W * cols; i += BEAM_LEX_THREADS) {
+        const int q = i / cols, c = i - q * cols;
+        ys[q][c] = topv[(long)(k * W + q) * W + c];
+        ix[q][c] = topi[(long)(k * W + q) * W + c];
+    }
+    for (int i = tid; i < W * NW; i += BEAM_LEX_THREADS) {
+        const int q = i / NW, j = i - q * NW;
+        wv[q][j] = wantv[(long)(k * W + q) * NW + j];
+    }
+    if (tid < NW) {   // an id outside [1, V1) (the -1 padding) is in no set: never a move, never met in a list
+        const int id = want[k * NW + tid];
+        wid[tid] = id;
+        wb[tid] = (id >= 1 && id < V1) ? (want_bits[k * NW + tid] & (G - 1)) : 0;
+    }
+    for (int i = tid; i < (t - 1) * W; i += BEAM_LEX_THREADS) {  // the beams before this step (forks read the OLD columns)
+        const int s = i / W, w = i - s * W;
+        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
+        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
+    }
+    if (tid < W) prev_sum[tid] = bsum[k * W + tid];
+    if (tid < G) {   // before step 1 only the first row of the initial state is occupied
+        int n = (t == 1) ? (tid == (init_state[k] & (G - 1)) ? 1 : 0) : state_n[k * G + tid];
+        prev_n[tid] = min(max(n, 0), Wb);
+    }
+    __syncthreads();
+    int n = 0, any = 0;                              // thread 0's: done beams so far, a state had a candidate
+    if (tid == 0) n = done_n[k];
+    for (int s = 0; s < G; ++s) {
+        const int b0 = s * Wb;
+        int total = 0;                               // the slots of target s
+        for (int sp = 0; sp <= s; ++sp)
+            if ((sp & ~s) == 0) total += (sp == s ? cols : NW) * prev_n[sp];
+        if (tid == 0) {
+            nvalid_s = 0;
+            first_s = BEAM_LEX_MAXC;
+        }
+        if (tid < Wb) sel_ci[tid] = -1;
+        __syncthreads();
+        int mine = 0, first = BEAM_LEX_MAXC;
+        for (int i = tid; i < total; i += BEAM_LEX_THREADS) {
+            int sp = 0, off = 0;                     // the source state of slot i and the first slot of its segment
+            for (;; ++sp) {
+                if ((sp & ~s) != 0) continue;
+                const int len = (sp == s ? cols : NW) * prev_n[sp];
+                if (i < off + len) break;
+                off += len;
+            }
+            const int np = prev_n[sp], a = (i - off) / np, q = sp * Wb + (i - off) - a * np;   // a: column, or want index
+            bool ok = t == 1 || prev_seq[t - 2][q] != 0;
+            float local;
+            int v;
+            if (sp == s) {
+                local = ys[q][a];
+                v = ix[q][a];
+                int vb = 0;
+                for (int j = 0; j < NW; ++j) vb |= (wid[j] == v) ? wb[j] : 0;
+                ok = ok && (vb & ~s) == 0;
+            } else {
+                local = wv[q][a];
+                v = wid[a];
+                ok = ok && (wb[a] & ~sp) != 0 && (sp | wb[a]) == s;
+            }
+            ok = ok && !(local == -INFINITY);
+            cand_c[i] = v;
+            cand_q[i] = ok ? q : -1;
+            cand_r[i] = local;
+            cand_p[i] = prev_sum[q] + local;         // fp32 add, as the reference's tensor arithmetic
+            if (ok) {
+                ++mine;
+                first = min(first, i);
+            }
+        }
+        if (mine) {
+            atomicAdd(&nvalid_s, mine);
+            atomicMin(&first_s, first);
+        }
+        __syncthreads();
+        for (int i = tid; i < total; i += BEAM_LEX_THREADS) {
+            if (cand_q[i] < 0) continue;
+            const float pi = cand_p[i];
+            int rank = 0;
+            for (int j = 0; j < total && rank < Wb; ++j) {
+                const float pj = cand_p[j];
+                rank += (cand_q[j] >= 0) && ((pj > pi) || (pj == pi && j < i));
+            }
+            if (rank < Wb) sel_ci[rank] = i;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int nvalid = nvalid_s, nnew = min(Wb, nvalid);
+            for (int vix = 0; vix < Wb; ++vix) {
+                slot_s[vix] = -1;
+                if (vix >= nnew) continue;
+                if (sel_ci[vix] < 0) sel_ci[vix] = first_s;   // only under NaN keys: stay on a valid slot
+                const int ci = sel_ci[vix];
+                if ((cand_c[ci] == 0 || t == S) && n < MAXD) {  // appended in construction order: state, then rank
+                    slot_s[vix] = n;
+                    done_p[(long)k * MAXD + n] = cand_p[ci];
+                    done_state[(long)k * MAXD + n] = s;
+                    ++n;
+                }
+            }
+            state_n[k * G + s] = nnew;
+            any |= nvalid > 0;
+            nnew_s = nnew;
+        }
+        __syncthreads();
+        const int nnew = nnew_s;
+        beam_fork_write(k, tid, BEAM_LEX_THREADS, W, b0, nnew, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp,
+                        prev_seq, prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
+        if (tid >= nnew && tid < Wb) {               // the state's unoccupied rows: inert, nothing stale is kept
+            order[k * W + b0 + tid] = k * W + b0 + tid;
+            nxt[k * W + b0 + tid] = 0;
+        }
+        __syncthreads();                             // the next state reuses the candidate arrays
+    }
+    if (tid == 0) {
+        done_n[k] = n;
+        if (!any) active[k] = 0;
+    }
+}
+
+extern "C" int rfn_beam_step_lex(const float* topv, const int32_t* topi, const float* wantv, const int32_t* want,
+                                 const int32_t* want_bits, int NW, int C, int V1, int W, int S, int t, int NB, int max_done,
+                                 int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* next_ids,
+                                 int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* state_n,
+                                 int32_t* done_state, const int32_t* init_state, int32_t* active, void* stream) {
+    if (C < 0 || C > RFN_LEX_MAX_SETS) return RFN_ERR_SHAPE;
+    if (C == 0)
+        return rfn_beam_step_topk(topv, topi, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids, done_seq,
+                                  done_lp, done_p, done_n, active, stream);
+    if (W < 1 || W > BEAM_MAX_W || W % (1 << C) || NW < 0 || NW > RFN_LEX_MAX_IDS || NW > W - W / (1 << C)) return RFN_ERR_SHAPE;
+    if (S < 1 || S > BEAM_MAX_S || t < 1 || t > S || NB < 1 || V1 < 1 || max_done < 1) return RFN_ERR_SHAPE;
+    if (!topv || !topi || !beam_seq || !beam_lp || !beam_sum || !order || !next_ids || !done_seq || !done_lp || !done_p ||
+        !done_n || !state_n || !done_state || !init_state || !active || (NW > 0 && (!wantv || !want || !want_bits)))
+        return RFN_ERR_ARG;
+    hipLaunchKernelGGL(beam_step_lex_k, dim3(NB), dim3(BEAM_LEX_THREADS), 0, (hipStream_t)stream, topv, topi, wantv, want, want_bits,
+                       NW, C, V1, W, S, t, NB, max_done, beam_seq, beam_lp, beam_sum, order, next_ids, done_seq, done_lp, done_p,
+                       done_n, state_n, done_state, init_state, active);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

@@ -1,6 +1,7 @@
 // Log-softmax over the vocabulary: forward, backward, and the top-W form (plain and masked) that hands the beam search a
 // row's W best log-probs without materialising the row.  One block of 256 per row (rfn_rows.h); rows that qualify are read
 // once, 16 B per lane, and held in registers.
+#include <type_traits>
 #include "rfn_rows.h"
 
 // ---- log-softmax over the vocabulary --------------------------------------------------------------
@@ -50,11 +51,23 @@ extern "C" int rfn_log_softmax_fwd(const float* logits, int64_t ldl, int rows, i
 // MASK (rfn_log_softmax_topk_masked): the row's block list (blk[r, :blk_n[r]], duplicates allowed) becomes a bit per token in
 // LDS; the log-sum-exp above it is still taken over ALL logits, and a blocked token then enters the selection as -inf, so the
 // list is the one a stable descending sort of the masked log-prob row gives (short rows are filled with the lowest -inf ids).
-template <bool VEC, int LW, bool MASK>
+// WANT (rfn_log_softmax_topk_want, rfn.h "lexically constrained beam search"): one more output, the log-probs of the NW tokens
+// want[r / row_div, :] as the selection sees them (-inf when blocked or when the id is the -1 padding).  A register-resident row
+// cannot be indexed by a run-time token without spilling, so both forms read the NW logits again: they lie in cache lines this
+// block has just read, and x[v] - lse is the operation every other entry gets.
+struct LsmWant {
+    const int* want;
+    long ld_want;
+    int NW, row_div;
+    float* wantv;
+};
+struct LsmNoWant {};
+template <bool VEC, int LW, bool MASK, bool WANT = false>
 __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restrict__ logits, long ldl, int V1, int W,
                                                           float* __restrict__ topv, int* __restrict__ topi,
                                                           const int* __restrict__ blk, long ld_blk,
-                                                          const int* __restrict__ blk_n) {
+                                                          const int* __restrict__ blk_n,
+                                                          std::conditional_t<WANT, LsmWant, LsmNoWant> wt = {}) {
     __shared__ float red[4];
     __shared__ float wv[4][LSM_TOPW];
     __shared__ int wi[4][LSM_TOPW];
@@ -84,6 +97,18 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
                         if ((b4 >> e) & 1u) xr[j][e] = -INFINITY;
                 }
             }
+        }
+    }
+    if constexpr (WANT) {
+        if ((int)threadIdx.x < wt.NW) {
+            const int id = wt.want[(long)(r / wt.row_div) * wt.ld_want + threadIdx.x];
+            float lp = -INFINITY;
+            if (id >= 0 && id < V1) {
+                bool blocked = false;
+                if constexpr (MASK) blocked = (lsm_bits[id >> 5] >> (id & 31)) & 1u;
+                if (!blocked) lp = x[id] - lse;
+            }
+            wt.wantv[(long)r * wt.NW + threadIdx.x] = lp;
         }
     }
     // the logit of token v as the selection sees it (the non-VEC form re-reads the row)
@@ -188,7 +213,9 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
     }
 }
 static int log_softmax_topk_launch(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk, int64_t ld_blk,
-                                   const int32_t* blk_n, float* topv, int32_t* topi, void* stream) {
+                                   const int32_t* blk_n, float* topv, int32_t* topi, void* stream,
+                                   const int32_t* want = nullptr, int64_t ld_want = 0, int NW = 0, int row_div = 1,
+                                   float* wantv = nullptr) {
     if (rows <= 0 || V1 <= 0 || W < 1 || W > LSM_TOPW) return RFN_ERR_SHAPE;
     if (!logits || !topv || !topi) return RFN_ERR_ARG;
     if (blk && (!blk_n || ld_blk < 1)) return RFN_ERR_ARG;
@@ -197,8 +224,14 @@ static int log_softmax_topk_launch(const float* logits, int64_t ldl, int rows, i
     hipStream_t st = (hipStream_t)stream;
     const bool vec = lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0);
 #define LSM_LAUNCH3(VECV, LWV, MASKV)                                                                                       \
-    hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, W, topv, \
-                       topi, blk, (long)ld_blk, blk_n)
+    do {                                                                                                                    \
+        if (want)                                                                                                           \
+            hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV, true>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, \
+                               V1, W, topv, topi, blk, (long)ld_blk, blk_n, LsmWant{want, (long)ld_want, NW, row_div, wantv});  \
+        else                                                                                                                \
+            hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, \
+                               W, topv, topi, blk, (long)ld_blk, blk_n, LsmNoWant{});                                       \
+    } while (0)
 #define LSM_LAUNCH(VECV, LWV)                                                                                               \
     do {                                                                                                                    \
         if (blk) LSM_LAUNCH3(VECV, LWV, true);                                                                              \
@@ -220,6 +253,16 @@ extern "C" int rfn_log_softmax_topk(const float* logits, int64_t ldl, int rows, 
 extern "C" int rfn_log_softmax_topk_masked(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk,
                                            int64_t ld_blk, const int32_t* blk_n, float* topv, int32_t* topi, void* stream) {
     return log_softmax_topk_launch(logits, ldl, rows, V1, W, blk, ld_blk, blk_n, topv, topi, stream);
+}
+
+extern "C" int rfn_log_softmax_topk_want(const float* logits, int64_t ldl, int rows, int V1, int W, int row_div, const int32_t* want,
+                                         int64_t ld_want, int NW, const int32_t* blk, int64_t ld_blk, const int32_t* blk_n,
+                                         float* topv, int32_t* topi, float* wantv, void* stream) {
+    if (!want) return log_softmax_topk_launch(logits, ldl, rows, V1, W, blk, ld_blk, blk_n, topv, topi, stream);
+    if (NW < 1 || NW > RFN_LEX_MAX_IDS || ld_want < NW || row_div < 1) return RFN_ERR_SHAPE;
+    if (!wantv) return RFN_ERR_ARG;
+    return log_softmax_topk_launch(logits, ldl, rows, V1, W, blk, ld_blk, blk_n, topv, topi, stream, want, ld_want, NW, row_div,
+                                   wantv);
 }
 
 // d logits = g - softmax * sum(g), one block per row.  VEC: rows of up to 10240 logits (16-B aligned, V1 % 4 == 0) keep g in

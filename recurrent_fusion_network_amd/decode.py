@@ -128,9 +128,10 @@ def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
 class BeamBuffers:
     """The state of a beam search over B images x W beams x S steps.  The rows' top-W lists are uninitialised storage, as
     one float buffer (`top_flat`, rfn_beam_loop) or as values and indices (`top_lists`, a host-stepped search).  `done_group`
-    (the group of every done beam) exists only for a diverse search (groups > 1)."""
+    (the group of every done beam) exists only for a diverse search (groups > 1), `state_n` / `done_state` (the occupied rows of
+    every state, the state of every done beam) only for a lexically constrained one (states = 2^C > 1; W then counts all rows)."""
 
-    def __init__(self, B, W, S, dev, groups=1):
+    def __init__(self, B, W, S, dev, groups=1, states=1):
         self.B, self.W, self.S, self.dev = B, W, S, dev
         self.rows, self.max_done = rows, max_done = B * W, W * S
         self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
@@ -144,6 +145,8 @@ class BeamBuffers:
         self.done_n = torch.zeros(B, dtype=torch.int32, device=dev)
         self.active = torch.ones(B, dtype=torch.int32, device=dev)
         self.done_group = torch.zeros(B, max_done, dtype=torch.int32, device=dev) if groups > 1 else None
+        self.state_n = torch.zeros(B, states, dtype=torch.int32, device=dev) if states > 1 else None
+        self.done_state = torch.zeros(B, max_done, dtype=torch.int32, device=dev) if states > 1 else None
 
     def top_flat(self):
         return torch.empty(2 * self.rows * self.W, device=self.dev)
@@ -152,20 +155,22 @@ class BeamBuffers:
         return torch.empty(self.rows, self.W, device=self.dev), torch.empty(self.rows, self.W, dtype=torch.int32, device=self.dev)
 
 
-def run_beam_loop(stepper, bufs, cons, div=None):
+def run_beam_loop(stepper, bufs, cons, div=None, lex=None):
     """The whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows).  cons: a parsed
-    _Constraints or None; div: a parsed _Diversity or None (bufs then holds done_group)."""
+    _Constraints or None; div: a parsed _Diversity or None (bufs then holds done_group); lex: a parsed _Lexical or None (bufs then
+    holds state_n / done_state)."""
     b, logp = bufs, bufs.top_flat()
     h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
-    N.check(N.lib.rfn_beam_loop_ex2(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
+    N.check(N.lib.rfn_beam_loop_ex3(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
                                     stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
                                     c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(),
                                     b.order.data_ptr(), b.ids.data_ptr(), b.done_seq.data_ptr(), b.done_lp.data_ptr(),
                                     b.done_p.data_ptr(), b.done_n.data_ptr(), b.active.data_ptr(), b.max_done,
                                     stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
                                     C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None,
-                                    C.byref(div.struct(b)) if div is not None else None, N.stream_ptr()),
-            'rfn_beam_loop_ex2')
+                                    C.byref(div.struct(b)) if div is not None else None,
+                                    C.byref(lex.struct(b)) if lex is not None else None, N.stream_ptr()),
+            'rfn_beam_loop_ex3')
 
 
 class _Constraints:
@@ -292,6 +297,87 @@ class _Diversity:
                                         b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
                                         b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(), b.done_n.data_ptr(),
                                         b.done_group.data_ptr(), b.active.data_ptr(), N.stream_ptr()), 'rfn_beam_step_div')
+
+
+class _Lexical:
+    """Lexically constrained beam search of one call (rfn.h "lexically constrained beam search"): opt['require'] names, per image,
+    up to 3 sets of token ids, and the returned caption should hold one id of every set -- a (B, C, K) integer tensor padded with
+    -1, or B lists of lists of ids.  opt['beam_size'] = Wb is then the beam of every one of the 2^C states, and the search runs
+    W = Wb * 2^C <= 32 rows per image.  `parse` returns None when no image has a non-empty set, so such a call issues exactly the
+    launches it always did.  Per image the unique ids (at most 16, and at most W - Wb: the bound under which the rows' W-wide top
+    lists suffice) become `want` with a set mask each in `want_bits`; `init_state` holds the bits of the image's empty sets."""
+
+    @staticmethod
+    def _sets(req, B):
+        if torch.is_tensor(req):
+            if req.dim() != 3 or req.is_floating_point():
+                raise ValueError('require must be a (B, C, K) integer tensor, got %s %s' % (tuple(req.shape), req.dtype))
+            req = [[[v for v in ids if v != -1] for ids in img] for img in req.tolist()]
+        else:
+            req = [[[int(v) for v in (ids.tolist() if torch.is_tensor(ids) else ids)] for ids in img] for img in req]
+        if len(req) != B:
+            raise ValueError('require names the sets of %d images, the batch holds %d' % (len(req), B))
+        return req
+
+    @classmethod
+    def parse(cls, opt, B, V1, Wb):
+        req = opt.get('require', None)
+        if req is None:
+            return None
+        req = cls._sets(req, B)
+        if not any(len(ids) for img in req for ids in img):
+            return None
+        nsets = max(len(img) for img in req)
+        if nsets > N.LEX_MAX_SETS:
+            raise ValueError('require holds %d sets for an image, at most %d are supported' % (nsets, N.LEX_MAX_SETS))
+        W = Wb << nsets
+        if W > 32:
+            raise ValueError('beam_size %d with %d required sets needs %d rows per image, at most 32 are supported' % (Wb, nsets, W))
+        want, bits, init = [], [], []
+        for img in req:
+            w, m, i0 = [], [], 0
+            for i in range(nsets):
+                ids = img[i] if i < len(img) else []
+                if not ids:
+                    i0 |= 1 << i
+                for v in ids:
+                    if not 1 <= v < V1:
+                        raise ValueError('require must hold token ids in [1, %d), got %d' % (V1, v))
+                    if v not in w:
+                        w.append(v)
+                        m.append(0)
+                    m[w.index(v)] |= 1 << i
+            want.append(w)
+            bits.append(m)
+            init.append(i0)
+        nw = max(len(w) for w in want)
+        if nw > N.LEX_MAX_IDS:
+            raise ValueError('require holds %d ids for an image, at most %d are supported' % (nw, N.LEX_MAX_IDS))
+        if nw > W - Wb:
+            raise ValueError('require holds %d ids for an image: with beam_size %d and %d sets at most %d are supported'
+                             % (nw, Wb, nsets, W - Wb))
+        lx = cls()
+        lx.C, lx.G, lx.Wb, lx.W, lx.NW = nsets, 1 << nsets, Wb, W, nw
+        lx.want = [w + [-1] * (nw - len(w)) for w in want]
+        lx.want_bits = [m + [0] * (nw - len(m)) for m in bits]
+        lx.init_state = init
+        return lx
+
+    def bind(self, dev):
+        up = lambda x: torch.tensor(x, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)  # noqa: E731
+        self.want_d, self.bits_d, self.init_d = up(self.want), up(self.want_bits), up(self.init_state)
+        return self
+
+    def struct(self, bufs):
+        self.wantv = torch.empty(bufs.rows, self.NW, device=bufs.dev)
+        self._struct = N.BeamLexical(self.C, self.NW, self.want_d.data_ptr(), self.bits_d.data_ptr(), self.init_d.data_ptr(),
+                                     self.wantv.data_ptr(), bufs.state_n.data_ptr(), bufs.done_state.data_ptr())
+        return self._struct
+
+    def met(self, state):
+        """state (B,) int32, the state of every image's returned caption -> how many of the image's non-empty sets it satisfies."""
+        table = torch.tensor([bin(x).count('1') for x in range(self.G)], dtype=torch.int32, device=state.device)
+        return table[(state & ~self.init_d).long()]
 
 
 class _Consensus:
@@ -529,7 +615,7 @@ def _length_penalty(opt):
 
 
 def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None, consensus=None,
-                       groups=1, keep=None):
+                       groups=1, keep=None, done_state=None, lex=None):
     """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
     once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
@@ -548,7 +634,10 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     (_consensus_beams) instead of the first of them; the lists keep their meaning and order, and nothing more is read back.
 
     keep (a dict, with keep['n'] = keep_candidates_n): it receives 'seq' (B, m, S) int64 and 'n_cand' (B,) int32, the candidate
-    set the consensus pick chooses from (_beam_candidates), on the device; with or without `consensus`."""
+    set the consensus pick chooses from (_beam_candidates), on the device; with or without `consensus`.
+
+    done_state (a lexically constrained search): the done beams are ordered by the number of satisfied sets descending first, then
+    as above; every done_beams dict gets its 'state', and lex (a dict) receives 'state' (B,) int32, the returned caption's."""
     dev, B = done_p.device, done_p.size(0)
     score = done_p
     if length_penalty:
@@ -560,10 +649,18 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     key = torch.where(torch.arange(max_done, device=dev)[None, :] < done_n[:, None], -score,
                       torch.full_like(score, float('inf')))
     rank = torch.sort(key, dim=1, stable=True).indices
+    if done_state is not None:      # a second stable sort: satisfied sets descending, the order above within equal counts
+        valid = torch.arange(max_done, device=dev)[None, :] < done_n[:, None]
+        nsat = torch.tensor([bin(x).count('1') for x in range(8)], device=dev)[done_state.long().clamp(0, 7)]
+        unmet = torch.where(valid, -nsat, torch.ones_like(nsat)).gather(1, rank)
+        rank = rank.gather(1, torch.sort(unmet, dim=1, stable=True).indices)
     pick = rank[:, :, None].expand(-1, -1, S)
     s_all, l_all, p_all = done_seq.gather(1, pick), done_lp.gather(1, pick), done_p.gather(1, rank)
     g_all = done_group.gather(1, rank) if done_group is not None else None
-    src = _BeamResults(s_all, l_all, p_all, done_n, g_all)
+    st_all = done_state.gather(1, rank) if done_state is not None else None
+    if lex is not None:
+        lex['state'] = st_all[:, 0].contiguous()
+    src = _BeamResults(s_all, l_all, p_all, done_n, g_all, st_all)
     if consensus is not None or keep is not None:
         cands, lps, p, n_cand, m = _beam_candidates(consensus.n if consensus is not None else keep['n'], s_all, l_all, p_all, done_n,
                                                     g_all, groups)
@@ -581,9 +678,9 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
 class _BeamResults:
     """Host copies of the sorted done beams, fetched once, on demand."""
 
-    def __init__(self, s_all, l_all, p_all, done_n, g_all=None):
+    def __init__(self, s_all, l_all, p_all, done_n, g_all=None, st_all=None):
         self._dev = (s_all, l_all, p_all, done_n)
-        self._g_dev = g_all
+        self._g_dev, self._st_dev = g_all, st_all
         self._host = None
 
     def host(self):
@@ -591,6 +688,7 @@ class _BeamResults:
             s_all, l_all, p_all, done_n = self._dev
             self._host = (s_all.cpu(), l_all.cpu(), p_all.cpu().tolist(), done_n.cpu().tolist())
             self._g_host = self._g_dev.cpu().tolist() if self._g_dev is not None else None
+            self._st_host = self._st_dev.cpu().tolist() if self._st_dev is not None else None
         return self._host
 
     def top_seq(self):
@@ -610,6 +708,10 @@ class _BeamResults:
             for k, img in enumerate(beams):
                 for d, g in zip(img, self._g_host[k]):
                     d['group'] = g
+        if self._st_host is not None:                # a lexically constrained search: the sets each beam satisfies
+            for k, img in enumerate(beams):
+                for d, st in zip(img, self._st_host[k]):
+                    d['state'] = st
         return beams
 
 

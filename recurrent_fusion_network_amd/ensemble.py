@@ -135,6 +135,9 @@ class EnsembleDecoder:
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
         if W > 32 or S > 64 or W > V1:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
+        if opt.get('require', None) is not None:
+            raise ValueError('require (lexically constrained beam search) is RecurrentFusionModel.sample_beam\'s: the ensemble\'s '
+                             'host-stepped search does not implement it')
         cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
         cs = _Consensus.parse(opt, V1, S, W)
         keep_n = keep_candidates_n(opt, W)

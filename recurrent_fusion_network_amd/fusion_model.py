@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty,
+from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Lexical,
                      _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit, keep_candidates_n, run_beam_loop,
                      run_greedy_loop)
 
@@ -452,6 +452,7 @@ class RecurrentFusionModel(nn.Module):
         self.diverse_beams = None       # sample_beam with group_size > 1: per image the G group bests
         self.consensus = None           # sample / sample_beam with opt['consensus']: {'index', 'scores'} of the pick (device)
         self.candidates = None          # sample_beam with opt['keep_candidates']: {'seq' (B, m, S), 'n_cand' (B,)} (device)
+        self.lexical_met = None         # sample_beam with opt['require']: (B,) int32, the non-empty sets the caption satisfies (device)
 
     def init_weights(self):
         """misc/RecurrentFusionModel.py:188-196."""
@@ -972,16 +973,29 @@ class RecurrentFusionModel(nn.Module):
 
         opt['keep_candidates'] = True leaves `self.candidates` = {'seq': (B, m, S) int64, 'n_cand': (B,) int32} on the device: the
         candidate set the consensus pick chooses from (with or without 'consensus'), for evalcap.DiversityEval.  Without the key
-        `self.candidates` is None and the call issues the launches it always did."""
+        `self.candidates` is None and the call issues the launches it always did.
+
+        opt['require'] = per image up to 3 sets of token ids, a (B, C, K) tensor padded with -1 or nested lists (rfn.h "lexically
+        constrained beam search"): the caption should hold one id of every set.  beam_size is then the beam of each of the 2^C
+        states and the search runs beam_size * 2^C <= 32 rows per image.  The done beams are ranked by the number of satisfied sets
+        first; every `done_beams` dict carries its 'state' (the bit mask of satisfied sets), and `self.lexical_met` is a (B,) int32
+        device tensor: how many of the image's non-empty sets the returned caption satisfies.  Composes with block_ngram,
+        banned_ids, bad_endings, length_penalty and keep_candidates; not with group_size > 1 or consensus.  With every set empty
+        the call issues the launches it always did."""
         beam_size = opt.get('beam_size', 10)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
         assert beam_size <= V1, 'lets assume this for now'
         if beam_size > 32 or S > 64:
             raise N.RfnError('beam search supports beam_size <= 32 and seq_length <= 64')
-        W = beam_size
-        cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, W)
-        cs = _Consensus.parse(opt, V1, S, W)
-        keep_n = keep_candidates_n(opt, W)
+        lex = _Lexical.parse(opt, B, V1, beam_size)
+        W = lex.W if lex is not None else beam_size
+        cons, alpha, div = _Constraints.parse(opt, V1, S), _length_penalty(opt), _Diversity.parse(opt, beam_size)
+        cs = _Consensus.parse(opt, V1, S, beam_size)
+        if lex is not None and (div is not None or cs is not None):
+            raise ValueError('require cannot be combined with group_size > 1 or consensus')
+        if lex is not None and int(self.path_flags) & N.PATH_OPT_DEC_UNHOISTED:
+            raise ValueError('require needs the hoisted decoder cell (path_flags select another form)')
+        keep_n = keep_candidates_n(opt, beam_size)
         keep = None if keep_n is None else {'n': keep_n}
         if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
@@ -993,16 +1007,19 @@ class RecurrentFusionModel(nn.Module):
             # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
             stepper = _Stepper(self, comb_b, h_b.repeat_interleave(W, dim=0).contiguous(),
                                c_b.repeat_interleave(W, dim=0).contiguous(), drop, seed)
-            bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
-            run_beam_loop(stepper, bufs, cons, div)
+            bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1, lex.G if lex is not None else 1)
+            run_beam_loop(stepper, bufs, cons, div, lex.bind(dev) if lex is not None else None)
+            lex_out = {} if lex is not None else None
             seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
                                                                             S, bufs.max_done, alpha, bufs.done_group, cs,
-                                                                            div.groups if div is not None else 1, keep)
+                                                                            div.groups if div is not None else 1, keep,
+                                                                            bufs.done_state, lex_out)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
         self.consensus = cs.result if cs is not None else None
         self.candidates = None if keep is None else {'seq': keep['seq'], 'n_cand': keep['n_cand']}
         self.diverse_beams = _diverse_beams(done_beams, div.groups) if div is not None else None
+        self.lexical_met = lex.met(lex_out['state']) if lex is not None else None
         reason_batch = _LazyList(B, lambda: [list(t.unbind(0)) for t in heads.unbind(1)])
         return seq, seq_lp, top_seq, top_prob, reason_batch
 

@@ -258,7 +258,72 @@ def consensus_ab(out_path, rounds=7):
         json.dump(res, f, indent=1)
         f.write('\n')
 
+def _kernel_us(fn):
+    """Device time of one call of `fn` per kernel name (us, summed over its launches; the profiler's device-activity records)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    out = {}
+    for ev in prof.events():
+        if getattr(ev, 'device_type', None) is not None and 'cuda' in str(ev.device_type).lower():
+            name = ev.name.split('(')[0].split('<')[0]
+            if 'memcpy' in name.lower() or 'memset' in name.lower():
+                continue
+            t = out.setdefault(name, [0, 0.0])
+            t[0] += 1
+            t[1] += float(getattr(ev, 'device_time', 0.0) or getattr(ev, 'cuda_time', 0.0) or 0.0)
+    return out
+
+def lexical_ab(out_path, rounds=7):
+    """--lexical [--out FILE]: config 5, one sample_beam call with beam_size = 3 and two single-id required sets per image (four
+    states of three beams: 12 rows per image) against the plain beam_size = 12 call of this same tree, which issues the parent's
+    launches by construction and so stands in for the parent.  Windows of 5 calls after a warm-up call, the two settings
+    alternating, medians of `rounds`; kernel launches per call and the device time per kernel name by the profiler, each in a
+    call of its own."""
+    import statistics
+    S, V1 = cfg.seq_length, cfg.vocab_size + 1
+    model.eval()
+    g = torch.Generator().manual_seed(5)
+    req = torch.randint(1, V1, (B, 2, 1), generator=g)
+    req[:, 1, 0] = torch.where(req[:, 1, 0] == req[:, 0, 0], req[:, 1, 0] % (V1 - 1) + 1, req[:, 1, 0])   # two distinct ids per image
+    settings = [('plain_beam_12', {'beam_size': 12}), ('lexical_beam_3_two_sets', {'beam_size': 3, 'require': req})]
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=%d, seq=%d, B=%d, 12 rows per image' % (V1, S, B), 'rounds': rounds,
+           'calls_per_window': 5, 'what': 'ms per sample_beam call, the two settings alternating'}
+
+    def call(o):
+        with torch.no_grad():
+            return model.sample_beam(fc, att, o)
+
+    ms = {k: [] for k, _ in settings}
+    for k, o in settings:
+        call(o)
+    for _ in range(rounds):
+        for k, o in settings:
+            ms[k].append(timed(lambda: call(o), 5)[0] * 1e3)
+    kernels = {}
+    for k, o in settings:
+        res[k] = {'ms': round(statistics.median(ms[k]), 3), 'min': round(min(ms[k]), 3), 'max': round(max(ms[k]), 3),
+                  'launches_per_call': HB.count_launches(lambda: call(o))}
+        kernels[k] = _kernel_us(lambda: call(o))
+        print(json.dumps({k: res[k]}), flush=True)
+    a, b = kernels['plain_beam_12'], kernels['lexical_beam_3_two_sets']
+    diff = sorted(((b.get(n, [0, 0.0])[1] - a.get(n, [0, 0.0])[1], n) for n in set(a) | set(b)), key=lambda x: -abs(x[0]))
+    res['kernel_us_lexical_minus_plain'] = [{'kernel': n, 'us': round(d, 1), 'plain': [a.get(n, [0, 0.0])[0], round(a.get(n, [0, 0.0])[1], 1)],
+                                             'lexical': [b.get(n, [0, 0.0])[0], round(b.get(n, [0, 0.0])[1], 1)]} for d, n in diff[:8]]
+    res['lexical_minus_plain_ms'] = round(res['lexical_beam_3_two_sets']['ms'] - res['plain_beam_12']['ms'], 3)
+    call(settings[1][1])
+    res['mean_sets_met_of_2'] = round(float(model.lexical_met.float().mean()), 3)
+    print(json.dumps(res), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
 PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
+if '--lexical' in sys.argv:
+    lexical_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'decode_lexical.json'))
+    sys.exit(0)
 if '--consensus' in sys.argv:
     consensus_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'decode_consensus.json'))
     sys.exit(0)
