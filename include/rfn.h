@@ -701,6 +701,34 @@ int rfn_xe_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, co
 int rfn_xe_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
                       const float* mask, int64_t ld_mask, float eps, const float* lse, float gscale,
                       const float* gscale_dev, void* stream);
+/* Distillation: the same language term plus a KL term towards a teacher's distribution, straight from the logits (the loss of
+ * RecurrentFusionModel.forward_loss(..., teacher=)).  Rows are (b, t): x = the student's logits row (time-major, as above),
+ * z = the teacher's row at teacher + b * z_sb + t * z_st, logits or log-probs (every term is invariant to a per-row shift of
+ * z; the two strides serve a batch-major (B, T, V1) tensor and a time-major (T, B, V1) buffer alike), q = the one-hot or
+ * label-smoothed target of rfn_xe_logits_*, m = mask[b, t], it = inv_temp = 1 / temperature, alpha in [0, 1]:
+ *   p_t(v)  = softmax(z * it)(v)            p_s(v) = softmax(x * it)(v)
+ *   KL(b,t) = sum_{v : p_t(v) > 0} p_t(v) * (log p_t(v) - log p_s(v))
+ *   xe      = sum_{b,t} m * ( -q . log_softmax(x) ) / B           (exactly rfn_xe_logits_fwd's loss, bit for bit)
+ *   kd      = sum_{b,t} m * KL(b,t) / (it*it) / B                 (the usual tau^2 scaling)
+ *   loss    = (1 - alpha) * xe + alpha * kd
+ *   d loss / d x[v] = m * g / B * ( (1 - alpha) * (softmax(x)[v] - q[v]) + alpha / it * (p_s(v) - p_t(v)) )
+ * A -inf teacher entry contributes 0 (constraint-masked log-probs are a legal teacher; no NaN from 0 * inf); a teacher row
+ * with no finite entry is the caller's error and is not checked; a row with m == 0 has loss terms of exactly 0 and _bwd writes
+ * zeros over its logits, whatever its teacher row holds (NaN included).  Targets are clamped as in rfn_xe_logits_*.
+ * _fwd: row_stats (3*T*B floats) = lse(x), lse(x*it), lse(z*it), each as T*B time-major rows; scratch: 2*B*T floats;
+ * loss_out[0] (+)= loss; terms_out (may be NULL) = {xe, kd}.  _bwd overwrites the logits with d loss / d logits * gscale *
+ * gscale_dev[0] (gscale_dev may be NULL) from the same target / mask / eps / teacher / alpha / inv_temp and _fwd's row_stats.
+ * Both rows are read 16 B per lane when the student passes rfn_xe_logits_*'s conditions (V1 % 4 == 0, V1 <= 10240, ldl % 4 == 0,
+ * 16-B aligned) and the teacher is 16-B aligned with z_sb % 4 == 0 and z_st % 4 == 0; otherwise element-wise.
+ * RFN_ERR_SHAPE: the checks of rfn_xe_logits_*, alpha outside [0, 1], inv_temp not finite or <= 0, |z_sb| or |z_st| < V1. */
+int rfn_kd_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                      const float* mask, int64_t ld_mask, float eps, const float* teacher, int64_t z_sb, int64_t z_st,
+                      float alpha, float inv_temp, float* row_stats, float* scratch, float* loss_out, int accumulate_loss,
+                      float* terms_out, void* stream);
+int rfn_kd_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                      const float* mask, int64_t ld_mask, float eps, const float* teacher, int64_t z_sb, int64_t z_st,
+                      float alpha, float inv_temp, const float* row_stats, float gscale, const float* gscale_dev,
+                      void* stream);
 /* ReviewNetRewardCriterion policy + entropy terms (misc/utils.py:50-72):
  * loss_out[0] (+)= [ -sum pol(b,t)*mask(b,t) + entropy_reg * sum mask0(b,t) * sum_v lp*exp(lp) ] / B with
  * mask0 = seq > 0, mask = [1, mask0[:, :-1]], pol = input*reward or the reference's PPO-clip surrogate.

@@ -175,6 +175,8 @@ def _load():
         'rfn_bcast_to_groups': (C.c_int, [I, F, P, L, P, P, L, L, I, I, I, P]),
         'rfn_xe_logits_fwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, P, P, I, P]),
         'rfn_xe_logits_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, F, P, P]),
+        'rfn_kd_logits_fwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, F, F, P, P, P, I, P, P]),
+        'rfn_kd_logits_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, F, F, P, F, P, P]),
         'rfn_decoder_logits': (P, [DP, I, I, I, P]),
         'rfn_xe_loss': (C.c_int, [P, I, I, I, P, L, P, L, F, F, P, P, I, P, P]),
         'rfn_multilabel_margin': (C.c_int, [P, I, I, P, F, F, P, P, I, P, P]),

@@ -1,5 +1,5 @@
-// The three criteria and their gradients: the XE language loss (from log-probs, and fused from the logits), the RL reward
-// criterion, and nn.MultiLabelMarginLoss for the reason heads.  One block of 256 per row writes the row's loss term; sum_k /
+// The criteria and their gradients: the XE language loss (from log-probs, and fused from the logits), the same with a KL term
+// towards a teacher's rows (distillation), the RL reward criterion, and nn.MultiLabelMarginLoss for the reason heads.  One block of 256 per row writes the row's loss term; sum_k /
 // sum_groups_k add the terms in a fixed order (no float atomics), so a loss is bitwise reproducible.
 #include <string.h>
 
@@ -165,6 +165,218 @@ extern "C" int rfn_xe_logits_bwd(float* logits, int64_t ldl, int B, int T, int V
     else
         hipLaunchKernelGGL(xe_logits_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
                            (long)ld_target, mask, (long)ld_mask, eps, gscale / (float)B, gscale_dev, lse);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- distillation: the language term and a KL term towards a teacher row, straight from the logits (rfn.h) -----------------
+// Rows as above (x = the student's time-major logits row r = t * B + b); z = the teacher's row (b, t), logits or log-probs
+// (every term is invariant to a per-row shift of z), at teacher + b * z_sb + t * z_st.  it = 1 / temperature.
+//   forward : lse(x) (log_softmax_row: xe_logits_fwd_k's bits), lse(x * it), lse(z * it) -> row_stats[0 / 1 / 2][r];
+//             the xe row term, xe_logits_fwd_k's expression -> row_xe[b * T + t];
+//             mask / it^2 * sum_{v : p_t(v) > 0} p_t(v) * (log p_t(v) - log p_s(v)) -> row_kd[b * T + t]
+//   backward: d logits[v] = mask * g / B * ((1 - alpha) * (softmax(x)[v] - q[v]) + alpha / it * (p_s(v) - p_t(v))), written
+//             over the logits.
+// A -inf teacher entry has p_t = 0 and is skipped (no 0 * inf); a row with mask == 0 has exact zeros for its kd term and its
+// gradient whatever its teacher row holds.  Vector form: both rows read once, 16 B per lane, into 2 x LSM_R4 f32x4.
+// kd_each: f(x[v], z[v]) over this thread's share of the two rows, from the registers (vector form) or from memory.
+template <bool VEC, class F>
+__device__ __forceinline__ void kd_each(const float* __restrict__ x, const float* __restrict__ z, int V1,
+                                        const f32x4 (&xr)[LSM_R4], const f32x4 (&zr)[LSM_R4], F f) {
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+#pragma unroll
+        for (int j = 0; j < LSM_R4; ++j)
+            if (threadIdx.x + 256 * j < n4) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f(xr[j][e], zr[j][e]);
+            }
+    } else {
+        for (int v = threadIdx.x; v < V1; v += 256) f(x[v], z[v]);
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void kd_logits_fwd_k(const float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ target, long ld_t,
+                                                       const float* __restrict__ mask, long ld_m, float eps,
+                                                       const float* __restrict__ teacher, long z_sb, long z_st, float it,
+                                                       float* __restrict__ row_stats, float* __restrict__ row_xe,
+                                                       float* __restrict__ row_kd) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, t = r / B, b = r - t * B;      // time-major rows
+    const float* x = logits + r * ldl;
+    const float* z = teacher + b * z_sb + t * z_st;
+    f32x4 xr[LSM_R4], zr[LSM_R4];
+    const float lse = log_softmax_row<VEC>(x, V1, xr, red);
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    float term = x[tg] - lse;                                // the xe term: xe_logits_fwd_k's expression, for its bits
+    if (eps > 0.f) {
+        float s = 0.f;
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) s += ((xr[j][0] - lse) + (xr[j][1] - lse)) + ((xr[j][2] - lse) + (xr[j][3] - lse));
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) s += x[v] - lse;
+        }
+        s = block_sum_256(s, red);
+        term = (1.0f - eps) * term + (eps / (float)V1) * s;
+    }
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+#pragma unroll
+        for (int j = 0; j < LSM_R4; ++j) {
+            const int i = threadIdx.x + 256 * j;
+            zr[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            if (i < n4) zr[j] = *reinterpret_cast<const f32x4*>(z + 4 * i);
+        }
+    }
+    // the tempered rows: it > 0, so max(x * it) is the rounded max(x) * it
+    float mx = -INFINITY, mz = -INFINITY;
+    kd_each<VEC>(x, z, V1, xr, zr, [&](float xv, float zv) {
+        mx = fmaxf(mx, xv);
+        mz = fmaxf(mz, zv);
+    });
+    mz = block_max_256(mz, red) * it;
+    float lse_s = lse;
+    if (it != 1.0f) mx = block_max_256(mx, red) * it;        // `it` is uniform over the grid
+    float ss = 0.f, sz = 0.f;
+    kd_each<VEC>(x, z, V1, xr, zr, [&](float xv, float zv) {
+        if (it != 1.0f) ss += expf(xv * it - mx);
+        sz += expf(zv * it - mz);                            // exp(-inf) = 0
+    });
+    if (it != 1.0f) lse_s = mx + logf(block_sum_256(ss, red));
+    const float lse_t = mz + logf(block_sum_256(sz, red));
+    float kl = 0.f;
+    kd_each<VEC>(x, z, V1, xr, zr, [&](float xv, float zv) {
+        const float lpt = zv * it - lse_t;
+        const float pt = expf(lpt);
+        kl += (pt > 0.f) ? pt * (lpt - (xv * it - lse_s)) : 0.f;
+    });
+    kl = block_sum_256(kl, red);
+    if (threadIdx.x == 0) {
+        const long n = (long)T * B;
+        row_stats[r] = lse;
+        row_stats[n + r] = lse_s;
+        row_stats[2 * n + r] = lse_t;
+        row_xe[b * T + t] = -mk * term;
+        row_kd[b * T + t] = (mk != 0.f) ? mk * kl / (it * it) : 0.f;
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void kd_logits_bwd_k(float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ target, long ld_t,
+                                                       const float* __restrict__ mask, long ld_m, float eps,
+                                                       const float* __restrict__ teacher, long z_sb, long z_st, float alpha,
+                                                       float it, float gcoef, const float* __restrict__ gdev,
+                                                       const float* __restrict__ row_stats) {
+    const int r = blockIdx.x, t = r / B, b = r - t * B;
+    float* x = logits + r * ldl;
+    const float* z = teacher + b * z_sb + t * z_st;
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    if (mk == 0.f) {                                         // exact zeros, whatever the teacher row and its stats hold
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+            for (int i = threadIdx.x; i < n4; i += 256) *reinterpret_cast<f32x4*>(x + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) x[v] = 0.f;
+        }
+        return;
+    }
+    const float c = mk * (gdev ? gcoef * gdev[0] : gcoef);   // mask * d loss / B
+    const long n = (long)T * B;
+    const float lse = row_stats[r], lse_s = row_stats[n + r], lse_t = row_stats[2 * n + r];
+    const float uni = eps / (float)V1, hot = 1.0f - eps, wx = 1.0f - alpha, wk = alpha / it;
+    auto grad = [&](float xv, float zv, bool is_tg) {
+        const float p = expf(xv - lse);
+        const float ps = (it != 1.0f) ? expf(xv * it - lse_s) : p;      // it == 1: the two soft-maxes are one expf
+        const float pt = expf(zv * it - lse_t);                          // exp(-inf) = 0
+        return c * (wx * ((p - uni) - (is_tg ? hot : 0.f)) + wk * (ps - pt));
+    };
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * i), zv = *reinterpret_cast<const f32x4*>(z + 4 * i);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = grad(xv[e], zv[e], 4 * i + e == tg);
+            *reinterpret_cast<f32x4*>(x + 4 * i) = o;
+        }
+    } else {
+        for (int v = threadIdx.x; v < V1; v += 256) x[v] = grad(x[v], z[v], v == tg);
+    }
+}
+// out[0] (+)= (1 - alpha) * xe[0] + alpha * kd[0]
+__global__ void kd_mix_k(const float* __restrict__ xe, const float* __restrict__ kd, float alpha, float* __restrict__ out,
+                         int accumulate) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const float l = (1.0f - alpha) * xe[0] + alpha * kd[0];
+        out[0] = accumulate ? out[0] + l : l;
+    }
+}
+static int kd_check(const void* logits, int64_t ldl, int B, int T, int V1, const void* target, const void* mask, float eps,
+                    const void* teacher, int64_t z_sb, int64_t z_st, float alpha, float inv_temp) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || ldl < V1 || eps < 0.f || eps >= 1.f) return RFN_ERR_SHAPE;
+    if (!(alpha >= 0.f && alpha <= 1.f) || !(inv_temp > 0.f) || !(inv_temp <= 3.402823466e38f)) return RFN_ERR_SHAPE;
+    if ((z_sb < 0 ? -z_sb : z_sb) < V1 || (z_st < 0 ? -z_st : z_st) < V1) return RFN_ERR_SHAPE;
+    if (!logits || !target || !mask || !teacher) return RFN_ERR_ARG;
+    return RFN_OK;
+}
+// the vector form needs lsm_vec_ok for the student and its analogue for the teacher
+static bool kd_vec_ok(const float* logits, int64_t ldl, int V1, const float* teacher, int64_t z_sb, int64_t z_st) {
+    return lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0) && rfn_aligned16(teacher) && z_sb % 4 == 0 && z_st % 4 == 0;
+}
+extern "C" int rfn_kd_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target,
+                                 int64_t ld_target, const float* mask, int64_t ld_mask, float eps, const float* teacher,
+                                 int64_t z_sb, int64_t z_st, float alpha, float inv_temp, float* row_stats, float* scratch,
+                                 float* loss_out, int accumulate_loss, float* terms_out, void* stream) {
+    const int rc = kd_check(logits, ldl, B, T, V1, target, mask, eps, teacher, z_sb, z_st, alpha, inv_temp);
+    if (rc != RFN_OK) return rc;
+    if (!row_stats || !scratch || !loss_out) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    float* row_kd = scratch + (size_t)B * T;
+    if (kd_vec_ok(logits, ldl, V1, teacher, z_sb, z_st))
+        hipLaunchKernelGGL(kd_logits_fwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, teacher, (long)z_sb, (long)z_st, inv_temp, row_stats,
+                           scratch, row_kd);
+    else
+        hipLaunchKernelGGL(kd_logits_fwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, teacher, (long)z_sb, (long)z_st, inv_temp, row_stats,
+                           scratch, row_kd);
+    RFN_CHECK_LAUNCH();
+    // the two sums by sum_k, in its order; without terms_out each lands on its own array's first slot (sum_k reads every
+    // element before its one store)
+    float* xe = terms_out ? terms_out : scratch;
+    float* kd = terms_out ? terms_out + 1 : row_kd;
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, xe, 0);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, row_kd, B * T, 1.0f / (float)B, kd, 0);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kd_mix_k, dim3(1), dim3(64), 0, st, xe, kd, alpha, loss_out, accumulate_loss);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+extern "C" int rfn_kd_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                                 const float* mask, int64_t ld_mask, float eps, const float* teacher, int64_t z_sb,
+                                 int64_t z_st, float alpha, float inv_temp, const float* row_stats, float gscale,
+                                 const float* gscale_dev, void* stream) {
+    const int rc = kd_check(logits, ldl, B, T, V1, target, mask, eps, teacher, z_sb, z_st, alpha, inv_temp);
+    if (rc != RFN_OK) return rc;
+    if (!row_stats) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (kd_vec_ok(logits, ldl, V1, teacher, z_sb, z_st))
+        hipLaunchKernelGGL(kd_logits_bwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, teacher, (long)z_sb, (long)z_st, alpha, inv_temp,
+                           gscale / (float)B, gscale_dev, row_stats);
+    else
+        hipLaunchKernelGGL(kd_logits_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, teacher, (long)z_sb, (long)z_st, alpha, inv_temp,
+                           gscale / (float)B, gscale_dev, row_stats);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

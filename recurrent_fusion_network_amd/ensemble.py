@@ -123,6 +123,32 @@ class EnsembleDecoder:
         return bufs.result()
 
     @torch.no_grad()
+    def teacher_logits(self, fc_feats, att_feats, seq):
+        """The members' mean pre-softmax logits on the ground-truth prefix, as the `teacher` of
+        RecurrentFusionModel.forward_loss: -> (B, S, V+1), S as the model's forward finds it (the first all-zero label column).
+        The members step teacher-forced on seq[:, :S]; step t's mean goes straight into row block t of ONE (S, B, V+1) buffer,
+        whose transposed view is returned (the distillation kernels take the teacher through its two strides, so nothing is
+        copied).  Members on other ranks of the process group contribute as in `score`.  The mean of logits, not of
+        probabilities: the distribution the ensemble decodes with."""
+        m0 = self.models[0]
+        B = m0._check_inputs(fc_feats, att_feats)
+        if seq.dim() != 2 or seq.size(0) != B:
+            raise N.RfnError('seq has shape %s, the features hold %d rows' % (tuple(seq.shape), B))
+        S = m0._decoder_steps(seq)
+        V1 = m0.vocab_size + 1
+        steppers = []
+        for m in self.models:
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
+        dev = steppers[0].h.device
+        feed = seq[:, :S].to(dev).long().t().contiguous()      # row t = the tokens fed at step t
+        out = torch.empty(S, B, V1, device=dev)
+        logit_m = torch.empty(B, V1, device=dev) if len(steppers) > 1 else None
+        for t in range(S):
+            self._averaged_step(steppers, feed[t], out[t], logit_m)
+        return out.transpose(0, 1)
+
+    @torch.no_grad()
     def sample_beam(self, fc_feats, att_feats, opt={}):
         """Beam search on the members' averaged distribution -> (seq (B, S), seqLogprobs (B, S), top_seq, top_prob) with
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,

@@ -278,10 +278,28 @@ class _DecoderLossFn(torch.autograd.Function):
     logits (time-major rows in the workspace), rfn_xe_logits_fwd turns them into the masked (label-smoothed) NLL and the rows'
     logsumexps; backward writes d logits over the logits (rfn_xe_logits_bwd, scaled by the upstream gradient read on the
     device) and rfn_decoder_bwd runs from there.  Neither log_prob (B, S, V+1) nor its gradient is ever materialised
-    (misc/RecurrentFusionModel.py:276 + misc/utils.py:163-184)."""
+    (misc/RecurrentFusionModel.py:276 + misc/utils.py:163-184).
+
+    `kd` = None, or (teacher (B, >= S, V+1) f32 with unit stride in the last dimension, alpha, inv_temp) for distillation:
+    rfn_kd_logits_fwd / _bwd take the place of the XE pair (rfn.h: loss = (1 - alpha) * xe + alpha * kd), the node keeps the
+    rows' three logsumexps, and `terms` (2 floats, {xe, kd}) is filled for logging.  The teacher is a constant: it is held
+    by the node as it is, outside autograd's saved tensors."""
 
     @staticmethod
-    def forward(ctx, model, save_bwd, drop, seed, ids, target, mask, eps, comb, h0, c0, *params):
+    def _criterion_fwd(d, B, S, logits, target, mask, eps, kd, stats, scratch, loss, terms, st):
+        if kd is None:
+            N.check(N.lib.rfn_xe_logits_fwd(logits, d.V1, B, S, d.V1, target.data_ptr(), target.stride(0), mask.data_ptr(),
+                                            mask.stride(0), float(eps), stats.data_ptr(), scratch.data_ptr(), loss.data_ptr(), 0, st),
+                    'rfn_xe_logits_fwd')
+        else:
+            z, alpha, it = kd
+            N.check(N.lib.rfn_kd_logits_fwd(logits, d.V1, B, S, d.V1, target.data_ptr(), target.stride(0), mask.data_ptr(),
+                                            mask.stride(0), float(eps), z.data_ptr(), z.stride(0), z.stride(1), alpha, it,
+                                            stats.data_ptr(), scratch.data_ptr(), loss.data_ptr(), 0, N.ptr(terms), st),
+                    'rfn_kd_logits_fwd')
+
+    @staticmethod
+    def forward(ctx, model, save_bwd, drop, seed, ids, target, mask, eps, kd, terms, comb, h0, c0, *params):
         d = model._dims_for(drop)
         B, S = ids.shape
         dev = comb.device
@@ -294,21 +312,20 @@ class _DecoderLossFn(torch.autograd.Function):
         N.check(N.lib.rfn_decoder_fwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(), ids.data_ptr(),
                                       ids.stride(0), None, ws.data_ptr(), ws_bytes, int(train), seed, st), 'rfn_decoder_fwd')
         logits = N.lib.rfn_decoder_logits(C.byref(d), B, S, int(train), ws.data_ptr())
-        lse = torch.empty(S * B, device=dev)
-        scratch = torch.empty(B * S, device=dev)
+        nk = 1 if kd is None else 3                  # row statistics / scratch arrays per row (rfn.h)
+        lse = torch.empty(nk * S * B, device=dev)
+        scratch = torch.empty(min(nk, 2) * B * S, device=dev)
         loss = torch.zeros(1, device=dev)
-        N.check(N.lib.rfn_xe_logits_fwd(logits, d.V1, B, S, d.V1, target.data_ptr(), target.stride(0), mask.data_ptr(),
-                                        mask.stride(0), float(eps), lse.data_ptr(), scratch.data_ptr(), loss.data_ptr(), 0, st),
-                'rfn_xe_logits_fwd')
+        _DecoderLossFn._criterion_fwd(d, B, S, logits, target, mask, eps, kd, lse, scratch, loss, terms, st)
         if train:
             ctx.model, ctx.seed, ctx.B, ctx.S, ctx.drop, ctx.eps = model, seed, B, S, drop, float(eps)
-            ctx.ids, ctx.target, ctx.mask, ctx.params, ctx.consumed = ids, target, mask, params, False
+            ctx.ids, ctx.target, ctx.mask, ctx.params, ctx.consumed, ctx.kd = ids, target, mask, params, False, kd
             ctx.save_for_backward(comb, h0, c0, lse, ws)
         return loss[0]
 
     @staticmethod
     def backward(ctx, g):
-        model, B, S = ctx.model, ctx.B, ctx.S
+        model, B, S, kd = ctx.model, ctx.B, ctx.S, ctx.kd
         comb, h0, c0, lse, ws = ctx.saved_tensors
         d = model._dims_for(ctx.drop)
         dev = comb.device
@@ -322,22 +339,27 @@ class _DecoderLossFn(torch.autograd.Function):
                                           ctx.ids.data_ptr(), ctx.ids.stride(0), None, ws.data_ptr(), ws.numel(), 1, ctx.seed, st),
                     'rfn_decoder_fwd (recompute)')
             lse = torch.empty_like(lse)
-            tmp, junk = torch.empty(B * S, device=dev), torch.zeros(1, device=dev)
-            N.check(N.lib.rfn_xe_logits_fwd(N.lib.rfn_decoder_logits(C.byref(d), B, S, 1, ws.data_ptr()), d.V1, B, S, d.V1,
-                                            ctx.target.data_ptr(), ctx.target.stride(0), ctx.mask.data_ptr(), ctx.mask.stride(0),
-                                            ctx.eps, lse.data_ptr(), tmp.data_ptr(), junk.data_ptr(), 0, st), 'rfn_xe_logits_fwd')
+            tmp, junk = torch.empty((1 if kd is None else 2) * B * S, device=dev), torch.zeros(1, device=dev)
+            _DecoderLossFn._criterion_fwd(d, B, S, N.lib.rfn_decoder_logits(C.byref(d), B, S, 1, ws.data_ptr()), ctx.target,
+                                          ctx.mask, ctx.eps, kd, lse, tmp, junk, None, st)
         ctx.consumed = True
         g = g.contiguous().float()
         logits = N.lib.rfn_decoder_logits(C.byref(d), B, S, 1, ws.data_ptr())
-        N.check(N.lib.rfn_xe_logits_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
-                                        ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, lse.data_ptr(), 1.0, g.data_ptr(), st),
-                'rfn_xe_logits_bwd')
+        if kd is None:
+            N.check(N.lib.rfn_xe_logits_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
+                                            ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, lse.data_ptr(), 1.0, g.data_ptr(), st),
+                    'rfn_xe_logits_bwd')
+        else:
+            z, alpha, it = kd
+            N.check(N.lib.rfn_kd_logits_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
+                                            ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, z.data_ptr(), z.stride(0), z.stride(1),
+                                            alpha, it, lse.data_ptr(), 1.0, g.data_ptr(), st), 'rfn_kd_logits_bwd')
         d_comb, d_h0, d_c0 = torch.empty_like(comb), torch.empty_like(h0), torch.empty_like(c0)
         N.check(N.lib.rfn_decoder_bwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
                                       ctx.ids.data_ptr(), ctx.ids.stride(0), None, None, d_comb.data_ptr(), d_h0.data_ptr(),
                                       d_c0.data_ptr(), gtable, ws.data_ptr(), ws.numel(), ctx.seed, st), 'rfn_decoder_bwd')
         model._bucket_done('decoder', flats['decoder'])
-        return (None,) * 8 + (d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
+        return (None,) * 10 + (d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
 
 
 class RecurrentFusionModel(nn.Module):
@@ -440,6 +462,7 @@ class RecurrentFusionModel(nn.Module):
         self._weights_epoch = 0          # bumped by FusedClampAdam.step (it writes parameters behind autograd's back)
         self._last_flat_grads = {}
         self._steps_cache = None
+        self.last_distill = None         # forward_loss with a teacher: {'xe', 'kd'}, the two loss terms as 0-dim device tensors
         # set by graphed.GraphedTrainStep while it captures / warms up: run exactly this many decoder steps instead of
         # stopping at the first all-zero label column (the loader's masks are zero on the extra steps)
         self.fixed_decoder_steps = None
@@ -661,7 +684,27 @@ class RecurrentFusionModel(nn.Module):
         log_prob = self._decode_teacher_forced(seq[:, :S], comb, h, c, train, seed, self.ss_prob)
         return log_prob, list(reason.unbind(0))
 
-    def forward_loss(self, fc_feats, att_feats, seq, masks, top_words, crit, reason_weight=1.0):
+    def _check_teacher(self, teacher, B, S, dev):
+        """The distillation teacher of forward_loss: a CUDA f32 tensor indexed (B, T_t >= S, V+1), unit stride in the last
+        dimension, any strides in the first two (forward's batch-major log-probs, EnsembleDecoder.teacher_logits' view of a
+        time-major buffer).  Runs before any native call."""
+        V1 = self.vocab_size + 1
+        if not torch.is_tensor(teacher):
+            raise N.RfnError('teacher must be a tensor (B, T, V+1) of logits or log-probs, got %s' % type(teacher).__name__)
+        if teacher.dim() != 3 or teacher.size(0) != B or teacher.size(1) < S or teacher.size(2) != V1:
+            raise N.RfnError('teacher has shape %s, this pass needs (%d, >= %d, %d)' % (tuple(teacher.shape), B, S, V1))
+        if teacher.dtype != torch.float32:
+            raise N.RfnError('teacher must be float32, got %s' % teacher.dtype)
+        if not teacher.is_cuda:
+            raise N.RfnError('teacher must live on the GPU: the HIP path has no CPU fallback')
+        if teacher.device != dev:
+            raise N.RfnError('teacher lives on %s, the features on %s' % (teacher.device, dev))
+        if teacher.stride(2) != 1 or abs(teacher.stride(0)) < V1 or abs(teacher.stride(1)) < V1:
+            raise N.RfnError('teacher rows need unit stride and must not overlap: strides %s' % (tuple(teacher.stride()),))
+        return teacher.detach()
+
+    def forward_loss(self, fc_feats, att_feats, seq, masks, top_words, crit, reason_weight=1.0, teacher=None, kd_alpha=0.5,
+                     kd_temperature=1.0):
         """The XE train step's forward AND criterion in one call (opt-in) ->
         (loss, reason_pred): the value and the gradients of
             log_prob, reason_pred = model(fc_feats, att_feats, seq)
@@ -670,8 +713,25 @@ class RecurrentFusionModel(nn.Module):
         tensor, its gradient and the four passes over them: the language term comes straight from the logits and its
         backward writes d logits in place (rfn_xe_logits_fwd / _bwd).  Equal to the two-call form to rounding (the row
         logsumexp is the same; the loss terms are summed in the same order).  Scheduled sampling needs the per-step
-        distributions and takes the two-call form."""
+        distributions and takes the two-call form.
+
+        Distillation (rfn.h rfn_kd_logits_fwd): with `teacher` -- (B, T_t >= S, V+1) f32 logits or log-probs on the device, unit
+        stride in the last dimension; `teacher_model(fc, att, seq)[0]` under no_grad, or EnsembleDecoder.teacher_logits -- the
+        language term becomes (1 - kd_alpha) * xe + kd_alpha * kd, kd = the masked KL(teacher || student) at temperature
+        kd_temperature times its square, still one pass over the logits rows in each direction (one more read of the teacher
+        row).  The teacher is a constant.  `self.last_distill` = {'xe', 'kd'}: the two terms as 0-dim device tensors (no
+        read-back).  kd_alpha == 0 is the call without a teacher, bit for bit ('kd' is then None).  Scheduled sampling does not
+        combine with a teacher: its rows are conditioned on the ground-truth prefix."""
         from .criteria import _MLMFn
+        if teacher is not None:
+            if self.ss_prob > 0:
+                raise N.RfnError('distillation does not combine with scheduled sampling (ss_prob = %g): the teacher\'s rows are '
+                                 'conditioned on the ground-truth prefix' % self.ss_prob)
+            kd_alpha, kd_temperature = float(kd_alpha), float(kd_temperature)
+            if not 0.0 <= kd_alpha <= 1.0:
+                raise N.RfnError('kd_alpha = %g is outside [0, 1]' % kd_alpha)
+            if not (0.0 < kd_temperature < float('inf')):
+                raise N.RfnError('kd_temperature = %g must be positive and finite' % kd_temperature)
         if self.ss_prob > 0:
             log_prob, reason = self.forward(fc_feats, att_feats, seq)
             return crit(log_prob, seq[:, 1:], masks[:, 1:], reason, top_words, reason_weight), reason
@@ -683,6 +743,11 @@ class RecurrentFusionModel(nn.Module):
         if int(self.dedup_seq_per_img) > 1:
             raise N.RfnError('forward_loss does not combine with dedup_seq_per_img; use forward() + the criterion')
         dev = fc_feats[0].device
+        kd = terms = None
+        if teacher is not None:
+            z = self._check_teacher(teacher, seq.size(0), S, dev)
+            if kd_alpha > 0.0:
+                kd, terms = (z, kd_alpha, 1.0 / kd_temperature), torch.empty(2, device=dev)
         comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
         seq = seq.to(dev).long()
         masks = masks.to(dev).float()
@@ -693,7 +758,9 @@ class RecurrentFusionModel(nn.Module):
         eps = float(crit.label_smoothing_epsilon) if crit.use_label_smoothing else 0.0
         params = self._params_of(self._decoder_slots)
         lang = _DecoderLossFn.apply(self, torch.is_grad_enabled(), train, seed, seq[:, :S], seq[:, 1:S + 1], masks[:, 1:S + 1], eps,
-                                    comb, h, c, *params)
+                                    kd, terms, comb, h, c, *params)
+        if teacher is not None:
+            self.last_distill = {'xe': terms[0], 'kd': terms[1]} if kd is not None else {'xe': lang.detach(), 'kd': None}
         heads = list(reason.unbind(0))
         return lang + _MLMFn.apply(float(reason_weight) / len(heads), top_words, *heads), heads
 
