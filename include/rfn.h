@@ -1015,6 +1015,72 @@ typedef struct rfn_beam_lexical {
     int32_t* state_n;             /* (NB, 2^C) */
     int32_t* done_state;          /* (NB, max_done) */
 } rfn_beam_lexical;
+/* ---- stochastic beam search: W distinct sampled captions (off by default; the reference has none) -------------------------
+ * After Kool, van Hoof and Welling 2019, "Stochastic beams and where to find them": one beam search of width W on
+ * Gumbel-perturbed log-probabilities returns W distinct captions that are an exact sample WITHOUT replacement from the model's
+ * distribution over captions; row 0 is an exact ordinary sample, and the perturbed scores give importance weights.
+ *
+ * Noise.  The search has a 64-bit seed and a 64-bit offset0.  Row r = k * W + j (image k, beam row j), step t in [1, S], token
+ * v: n = the upper 24 bits (word >> 8) of word 0 of Philox4x32-10 with key = seed and counter = (idx = r * V1 + v, offset =
+ * offset0 + t), the layout of rfn_dropout_mask; u = (n + 0.5) / 2^24, never 0 or 1; e = -ln(-ln u).  All in fp64.
+ *
+ * State.  Every row holds, in fp64, phi (the log-probability of its prefix) and G (its perturbed log-probability), and the
+ * flags live and finished (finished: live, and its last token is 0).  Before step 1 only row 0 of an image is live, with phi = 0
+ * and G = the draw e of (r = k * W, v = 0, t = 0); the other rows are dead (phi = G = -inf).  The root's G must be a Gumbel(0)
+ * draw and not the constant 0: the maximum of the captions' perturbed scores is such a draw, and fixing it conditions every G
+ * below it -- the SET drawn is the same either way (G' is increasing in G_j), but the weights below assume unconditional scores
+ * and come out biased under the constant (their sum averages 0.83 instead of 1 on the 40-caption model of tests/sbs_cpu.py).
+ * rfn_beam_sbs_begin writes that state (one launch); rfn_beam_loop_ex4 calls it.
+ *
+ * Step t of image k:
+ *   - a live, unfinished row j with log-prob row x -- the fp32 bits rfn_log_softmax_fwd writes, -inf where the decoding
+ *     constraints blocked a token; a -inf or NaN entry is never a candidate -- has, per token v, key_v = double(x_v) + e,
+ *     gamma_v = phi_j + key_v and Z_j = max_v gamma_v.  Candidate (j, v) has phi' = phi_j + double(x_v) and
+ *     G' = -ln(exp(-G_j) - exp(-Z_j) + exp(-gamma_v)), evaluated as d = G_j - gamma_v + log1mexp(gamma_v - Z_j), G' = G_j -
+ *     max(0, d) - log1p(exp(-|d|)), with log1mexp(a) = ln(-expm1(a)) for a > -ln 2 and log1p(-exp(a)) otherwise; the argmax
+ *     child (the first entry of the row's list: largest key, lowest token among equals) gets G' = G_j exactly;
+ *   - a live finished row has the single candidate "itself": token 0, token log-prob 0, phi and G unchanged.  Carrying finished
+ *     rows as candidates is what makes the sample exact;
+ *   - the new rows are the min(W, candidates) candidates of largest G', stored in descending G', ties by source row ascending,
+ *     then token ascending.  Rows beyond that are dead: live = 0, phi = G = -inf, tokens and token log-probs 0, order = identity,
+ *     next_ids = 0.  A row becomes finished when its token is 0; at t = S every row is closed as it stands;
+ *   - G' is non-decreasing in gamma_v for a fixed row, so the image's W best candidates lie inside each row's W best key_v: the
+ *     per-row lists of rfn_log_softmax_topk_gumbel are all a row has to hand over.
+ * Weights after step S: with kappa = G of the last live row, live rows before the last get weight = exp(phi) / q, q =
+ * -expm1(-exp(phi - kappa)); the last live row and the dead rows get 0 -- Kool et al.'s estimator over W - 1 samples with the
+ * W-th as threshold: sum_i weight_i f(caption_i) is an unbiased estimate of E f.  With decoding constraints the weights are
+ * RELATIVE: the restricted distribution is not renormalised (phi sums the model's own log-probs), so they estimate sums over the
+ * allowed captions, not expectations under a renormalised model.
+ *
+ * rfn_log_softmax_topk_gumbel: one block per row, the structure and limits of rfn_log_softmax_topk_masked (W <= 32, the same
+ * log-sum-exp, hence the same log-prob bits; blk == NULL: no block list).  Rows with live[r] == 0 are skipped, none of their
+ * outputs is written.  Per live row the W best candidates by key (descending, token ascending): topk64 (rows, W) fp64 keys, topv
+ * their own fp32 log-probs, topi their tokens; a row with fewer than W candidates fills the rest with (-inf, -inf, 0).  offset is
+ * offset0 + t of the step that READS the lists.  Error codes as rfn_log_softmax_topk_masked; live or topk64 NULL: RFN_ERR_ARG.
+ *
+ * rfn_beam_step_sbs: one block per image.  beam_seq / beam_lp keep the (S, NB, W) layout of rfn_beam_step (zero-initialised by the
+ * caller), so rfn_decode_blocklist reads them as it does there: a finished row's history ends in 0 and is left alone.  phi /
+ * gumbel (NB, W) fp64 and live (NB * W) int32 are the state above; order / next_ids as in rfn_beam_step_topk (a finished row
+ * continues the row it came from and feeds token 0, a dead row continues itself).  weight (NB, W) fp64 and n_live (NB) int32 are
+ * written at t == S only.  RFN_ERR_SHAPE: W > 32, S > 64, t outside [1, S]; RFN_ERR_ARG: a NULL pointer. */
+int rfn_log_softmax_topk_gumbel(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk, int64_t ld_blk,
+                                const int32_t* blk_n, const int32_t* live, uint64_t seed, uint64_t offset, double* topk64,
+                                float* topv, int32_t* topi, void* stream);
+int rfn_beam_sbs_begin(int NB, int W, int V1, uint64_t seed, uint64_t offset0, double* phi, double* gumbel, int32_t* live,
+                       void* stream);
+int rfn_beam_step_sbs(const double* topk64, const float* topv, const int32_t* topi, int V1, int W, int S, int t, int NB,
+                      int64_t* beam_seq, float* beam_lp, double* phi, double* gumbel, int32_t* live, int32_t* order,
+                      int64_t* next_ids, double* weight, int32_t* n_live, void* stream);
+/* What rfn_beam_loop_ex4 takes besides the constraints, the diversity and the required words. */
+typedef struct rfn_beam_stochastic {
+    uint64_t seed, offset0;       /* the noise of step t is drawn at (seed, offset0 + t) */
+    double* phi;                  /* (NB, W), device */
+    double* gumbel;               /* (NB, W), device */
+    int32_t* live;                /* (NB * W), device; the loop sets all three with rfn_beam_sbs_begin */
+    double* weight;               /* (NB, W), written by the last step */
+    int32_t* n_live;              /* (NB), written by the last step */
+    double* topk64;               /* (NB * W, W) scratch: the rows' keys */
+} rfn_beam_stochastic;
 /* dst[r,:] = src[order[r],:]  (src != dst) */
 int rfn_gather_rows(const float* src, float* dst, const int32_t* order, int rows, int R, void* stream);
 
@@ -1203,6 +1269,18 @@ int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const float* cons
                       float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
                       const rfn_decode_constraints* cons, const rfn_beam_diversity* div, const rfn_beam_lexical* lex,
                       void* stream);
+/* rfn_beam_loop_ex3 as a stochastic beam search (above): per step rfn_beam_step_sbs in place of rfn_beam_step_topk and
+ * rfn_log_softmax_topk_gumbel in place of rfn_log_softmax_topk_masked (and one rfn_beam_sbs_begin before the first step), the two rfn_gather_rows and the optional rfn_decode_blocklist
+ * as they were -- the launch count per step is the plain search's.  beam_sum, the done-beam arrays and active are not used and may
+ * be NULL with sbs; beam_seq / beam_lp are required.  cons composes (the weights are then relative, see above).  sbs == NULL: the
+ * calls and the bits of rfn_beam_loop_ex3, which forwards here.  RFN_ERR_UNSUPPORTED: sbs with div->groups > 1 or with lex;
+ * RFN_ERR_SHAPE: S > 64; RFN_ERR_ARG: a NULL member of sbs. */
+int rfn_beam_loop_ex4(const rfn_dims* d, int NB, int W, int S, const float* const* params, const float* comb,
+                      const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp, int64_t* beam_seq,
+                      float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids, int64_t* done_seq, float* done_lp,
+                      float* done_p, int32_t* done_n, int32_t* active, int max_done, void* ws, size_t ws_bytes, uint64_t seed,
+                      const rfn_decode_constraints* cons, const rfn_beam_diversity* div, const rfn_beam_lexical* lex,
+                      const rfn_beam_stochastic* sbs, void* stream);
 
 /* ---- self-critical reward: CIDEr-D of token-id captions (get_rewards.py:39-112, cider/pyciderevalcap/ciderD) ---------
  * CiderD(n=4, sigma) as compute_reward calls it (csrc/rfn_reward.hip).  A caption is the ids of its row up to and including

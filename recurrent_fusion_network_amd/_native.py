@@ -102,6 +102,12 @@ class BeamLexical(C.Structure):
                 ('init_state', C.c_void_p), ('wantv', C.c_void_p), ('state_n', C.c_void_p), ('done_state', C.c_void_p)]
 
 
+class BeamStochastic(C.Structure):
+    """rfn_beam_stochastic (rfn.h)."""
+    _fields_ = [('seed', C.c_uint64), ('offset0', C.c_uint64), ('phi', C.c_void_p), ('gumbel', C.c_void_p), ('live', C.c_void_p),
+                ('weight', C.c_void_p), ('n_live', C.c_void_p), ('topk64', C.c_void_p)]
+
+
 DECODE_MAX_IDS = 64
 LEX_MAX_SETS, LEX_MAX_IDS = 3, 16
 
@@ -117,7 +123,7 @@ def _load():
     lib.rfn_error_string.restype = C.c_char_p
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
     DP, CP, SP = C.POINTER(Dims), C.POINTER(DecodeConstraints), C.POINTER(DecodeSampling)
-    BDP, BLP = C.POINTER(BeamDiversity), C.POINTER(BeamLexical)
+    BDP, BLP, BSP = C.POINTER(BeamDiversity), C.POINTER(BeamLexical), C.POINTER(BeamStochastic)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -215,6 +221,11 @@ def _load():
         'rfn_beam_loop_ex': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, P]),
         'rfn_beam_loop_ex2': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, P]),
         'rfn_beam_loop_ex3': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, BLP, P]),
+        # stochastic beam search (rfn.h)
+        'rfn_log_softmax_topk_gumbel': (C.c_int, [P, L, I, I, I, P, L, P, P, U64, U64, P, P, P, P]),
+        'rfn_beam_sbs_begin': (C.c_int, [I, I, I, U64, U64, P, P, P, P]),
+        'rfn_beam_step_sbs': (C.c_int, [P, P, P, I, I, I, I, I] + [P] * 10),
+        'rfn_beam_loop_ex4': (C.c_int, [DP, I, I, I] + [P] * 18 + [I, P, SZ, U64, CP, BDP, BLP, BSP, P]),
         'rfn_log_softmax_topk_want': (C.c_int, [P, L, I, I, I, I, P, L, I, P, L, P, P, P, P, P]),
         'rfn_beam_step_lex': (C.c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I] + [P] * 14),
         'rfn_decoder_fwd_sampled': (C.c_int, [DP, I, I, P, P, P, P, P, L, F, F, P, P, P, P, SZ, I, U64, P]),

@@ -45,7 +45,8 @@ static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, 
                              float* logp, int64_t ld_logp, void* ws, size_t ws_bytes, uint64_t seed_arg, int step,
                              void* st, float* topv = nullptr, int32_t* topi = nullptr, int topw = 0, int row_div = 1,
                              const int32_t* blk = nullptr, int64_t ld_blk = 0, const int32_t* blk_n = nullptr,
-                             const int32_t* want = nullptr, int n_want = 0, float* wantv = nullptr) {
+                             const int32_t* want = nullptr, int n_want = 0, float* wantv = nullptr,
+                             const rfn_beam_stochastic* sbs = nullptr, uint64_t sbs_offset = 0) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
@@ -79,7 +80,11 @@ static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, 
         }
         // beam search: W best per row, no full rows (blk: of the rows masked by their block lists)
         // (want: plus the log-probs of the image's required tokens, for the lexically constrained search)
-        if (topv && want)
+        // (sbs: the W best Gumbel-perturbed entries of the live rows, for the stochastic search)
+        if (topv && sbs)
+            RFN_TRY(rfn_log_softmax_topk_gumbel(lg, V1, B, V1, topw, blk, ld_blk, blk_n, sbs->live, sbs->seed, sbs_offset, sbs->topk64,
+                                                topv, topi, st));
+        else if (topv && want)
             RFN_TRY(rfn_log_softmax_topk_want(lg, V1, B, V1, topw, row_div, want, n_want, n_want, blk, ld_blk, blk_n, topv, topi, wantv,
                                               st));
         else if (topv) RFN_TRY(rfn_log_softmax_topk_masked(lg, V1, B, V1, topw, blk, ld_blk, blk_n, topv, topi, st));
@@ -214,12 +219,15 @@ extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const fl
 // div: diverse beam search (rfn.h): the step is rfn_beam_step_div on the same top-W lists, everything else is unchanged.
 // lex: lexically constrained search (rfn.h): the step is rfn_beam_step_lex, and every decoder step also writes the log-probs of the
 // image's required tokens (rfn_log_softmax_topk_want in place of rfn_log_softmax_topk_masked); the launch count is unchanged.
-extern "C" int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+// sbs: stochastic beam search (rfn.h): the step is rfn_beam_step_sbs on the lists rfn_log_softmax_topk_gumbel writes in place of
+// rfn_log_softmax_topk_masked, with the noise of (sbs->seed, sbs->offset0 + t) for step t; the launch count is unchanged.
+extern "C" int rfn_beam_loop_ex4(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
                                  const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
                                  int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
                                  int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
                                  void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons,
-                                 const rfn_beam_diversity* div, const rfn_beam_lexical* lex, void* st) {
+                                 const rfn_beam_diversity* div, const rfn_beam_lexical* lex, const rfn_beam_stochastic* sbs,
+                                 void* st) {
     // `logp` holds, per beam row, its W best log-probs and their tokens (2 * W values): the search never looks at more
     // (:463-466), so the full (rows, V+1) log-prob matrix is neither written nor read back
     RFN_TRY(check_dims(d));
@@ -242,13 +250,23 @@ extern "C" int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const 
         if (!lex->want || !lex->want_bits || !lex->init_state || !lex->wantv || !lex->state_n || !lex->done_state || !beam_seq)
             return RFN_ERR_ARG;
     }
+    if (sbs) {
+        if (diverse || lex) return RFN_ERR_UNSUPPORTED;
+        if (S > 64) return RFN_ERR_SHAPE;
+        if (!sbs->phi || !sbs->gumbel || !sbs->live || !sbs->weight || !sbs->n_live || !sbs->topk64 || !beam_seq || !beam_lp)
+            return RFN_ERR_ARG;
+    }
     float* topv = logp;
     int32_t* topi = (int32_t*)(logp + (size_t)rows * W);
     float *hc = h, *cc = c, *ha = h_alt, *ca = c_alt;
     if (hipMemsetAsync(ids, 0, (size_t)rows * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;
+    if (sbs) RFN_TRY(rfn_beam_sbs_begin(NB, W, V1, sbs->seed, sbs->offset0, sbs->phi, sbs->gumbel, sbs->live, st));
     for (int t = 0; t <= S; ++t) {
         if (t >= 1) {
-            if (lex)   // at t == 1 the step takes the occupancy from init_state and writes state_n
+            if (sbs)
+                RFN_TRY(rfn_beam_step_sbs(sbs->topk64, topv, topi, V1, W, S, t, NB, beam_seq, beam_lp, sbs->phi, sbs->gumbel, sbs->live,
+                                          order, ids, sbs->weight, sbs->n_live, st));
+            else if (lex)   // at t == 1 the step takes the occupancy from init_state and writes state_n
                 RFN_TRY(rfn_beam_step_lex(topv, topi, lex->wantv, lex->want, lex->want_bits, lex->n_want, lex->n_sets, V1, W, S, t, NB,
                                           max_done, beam_seq, beam_lp, beam_sum, order, ids, done_seq, done_lp, done_p, done_n,
                                           lex->state_n, lex->done_state, lex->init_state, active, st));
@@ -270,12 +288,22 @@ extern "C" int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const 
         RFN_TRY(decoder_step_impl(d, rows, prm, comb, cproj, ids, nullptr, 0, hc, cc, nullptr, nullptr, 0, ws, ws_bytes, seed, t, st,
                                   topv, topi, W, W,   // the W rows of an image share its thought vectors (comb / cproj: NB rows)
                                   cons ? cons->blk : nullptr, RFN_DECODE_MAX_IDS + S, cons ? cons->blk_n : nullptr,
-                                  lex ? lex->want : nullptr, lex ? lex->n_want : 0, lex ? lex->wantv : nullptr));
+                                  lex ? lex->want : nullptr, lex ? lex->n_want : 0, lex ? lex->wantv : nullptr, sbs,
+                                  sbs ? sbs->offset0 + (uint64_t)(t + 1) : 0));   // this step's lists are read by step t + 1
     }
     if (hc != h) {   // an odd number of swaps: bring the live state home
         RFN_TRY(mem_batch({{h, hc, (long)rows * R}, {c, cc, (long)rows * R}}, st));
     }
     return RFN_OK;
+}
+extern "C" int rfn_beam_loop_ex3(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
+                                 const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,
+                                 int64_t* beam_seq, float* beam_lp, float* beam_sum, int32_t* order, int64_t* ids,
+                                 int64_t* done_seq, float* done_lp, float* done_p, int32_t* done_n, int32_t* active, int max_done,
+                                 void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons,
+                                 const rfn_beam_diversity* div, const rfn_beam_lexical* lex, void* st) {
+    return rfn_beam_loop_ex4(d, NB, W, S, prm, comb, cproj, h, c, h_alt, c_alt, logp, beam_seq, beam_lp, beam_sum, order, ids, done_seq,
+                             done_lp, done_p, done_n, active, max_done, ws, ws_bytes, seed, cons, div, lex, nullptr, st);
 }
 extern "C" int rfn_beam_loop_ex2(const rfn_dims* d, int NB, int W, int S, const float* const* prm, const float* comb,
                                  const float* cproj, float* h, float* c, float* h_alt, float* c_alt, float* logp,

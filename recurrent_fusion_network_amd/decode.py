@@ -173,6 +173,76 @@ def run_beam_loop(stepper, bufs, cons, div=None, lex=None):
             'rfn_beam_loop_ex3')
 
 
+class _Stochastic:
+    """Stochastic beam search of one call (rfn.h "stochastic beam search"; RecurrentFusionModel.sample_distinct): opt['seed'] (a
+    64-bit integer, None = a fresh one from torch's generator) keys the Gumbel noise; the decoding constraints' keys are parsed by
+    _Constraints.  Every other key is refused by name: the search samples the model's own distribution, so nothing that reshapes it
+    (temperature, top_k, top_p), ranks its rows otherwise (length_penalty, consensus, group_size, require) or replays tokens
+    (force_ids) applies."""
+
+    KEYS = ('seed', 'block_ngram', 'banned_ids', 'bad_endings')
+    MAX_N = 32
+
+    @classmethod
+    def parse(cls, opt, n, S):
+        temp = opt.get('temperature', None)                  # the neutral value is not an error
+        bad = sorted(k for k in opt if k not in cls.KEYS and not (k == 'temperature' and (temp is None or float(temp) == 1.0)))
+        if bad:
+            raise ValueError('sample_distinct takes %s, not %s' % (', '.join(cls.KEYS), ', '.join(map(repr, bad))))
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= cls.MAX_N:
+            raise ValueError('sample_distinct draws 1 <= n <= %d captions per image, got %r' % (cls.MAX_N, n))
+        if S > 64:
+            raise N.RfnError('stochastic beam search supports seq_length <= 64')
+        seed = opt.get('seed', None)
+        if seed is not None and (isinstance(seed, bool) or int(seed) != seed):
+            raise ValueError('seed must be an integer, got %r' % (seed,))
+        s = cls()
+        s.n, s.seed = int(n), (None if seed is None else int(seed) & (2 ** 64 - 1))
+        return s
+
+
+class StochasticBuffers:
+    """The state of a stochastic beam search over B images x W rows x S steps: the beam arrays of BeamBuffers that the search uses
+    (it has no done beams: finished rows stay in the beam), and phi / gumbel / live, weight / n_live and the rows' keys."""
+
+    def __init__(self, B, W, S, dev):
+        self.B, self.W, self.S, self.dev, self.rows = B, W, S, dev, B * W
+        self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
+        self.bl = torch.zeros(S, B, W, device=dev)
+        self.order = torch.zeros(self.rows, dtype=torch.int32, device=dev)
+        self.ids = torch.zeros(self.rows, dtype=torch.long, device=dev)
+        self.phi = torch.zeros(B, W, dtype=torch.float64, device=dev)
+        self.gumbel = torch.zeros(B, W, dtype=torch.float64, device=dev)
+        self.live = torch.zeros(B, W, dtype=torch.int32, device=dev)       # the loop sets the three (rfn_beam_sbs_begin)
+        self.weight = torch.zeros(B, W, dtype=torch.float64, device=dev)
+        self.n_live = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.topk64 = torch.empty(self.rows, W, dtype=torch.float64, device=dev)
+
+    def top_flat(self):
+        return torch.empty(2 * self.rows * self.W, device=self.dev)
+
+    def struct(self, seed, offset0=0):
+        self._struct = N.BeamStochastic(seed, offset0, self.phi.data_ptr(), self.gumbel.data_ptr(), self.live.data_ptr(),
+                                        self.weight.data_ptr(), self.n_live.data_ptr(), self.topk64.data_ptr())
+        return self._struct
+
+
+def run_stochastic_loop(stepper, bufs, cons, noise_seed):
+    """The whole stochastic search in one call (rfn_beam_loop_ex4): S x (bookkeeping, state re-gather, decoder step on the B * W
+    rows ending in the Gumbel top-W).  cons: a parsed _Constraints or None; noise_seed: the 64-bit key of the Gumbel noise (the
+    stepper's own seed keys the dropout masks, as everywhere)."""
+    b, logp = bufs, bufs.top_flat()
+    h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
+    N.check(N.lib.rfn_beam_loop_ex4(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
+                                    stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
+                                    c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), None,
+                                    b.order.data_ptr(), b.ids.data_ptr(), None, None, None, None, None, b.W * b.S,
+                                    stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
+                                    C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None, None, None,
+                                    C.byref(b.struct(noise_seed)), N.stream_ptr()),
+            'rfn_beam_loop_ex4')
+
+
 class _Constraints:
     """The decoding constraints of one call (rfn.h "decoding constraints"): opt['block_ngram'] (0 = off, 2 .. 4),
     opt['banned_ids'] and opt['bad_endings'] (at most 64 ids each, token 0 never banned).  `parse` returns None when all of

@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _native as N
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Lexical,
                      _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit, keep_candidates_n, run_beam_loop,
-                     run_greedy_loop)
+                     run_greedy_loop, run_stochastic_loop, _Stochastic, StochasticBuffers)
 
 _INIT = 0.1
 
@@ -919,6 +919,49 @@ class RecurrentFusionModel(nn.Module):
             h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
         out = self._sample_replayed(comb, h, c, train, seed, want_grad, opt.get('temperature', 1.0), force, n)
         return (*out, list(reason.unbind(0)))
+
+    def sample_distinct(self, fc_feats, att_feats, n, opt={}):
+        """n DISTINCT sampled captions per image by stochastic beam search (rfn.h "stochastic beam search"; Kool et al. 2019; the
+        reference has nothing of the kind): one beam search of width n on Gumbel-perturbed log-probabilities, an exact sample
+        without replacement from the model's distribution over captions -> (seq (B*n, S) int64, seqLogprobs (B*n, S) f32,
+        reason_pred), rows image-major in descending perturbed score (row k * n is an exact ordinary sample of image k), zeros
+        after a caption's END and in dead rows (an image with fewer than n possible captions).  Nothing is read back: no early-exit
+        trim, no synchronisation.  Sets
+            self.stochastic_beams = {'logprob', 'gumbel', 'weight': (B, n) f64, 'n_live': (B,) int32}   device tensors: the
+                caption's log-probability (the ascending fp64 sum of its seqLogprobs), its perturbed score G, and its importance
+                weight -- sum_j weight[k, j] * f(caption j) estimates E f under the model (the last live row is the threshold and
+                weighs 0); -inf / -inf / 0 for dead rows
+            self.candidates = {'seq': (B, n, S), 'n_cand': n_live}   what rewards.consensus, rewards.diversity,
+                evalcap.DiversityEval and decode.rescore take, as after sample_beam's keep_candidates.
+        opt: 'seed' (the 64-bit key of the noise; default a fresh one from torch's generator, so torch.manual_seed reproduces a
+        call) and the decoding constraints 'block_ngram', 'banned_ids', 'bad_endings' -- the weights are then relative: the
+        restricted distribution is not renormalised.  Every other key raises ValueError by name.  Runs under no_grad only; dropout
+        follows the module's mode, as in sample_beam.  n <= 32, seq_length <= 64; needs the hoisted decoder cell.  EnsembleDecoder
+        has no such method, and no gradient estimator is built on the weights."""
+        B, S, V1 = self._check_inputs(fc_feats, att_feats), self.seq_length, self.vocab_size + 1
+        sb = _Stochastic.parse(opt, n, S)
+        if sb.n > V1:
+            raise ValueError('sample_distinct draws n <= vocab_size + 1 = %d captions per image, got %d' % (V1, sb.n))
+        cons = _Constraints.parse(opt, V1, S)
+        if torch.is_grad_enabled():
+            raise N.RfnError('stochastic beam search is not differentiated: call sample_distinct under no_grad')
+        if int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
+            raise N.RfnError('n rows per image need the hoisted decoder cell (path_flags select another form)')
+        W = sb.n
+        drop = bool(self.training)
+        seed = _fresh_seed() if drop else 0
+        noise_seed = sb.seed if sb.seed is not None else _fresh_seed()
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, drop, seed)
+        dev = comb.device
+        stepper = _Stepper(self, comb, h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous(),
+                           drop, seed)
+        bufs = StochasticBuffers(B, W, S, dev)
+        run_stochastic_loop(stepper, bufs, cons, noise_seed)
+        cands = bufs.bs.permute(1, 2, 0).contiguous()                                # (B, n, S)
+        self.stochastic_beams = {'logprob': bufs.phi, 'gumbel': bufs.gumbel, 'weight': bufs.weight, 'n_live': bufs.n_live}
+        self.candidates = {'seq': cands, 'n_cand': bufs.n_live}
+        self.consensus = None
+        return cands.view(B * W, S), bufs.bl.permute(1, 2, 0).reshape(B * W, S), list(reason.unbind(0))
 
     def _sample_replayed(self, comb, h, c, train, seed, want_grad, temperature, force, n=1):
         """Multinomial (:623-631) or replayed ids -> (seq, seq_lp, logp).  ONE pass of the training decoder is both the pass

@@ -320,7 +320,77 @@ def lexical_ab(out_path, rounds=7):
         json.dump(res, f, indent=1)
         f.write('\n')
 
+def stochastic_ab(out_path, rounds=7):
+    """--stochastic [--out FILE]: config 5, sample_distinct with n = 5 alternating with the plain sample_beam(beam_size = 5) call of this
+    same tree -- which issues the parent's launches by construction and so stands in for the parent -- and with sample(sample_n = 5).
+    Windows of 5 calls after a warm-up call, medians of `rounds`; kernel launches per call by the profiler; and one
+    rfn_log_softmax_topk_gumbel launch next to one rfn_log_softmax_topk launch at 640 x 9488, W = 5, by device events around the
+    single launch."""
+    import statistics
+    from recurrent_fusion_network_amd import _native as N
+    S, V1, W = cfg.seq_length, cfg.vocab_size + 1, 5
+    model.eval()
+
+    def call(kind):
+        with torch.no_grad():
+            if kind == 'sample_distinct_5':
+                return model.sample_distinct(fc, att, W, {'seed': 7})
+            if kind == 'plain_beam_5':
+                return model.sample_beam(fc, att, {'beam_size': W})
+            return model.sample(fc, att, {'sample_max': 0, 'sample_n': W})
+
+    kinds = ('plain_beam_5', 'sample_distinct_5', 'sample_n_5')
+    res = {'config': 'M=4, L=196, D=2048, R=512, V+1=%d, seq=%d, B=%d, 5 rows per image' % (V1, S, B), 'rounds': rounds,
+           'calls_per_window': 5, 'what': 'ms per call, the three settings alternating; sample_n_5 includes its one read-back'}
+    ms = {k: [] for k in kinds}
+    for k in kinds:
+        call(k)
+    for _ in range(rounds):
+        for k in kinds:
+            ms[k].append(timed(lambda: call(k), 5)[0] * 1e3)
+    for k in kinds:
+        res[k] = {'ms': round(statistics.median(ms[k]), 3), 'min': round(min(ms[k]), 3), 'max': round(max(ms[k]), 3),
+                  'launches_per_call': HB.count_launches(lambda: call(k))}
+        print(json.dumps({k: res[k]}), flush=True)
+    res['sample_distinct_over_plain_beam'] = round(res['sample_distinct_5']['ms'] / res['plain_beam_5']['ms'], 4)
+    res['sample_distinct_minus_plain_beam_ms'] = round(res['sample_distinct_5']['ms'] - res['plain_beam_5']['ms'], 3)
+    call('sample_distinct_5')
+    res['distinct_captions_of_5'] = {'sample_distinct_5': round(float(model.stochastic_beams['n_live'].float().mean()), 3)}
+    rows = call('sample_n_5')[0].view(B, W, -1).cpu()
+    res['distinct_captions_of_5']['sample_n_5'] = round(sum(len({tuple(r) for r in img.tolist()}) for img in rows) / B, 3)
+    # one launch of each top-W kernel on randn * 3 logits
+    g = torch.Generator().manual_seed(1)
+    R_ = B * W
+    x = (torch.randn(R_, V1, generator=g) * 3.0).to(dev)
+    tv, ti = torch.empty(R_, W, device=dev), torch.empty(R_, W, dtype=torch.int32, device=dev)
+    tk, live = torch.empty(R_, W, dtype=torch.float64, device=dev), torch.ones(R_, dtype=torch.int32, device=dev)
+
+    def one(fn, reps=50):
+        t = []
+        for _ in range(reps + 5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            N.check(fn())
+            e1.record()
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) * 1e3)
+        return round(sorted(t[5:])[reps // 2], 2)
+
+    res['single_launch_us'] = {
+        'shape': [R_, V1], 'W': W, 'note': 'median of 50, device events around one launch (they include the launch gap)',
+        'rfn_log_softmax_topk': one(lambda: N.lib.rfn_log_softmax_topk(x.data_ptr(), V1, R_, V1, W, tv.data_ptr(), ti.data_ptr(), N.stream_ptr())),
+        'rfn_log_softmax_topk_gumbel': one(lambda: N.lib.rfn_log_softmax_topk_gumbel(x.data_ptr(), V1, R_, V1, W, None, 0, None, live.data_ptr(),
+                                                                                     7, 1, tk.data_ptr(), tv.data_ptr(), ti.data_ptr(),
+                                                                                     N.stream_ptr()))}
+    print(json.dumps(res), flush=True)
+    with open(out_path, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
 PROFILES = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles')
+if '--stochastic' in sys.argv:
+    stochastic_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'decode_stochastic.json'))
+    sys.exit(0)
 if '--lexical' in sys.argv:
     lexical_ab(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(PROFILES, 'decode_lexical.json'))
     sys.exit(0)
