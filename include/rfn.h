@@ -729,6 +729,34 @@ int rfn_kd_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const in
                       const float* mask, int64_t ld_mask, float eps, const float* teacher, int64_t z_sb, int64_t z_st,
                       float alpha, float inv_temp, const float* row_stats, float gscale, const float* gscale_dev,
                       void* stream);
+/* The same pair with a COMPACT teacher: row (b, t) of the teacher is the K <= 32 pairs
+ *   (t_ids[b * i_sb + t * i_st + k], t_val[b * v_sb + t * v_st + k]),  k < K,
+ * e.g. the lists rfn_log_softmax_topk writes, batch-major or time-major (two strides each, in elements).  Their meaning is
+ * exactly rfn_kd_logits_*'s on the dense row z with z[id_k] = val_k and -inf everywhere else:
+ *   p_t(k)  = softmax over the K entries of val * it          p_s(v) = softmax(x * it)(v)
+ *   KL(b,t) = sum_k p_t(k) * (log p_t(k) - log p_s(id_k))
+ * and xe, kd, loss and d loss / d x are as written above (p_t(v) = 0 off the K ids): the teacher's tail mass is dropped and the
+ * K entries are renormalised.  val may be logits or log-probs (every term is invariant to a per-row shift).
+ * An entry is padding when its id is outside [0, V1) or its val is -inf: it contributes 0 and its id is never used as an index,
+ * so a row may hold fewer than K live entries.  The live ids of a row must be distinct (not checked here: the caller's
+ * contract); a row without a live entry is the caller's error, as a dense row without a finite entry is.  A row with m == 0 has
+ * loss terms of exactly 0, _bwd writes zeros over its logits, and neither its ids nor its values are read.
+ * row_stats (3*T*B) = lse(x), lse(x*it), lse over the live entries of val*it (0 for a row with m == 0): the dense pair's layout;
+ * scratch: 2*B*T floats; loss_out, terms_out, gscale, gscale_dev as above.  The xe term and lse(x) are rfn_xe_logits_fwd's bits
+ * at any alpha.  No atomics: the K entries are reduced by one wave's shuffles in a fixed order, so two runs give the same bits.
+ * The student's row is read 16 B per lane under rfn_xe_logits_*'s conditions and element-wise otherwise, whatever the alignment
+ * of t_ids / t_val (K elements per row, read one per lane).  _bwd writes in place: it gathers x[id_k] before any lane of the
+ * row's block writes, writes the teacher-free gradient over the row, and rewrites the K elements behind a block barrier.
+ * RFN_ERR_SHAPE: the checks of rfn_xe_logits_*, alpha / inv_temp as rfn_kd_logits_*, K < 1, K > 32, |i_sb|, |i_st|, |v_sb| or
+ * |v_st| < K.  RFN_ERR_ARG: a NULL pointer (gscale_dev and terms_out may be NULL).  Shape checks come first. */
+int rfn_kd_topk_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                    const float* mask, int64_t ld_mask, float eps, const int32_t* t_ids, int64_t i_sb, int64_t i_st,
+                    const float* t_val, int64_t v_sb, int64_t v_st, int K, float alpha, float inv_temp, float* row_stats,
+                    float* scratch, float* loss_out, int accumulate_loss, float* terms_out, void* stream);
+int rfn_kd_topk_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                    const float* mask, int64_t ld_mask, float eps, const int32_t* t_ids, int64_t i_sb, int64_t i_st,
+                    const float* t_val, int64_t v_sb, int64_t v_st, int K, float alpha, float inv_temp, const float* row_stats,
+                    float gscale, const float* gscale_dev, void* stream);
 /* ReviewNetRewardCriterion policy + entropy terms (misc/utils.py:50-72):
  * loss_out[0] (+)= [ -sum pol(b,t)*mask(b,t) + entropy_reg * sum mask0(b,t) * sum_v lp*exp(lp) ] / B with
  * mask0 = seq > 0, mask = [1, mask0[:, :-1]], pol = input*reward or the reference's PPO-clip surrogate.

@@ -183,6 +183,8 @@ def _load():
         'rfn_xe_logits_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, F, P, P]),
         'rfn_kd_logits_fwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, F, F, P, P, P, I, P, P]),
         'rfn_kd_logits_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, F, F, P, F, P, P]),
+        'rfn_kd_topk_fwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, P, L, L, I, F, F, P, P, P, I, P, P]),
+        'rfn_kd_topk_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, L, P, L, L, I, F, F, P, F, P, P]),
         'rfn_decoder_logits': (P, [DP, I, I, I, P]),
         'rfn_xe_loss': (C.c_int, [P, I, I, I, P, L, P, L, F, F, P, P, I, P, P]),
         'rfn_multilabel_margin': (C.c_int, [P, I, I, P, F, F, P, P, I, P, P]),

@@ -1,5 +1,5 @@
 // The criteria and their gradients: the XE language loss (from log-probs, and fused from the logits), the same with a KL term
-// towards a teacher's rows (distillation), the RL reward criterion, and nn.MultiLabelMarginLoss for the reason heads.  One block of 256 per row writes the row's loss term; sum_k /
+// towards a teacher's rows (distillation; dense rows, or their K <= 32 best entries), the RL reward criterion, and nn.MultiLabelMarginLoss for the reason heads.  One block of 256 per row writes the row's loss term; sum_k /
 // sum_groups_k add the terms in a fixed order (no float atomics), so a loss is bitwise reproducible.
 #include <string.h>
 
@@ -377,6 +377,230 @@ extern "C" int rfn_kd_logits_bwd(float* logits, int64_t ldl, int B, int T, int V
         hipLaunchKernelGGL(kd_logits_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
                            (long)ld_target, mask, (long)ld_mask, eps, teacher, (long)z_sb, (long)z_st, alpha, inv_temp,
                            gscale / (float)B, gscale_dev, row_stats);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+// ---- distillation from a compact teacher: the K <= 32 best entries of each teacher row (rfn.h) ---------------------------
+// The pair above with the teacher's row z given as K (id, value) pairs: z[id_k] = val_k, -inf everywhere else, so p_t lives
+// on the K entries alone and the KL term and its gradient touch K elements of the student's row.  An entry whose id is
+// outside [0, V1) or whose value is -inf is padding (never used as an index).  The student's row is read exactly as the XE
+// pair reads it (log_softmax_row: 16 B per lane or element-wise); the K entries sit in the first K lanes of wave 0, one
+// each, and their reductions are that wave's shuffles (K <= 32 < 64 lanes) in a fixed order: no atomics.
+//   forward : lse(x), lse(x * it) as above; lse over the live entries of val * it -> row_stats[2][r]; the KL sum gathers
+//             x[id_k] from the row this block has just read.
+//   backward: d logits is written IN PLACE, so the order is (1) wave 0 gathers x[id_k] and waits for the loads, block
+//             barrier, (2) all lanes write the teacher-free gradient c * (wx * (p - q) + wk * p_s) over the row and wait for
+//             their stores, block barrier, (3) lane k rewrites element id_k in full, with p_t(k), from its gathered x[id_k]
+//             (the dense kernel's expression; the live ids of a row are distinct, so no two lanes write one element).
+// A row with mask == 0 reads neither its ids nor its values.
+#define KD_TOPK 32
+struct KdEntry {
+    int id;          // in [0, V1) when live
+    float z;         // val * it; -inf when not live
+    bool live;
+};
+// lane k < K of wave 0 takes entry k of the row; every other lane, and every lane of a row with mask == 0, gets a dead entry
+__device__ __forceinline__ KdEntry kd_topk_entry(const int* __restrict__ ids, const float* __restrict__ val, int K, int V1,
+                                                 float it, bool row_live) {
+    KdEntry e{0, -INFINITY, false};
+    if (row_live && (int)threadIdx.x < K) {
+        const int id = ids[threadIdx.x];
+        const float v = val[threadIdx.x];
+        if (id >= 0 && id < V1 && v != -INFINITY) {
+            e.id = id;
+            e.z = v * it;
+            e.live = true;
+        }
+    }
+    return e;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void kd_topk_fwd_k(const float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                     const int64_t* __restrict__ target, long ld_t,
+                                                     const float* __restrict__ mask, long ld_m, float eps,
+                                                     const int* __restrict__ t_ids, long i_sb, long i_st,
+                                                     const float* __restrict__ t_val, long v_sb, long v_st, int K, float it,
+                                                     float* __restrict__ row_stats, float* __restrict__ row_xe,
+                                                     float* __restrict__ row_kd) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, t = r / B, b = r - t * B;      // time-major rows
+    const float* x = logits + r * ldl;
+    f32x4 xr[LSM_R4];
+    const float lse = log_softmax_row<VEC>(x, V1, xr, red);
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    float term = x[tg] - lse;                                // the xe term: xe_logits_fwd_k's expression, for its bits
+    if (eps > 0.f) {
+        float s = 0.f;
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) s += ((xr[j][0] - lse) + (xr[j][1] - lse)) + ((xr[j][2] - lse) + (xr[j][3] - lse));
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) s += x[v] - lse;
+        }
+        s = block_sum_256(s, red);
+        term = (1.0f - eps) * term + (eps / (float)V1) * s;
+    }
+    float lse_s = lse;
+    if (it != 1.0f) {                                        // `it` is uniform over the grid; it > 0: max(x * it) = max(x) * it
+        float mx = -INFINITY, ss = 0.f;
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) mx = fmaxf(mx, fmaxf(fmaxf(xr[j][0], xr[j][1]), fmaxf(xr[j][2], xr[j][3])));
+            mx = block_max_256(mx, red) * it;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ss += expf(xr[j][e] * it - mx);
+                }
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) mx = fmaxf(mx, x[v]);
+            mx = block_max_256(mx, red) * it;
+            for (int v = threadIdx.x; v < V1; v += 256) ss += expf(x[v] * it - mx);
+        }
+        lse_s = mx + logf(block_sum_256(ss, red));
+    }
+    if (threadIdx.x < 64) {                                  // wave 0: the K entries, one per lane
+        const bool row_live = mk != 0.f;
+        const KdEntry e = kd_topk_entry(t_ids + b * i_sb + t * i_st, t_val + b * v_sb + t * v_st, K, V1, it, row_live);
+        const float mz = rfn_wave_max(e.z);
+        const float lse_t = mz + logf(rfn_wave_sum(e.live ? expf(e.z - mz) : 0.f));
+        float kl = 0.f;
+        if (e.live) {
+            const float lpt = e.z - lse_t;
+            const float pt = expf(lpt);
+            if (pt > 0.f) kl = pt * (lpt - (x[e.id] * it - lse_s));
+        }
+        kl = rfn_wave_sum(kl);
+        if (threadIdx.x == 0) {
+            const long n = (long)T * B;
+            row_stats[r] = lse;
+            row_stats[n + r] = lse_s;
+            row_stats[2 * n + r] = row_live ? lse_t : 0.f;
+            row_xe[b * T + t] = -mk * term;
+            row_kd[b * T + t] = row_live ? mk * kl / (it * it) : 0.f;
+        }
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void kd_topk_bwd_k(float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                     const int64_t* __restrict__ target, long ld_t,
+                                                     const float* __restrict__ mask, long ld_m, float eps,
+                                                     const int* __restrict__ t_ids, long i_sb, long i_st,
+                                                     const float* __restrict__ t_val, long v_sb, long v_st, int K, float alpha,
+                                                     float it, float gcoef, const float* __restrict__ gdev,
+                                                     const float* __restrict__ row_stats) {
+    const int r = blockIdx.x, t = r / B, b = r - t * B;
+    float* x = logits + r * ldl;
+    long tg = target[b * ld_t + t];
+    if (tg < 0 || tg >= V1) tg = 0;
+    const float mk = mask[b * ld_m + t];
+    if (mk == 0.f) {                                         // exact zeros; the teacher's entries are not read (block-uniform)
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+            for (int i = threadIdx.x; i < n4; i += 256) *reinterpret_cast<f32x4*>(x + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) x[v] = 0.f;
+        }
+        return;
+    }
+    const float c = mk * (gdev ? gcoef * gdev[0] : gcoef);   // mask * d loss / B
+    const long n = (long)T * B;
+    const float lse = row_stats[r], lse_s = row_stats[n + r], lse_t = row_stats[2 * n + r];
+    const float uni = eps / (float)V1, hot = 1.0f - eps, wx = 1.0f - alpha, wk = alpha / it;
+    auto grad = [&](float xv, float pt, bool is_tg) {        // kd_logits_bwd_k's expression
+        const float p = expf(xv - lse);
+        const float ps = (it != 1.0f) ? expf(xv * it - lse_s) : p;
+        return c * (wx * ((p - uni) - (is_tg ? hot : 0.f)) + wk * (ps - pt));
+    };
+    // (1) the original x[id_k], before any lane of the block writes: the loads have returned when the barrier is passed
+    const KdEntry e = kd_topk_entry(t_ids + b * i_sb + t * i_st, t_val + b * v_sb + t * v_st, K, V1, it, true);
+    float xk = 0.f;
+    if (e.live) xk = x[e.id];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // (2) the row without the teacher's term
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * i);
+            f32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = grad(xv[q], 0.f, 4 * i + q == tg);
+            *reinterpret_cast<f32x4*>(x + 4 * i) = o;
+        }
+    } else {
+        for (int v = threadIdx.x; v < V1; v += 256) x[v] = grad(x[v], 0.f, v == tg);
+    }
+    // (3) the K entries again, in full, behind every lane's stores of (2)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (e.live) x[e.id] = grad(xk, expf(e.z - lse_t), e.id == tg);
+}
+static int kd_topk_check(const void* logits, int64_t ldl, int B, int T, int V1, const void* target, const void* mask, float eps,
+                         const void* t_ids, int64_t i_sb, int64_t i_st, const void* t_val, int64_t v_sb, int64_t v_st, int K,
+                         float alpha, float inv_temp) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || ldl < V1 || eps < 0.f || eps >= 1.f) return RFN_ERR_SHAPE;
+    if (!(alpha >= 0.f && alpha <= 1.f) || !(inv_temp > 0.f) || !(inv_temp <= 3.402823466e38f)) return RFN_ERR_SHAPE;
+    if (K < 1 || K > KD_TOPK) return RFN_ERR_SHAPE;
+    for (const int64_t s : {i_sb, i_st, v_sb, v_st})
+        if ((s < 0 ? -s : s) < K) return RFN_ERR_SHAPE;
+    if (!logits || !target || !mask || !t_ids || !t_val) return RFN_ERR_ARG;
+    return RFN_OK;
+}
+extern "C" int rfn_kd_topk_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                               const float* mask, int64_t ld_mask, float eps, const int32_t* t_ids, int64_t i_sb, int64_t i_st,
+                               const float* t_val, int64_t v_sb, int64_t v_st, int K, float alpha, float inv_temp,
+                               float* row_stats, float* scratch, float* loss_out, int accumulate_loss, float* terms_out,
+                               void* stream) {
+    const int rc = kd_topk_check(logits, ldl, B, T, V1, target, mask, eps, t_ids, i_sb, i_st, t_val, v_sb, v_st, K, alpha, inv_temp);
+    if (rc != RFN_OK) return rc;
+    if (!row_stats || !scratch || !loss_out) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    float* row_kd = scratch + (size_t)B * T;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(kd_topk_fwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, t_ids, (long)i_sb, (long)i_st, t_val, (long)v_sb, (long)v_st,
+                           K, inv_temp, row_stats, scratch, row_kd);
+    else
+        hipLaunchKernelGGL(kd_topk_fwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, t_ids, (long)i_sb, (long)i_st, t_val, (long)v_sb, (long)v_st,
+                           K, inv_temp, row_stats, scratch, row_kd);
+    RFN_CHECK_LAUNCH();
+    // the two sums and the mix as in rfn_kd_logits_fwd
+    float* xe = terms_out ? terms_out : scratch;
+    float* kd = terms_out ? terms_out + 1 : row_kd;
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, xe, 0);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, row_kd, B * T, 1.0f / (float)B, kd, 0);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kd_mix_k, dim3(1), dim3(64), 0, st, xe, kd, alpha, loss_out, accumulate_loss);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+extern "C" int rfn_kd_topk_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* target, int64_t ld_target,
+                               const float* mask, int64_t ld_mask, float eps, const int32_t* t_ids, int64_t i_sb, int64_t i_st,
+                               const float* t_val, int64_t v_sb, int64_t v_st, int K, float alpha, float inv_temp,
+                               const float* row_stats, float gscale, const float* gscale_dev, void* stream) {
+    const int rc = kd_topk_check(logits, ldl, B, T, V1, target, mask, eps, t_ids, i_sb, i_st, t_val, v_sb, v_st, K, alpha, inv_temp);
+    if (rc != RFN_OK) return rc;
+    if (!row_stats) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(kd_topk_bwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, t_ids, (long)i_sb, (long)i_st, t_val, (long)v_sb, (long)v_st,
+                           K, alpha, inv_temp, gscale / (float)B, gscale_dev, row_stats);
+    else
+        hipLaunchKernelGGL(kd_topk_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, target,
+                           (long)ld_target, mask, (long)ld_mask, eps, t_ids, (long)i_sb, (long)i_st, t_val, (long)v_sb, (long)v_st,
+                           K, alpha, inv_temp, gscale / (float)B, gscale_dev, row_stats);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

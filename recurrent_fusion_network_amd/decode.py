@@ -661,6 +661,30 @@ def _consensus_beams(cs, cands, lps, p, n_cand, m):
     return seq, seq_lp
 
 
+def labels_from_seq(seq, seq_length=None):
+    """Decoded ids -> the (labels, masks) a loader hands forward_loss, for sequence-level distillation: decode with the teacher
+    (sample_beam, EnsembleDecoder.sample_beam, the rows of sample_distinct's candidates), turn the ids into labels here, train
+    the student on them with the usual forward_loss.  seq (B, S') integer ids, 0 = END / padding; S = seq_length (default S',
+    not below it).
+      labels (B, S + 2) int64: column 0 is 0 (BOS), then the caption with everything from its first 0 onward zeroed;
+      masks  (B, S + 2) float32: ones over the first n + 2 columns, n = the tokens before the first 0 (BOS, the n words, END)
+    -- what the reference's loader writes for a ground-truth caption (dataloader.py:285, :312-315).  Tensor ops on seq's device
+    only: no host synchronisation."""
+    if not torch.is_tensor(seq) or seq.dim() != 2 or seq.is_floating_point() or seq.is_complex() or seq.dtype == torch.bool:
+        raise ValueError('seq must be a (B, S) tensor of integer token ids')
+    B, Sp = seq.shape
+    S = Sp if seq_length is None else int(seq_length)
+    if S < Sp:
+        raise ValueError('seq_length = %d is below the %d columns of seq' % (S, Sp))
+    s = seq.long()
+    alive = (s != 0).long().cumprod(1)                       # 1 up to the first 0, 0 from there on
+    labels = s.new_zeros(B, S + 2)
+    labels[:, 1:Sp + 1] = s * alive
+    n = alive.sum(1, keepdim=True)
+    masks = (torch.arange(S + 2, device=seq.device).unsqueeze(0) < n + 2).float()
+    return labels, masks
+
+
 def keep_candidates_n(opt, beam_size):
     """opt['keep_candidates']: None without the key, else how many ranked done beams a plain search keeps (consensus_n or
     beam_size; a diverse search keeps its G group bests)."""

@@ -149,6 +149,40 @@ class EnsembleDecoder:
         return out.transpose(0, 1)
 
     @torch.no_grad()
+    def teacher_topk(self, fc_feats, att_feats, seq, k):
+        """`teacher_logits` as a compact teacher: -> distill.TopKTeacher (B, S, k), the k <= min(32, V+1) best entries of every
+        row of the members' mean logits, as log-probs in rfn_log_softmax_topk's order.  Each step's mean goes through that
+        kernel into slice t of one (S, B, k) pair of buffers, so only ONE (B, V+1) block of logits ever exists -- never
+        (S, B, V+1) -- and what is returned can be kept for the whole training set.  Bit for bit
+        TopKTeacher.from_dense(self.teacher_logits(...), k)."""
+        from .distill import MAX_K, TopKTeacher
+        m0 = self.models[0]
+        B = m0._check_inputs(fc_feats, att_feats)
+        if seq.dim() != 2 or seq.size(0) != B:
+            raise N.RfnError('seq has shape %s, the features hold %d rows' % (tuple(seq.shape), B))
+        V1 = m0.vocab_size + 1
+        k = int(k)
+        if not 1 <= k <= min(MAX_K, V1):
+            raise ValueError('k = %d: 1 <= k <= min(%d, V+1 = %d)' % (k, MAX_K, V1))
+        S = m0._decoder_steps(seq)
+        steppers = []
+        for m in self.models:
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
+        dev = steppers[0].h.device
+        st = N.stream_ptr()
+        feed = seq[:, :S].to(dev).long().t().contiguous()      # row t = the tokens fed at step t
+        ids = torch.empty(S, B, k, dtype=torch.int32, device=dev)
+        logp = torch.empty(S, B, k, device=dev)
+        logit_sum = torch.empty(B, V1, device=dev)
+        logit_m = torch.empty(B, V1, device=dev) if len(steppers) > 1 else None
+        for t in range(S):
+            self._averaged_step(steppers, feed[t], logit_sum, logit_m)
+            N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, B, V1, k, logp[t].data_ptr(), ids[t].data_ptr(), st),
+                    'rfn_log_softmax_topk')
+        return TopKTeacher(ids.transpose(0, 1), logp.transpose(0, 1))
+
+    @torch.no_grad()
     def sample_beam(self, fc_feats, att_feats, opt={}):
         """Beam search on the members' averaged distribution -> (seq (B, S), seqLogprobs (B, S), top_seq, top_prob) with
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from .distill import TopKTeacher
 from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Lexical,
                      _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit, keep_candidates_n, run_beam_loop,
                      run_greedy_loop, run_stochastic_loop, _Stochastic, StochasticBuffers)
@@ -283,7 +284,8 @@ class _DecoderLossFn(torch.autograd.Function):
     `kd` = None, or (teacher (B, >= S, V+1) f32 with unit stride in the last dimension, alpha, inv_temp) for distillation:
     rfn_kd_logits_fwd / _bwd take the place of the XE pair (rfn.h: loss = (1 - alpha) * xe + alpha * kd), the node keeps the
     rows' three logsumexps, and `terms` (2 floats, {xe, kd}) is filled for logging.  The teacher is a constant: it is held
-    by the node as it is, outside autograd's saved tensors."""
+    by the node as it is, outside autograd's saved tensors.  A distill.TopKTeacher in the teacher's place (K <= 32 (id, value)
+    pairs per row) goes to rfn_kd_topk_fwd / _bwd, with the same statistics and terms."""
 
     @staticmethod
     def _criterion_fwd(d, B, S, logits, target, mask, eps, kd, stats, scratch, loss, terms, st):
@@ -293,6 +295,11 @@ class _DecoderLossFn(torch.autograd.Function):
                     'rfn_xe_logits_fwd')
         else:
             z, alpha, it = kd
+            if isinstance(z, TopKTeacher):
+                N.check(N.lib.rfn_kd_topk_fwd(logits, d.V1, B, S, d.V1, target.data_ptr(), target.stride(0), mask.data_ptr(),
+                                              mask.stride(0), float(eps), *z._abi(), alpha, it, stats.data_ptr(), scratch.data_ptr(),
+                                              loss.data_ptr(), 0, N.ptr(terms), st), 'rfn_kd_topk_fwd')
+                return
             N.check(N.lib.rfn_kd_logits_fwd(logits, d.V1, B, S, d.V1, target.data_ptr(), target.stride(0), mask.data_ptr(),
                                             mask.stride(0), float(eps), z.data_ptr(), z.stride(0), z.stride(1), alpha, it,
                                             stats.data_ptr(), scratch.data_ptr(), loss.data_ptr(), 0, N.ptr(terms), st),
@@ -351,9 +358,14 @@ class _DecoderLossFn(torch.autograd.Function):
                     'rfn_xe_logits_bwd')
         else:
             z, alpha, it = kd
-            N.check(N.lib.rfn_kd_logits_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
-                                            ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, z.data_ptr(), z.stride(0), z.stride(1),
-                                            alpha, it, lse.data_ptr(), 1.0, g.data_ptr(), st), 'rfn_kd_logits_bwd')
+            if isinstance(z, TopKTeacher):
+                N.check(N.lib.rfn_kd_topk_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
+                                              ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, *z._abi(), alpha, it, lse.data_ptr(),
+                                              1.0, g.data_ptr(), st), 'rfn_kd_topk_bwd')
+            else:
+                N.check(N.lib.rfn_kd_logits_bwd(logits, d.V1, B, S, d.V1, ctx.target.data_ptr(), ctx.target.stride(0),
+                                                ctx.mask.data_ptr(), ctx.mask.stride(0), ctx.eps, z.data_ptr(), z.stride(0), z.stride(1),
+                                                alpha, it, lse.data_ptr(), 1.0, g.data_ptr(), st), 'rfn_kd_logits_bwd')
         d_comb, d_h0, d_c0 = torch.empty_like(comb), torch.empty_like(h0), torch.empty_like(c0)
         N.check(N.lib.rfn_decoder_bwd(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
                                       ctx.ids.data_ptr(), ctx.ids.stride(0), None, None, d_comb.data_ptr(), d_h0.data_ptr(),
@@ -687,8 +699,17 @@ class RecurrentFusionModel(nn.Module):
     def _check_teacher(self, teacher, B, S, dev):
         """The distillation teacher of forward_loss: a CUDA f32 tensor indexed (B, T_t >= S, V+1), unit stride in the last
         dimension, any strides in the first two (forward's batch-major log-probs, EnsembleDecoder.teacher_logits' view of a
-        time-major buffer).  Runs before any native call."""
+        time-major buffer) -- or a distill.TopKTeacher (B, T_t >= S, K) on that device (its own constructor has checked dtype,
+        K and strides).  Runs before any native call."""
         V1 = self.vocab_size + 1
+        if isinstance(teacher, TopKTeacher):
+            if teacher.size(0) != B or teacher.size(1) < S:
+                raise N.RfnError('teacher has shape %s, this pass needs (%d, >= %d, K)' % (tuple(teacher.shape), B, S))
+            if not teacher.ids.is_cuda:
+                raise N.RfnError('teacher must live on the GPU: the HIP path has no CPU fallback')
+            if teacher.device != dev:
+                raise N.RfnError('teacher lives on %s, the features on %s' % (teacher.device, dev))
+            return teacher
         if not torch.is_tensor(teacher):
             raise N.RfnError('teacher must be a tensor (B, T, V+1) of logits or log-probs, got %s' % type(teacher).__name__)
         if teacher.dim() != 3 or teacher.size(0) != B or teacher.size(1) < S or teacher.size(2) != V1:
@@ -721,7 +742,12 @@ class RecurrentFusionModel(nn.Module):
         kd_temperature times its square, still one pass over the logits rows in each direction (one more read of the teacher
         row).  The teacher is a constant.  `self.last_distill` = {'xe', 'kd'}: the two terms as 0-dim device tensors (no
         read-back).  kd_alpha == 0 is the call without a teacher, bit for bit ('kd' is then None).  Scheduled sampling does not
-        combine with a teacher: its rows are conditioned on the ground-truth prefix."""
+        combine with a teacher: its rows are conditioned on the ground-truth prefix.
+
+        A compact teacher (rfn.h rfn_kd_topk_fwd): `teacher` may be a distill.TopKTeacher -- the K <= 32 best (id, log-prob)
+        pairs of every row, 8 * K bytes instead of 4 * (V+1), from TopKTeacher.from_dense, EnsembleDecoder.teacher_topk or a
+        cache on disk.  Same arguments, same `last_distill`, same refusals; the meaning is the dense teacher's with -inf off
+        the K ids (the K entries are renormalised; the tail mass is dropped)."""
         from .criteria import _MLMFn
         if teacher is not None:
             if self.ss_prob > 0:
