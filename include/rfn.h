@@ -343,7 +343,18 @@ int rfn_copy_small_f32(float* const* dst_host, const float* const* src_host, int
  *
  * Aliasing: dproj may be proj itself (same pointer and strides: in place) in every
  * backward entry; scores_scratch must not be alpha (RFN_ERR_ARG).  No other output may overlap an input or another
- * output; inputs may overlap each other freely.  (tests/test_attention_edges_gpu.py pins all of the above.) */
+ * output; inputs may overlap each other freely.  (tests/test_attention_edges_gpu.py pins all of the above.)
+ *
+ * Ragged maps (rfn_attn_fwd_ragged / rfn_attn_bwd_ragged; tests/test_ragged_attention_gpu.py): `len` is a HOST array of
+ * ngroups DEVICE pointers, len[g] a (B,) int32 vector or NULL; the array itself may be NULL.  Image b of encoder g has
+ * n = clamp(len[g][b], 1, L_g) valid rows (NULL: n = L_g); the clamp happens on the device, nothing is read back.  Same
+ * limits (LDS is sized by L_g, not by n), alignment rules, aliasing rules and error contract as above; `len` is never a
+ * required pointer.  Forward: raw scores, softmax and context run over l < n in the order of the full-length kernels,
+ * alpha[b, l] = 0 exactly for l >= n, and rows l >= n of proj and att_seq are never loaded (the raw-score scratch past n is
+ * not written).  Backward: dalpha, the softmax / tanh backward, dhproj and dw_part cover l < n; dproj[b, l, :] is written as
+ * exact zeros for l >= n when accumulate_dproj == 0 (so a consumer may read all B * L rows) and left alone otherwise.  The
+ * row count is uniform within a block: a shorter trip count, no mask multiply.  With every n == L_g the results are the
+ * _het calls', bit for bit; those calls forward here with len = NULL. */
 int rfn_attn_scores_fwd(const float* proj, int64_t proj_sb, int64_t proj_sl, const float* hproj,
                         const float* w_out, const float* b_out, int B, int L, int A, float* alpha,
                         void* stream);
@@ -397,6 +408,14 @@ int rfn_attn_bwd_het(int ngroups, const float* const* proj, const float* const* 
                      const float* const* alpha, const float* const* att_seq, const float* const* dz, int B,
                      const int* L_host, int A, const int* D_host, float* const* dproj, int accumulate_dproj,
                      float* const* dhproj, float* const* dw_part, void* stream);
+int rfn_attn_fwd_ragged(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                        const float* const* b_out, const float* const* att_seq, int B, const int* L_host, int A,
+                        const int* D_host, float* const* scores_scratch, float* const* alpha, float* const* z,
+                        const int32_t* const* len, void* stream);
+int rfn_attn_bwd_ragged(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                        const float* const* alpha, const float* const* att_seq, const float* const* dz, int B,
+                        const int* L_host, int A, const int* D_host, float* const* dproj, int accumulate_dproj,
+                        float* const* dhproj, float* const* dw_part, const int32_t* const* len, void* stream);
 /* The same for `ngroups` encoders that share (L, A, D) and every stride, one launch (grid = B x ngroups). */
 int rfn_attn_bwd_grouped(int ngroups, const float* const* proj, int64_t proj_sb, int64_t proj_sl,
                          const float* const* hproj, const float* const* w_out, const float* const* alpha,
@@ -1151,6 +1170,30 @@ int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* params,
  * part 2: att_2_att_h.bias and h_2_att_h.bias have the same gradient, which part 1 computes once and writes to both. */
 int rfn_prefix_bwd_wgrad(const rfn_dims* d, int B, const float* const* att_feats, float* const* grads,
                          void* ws, size_t ws_bytes, int enc, int parts, void* stream);
+/* Ragged attention maps through stage I: the three entries above plus `att_len`, a HOST array of M DEVICE pointers
+ * (att_len[i]: (B,) int32 valid rows of encoder i's map per image, or NULL = all L_i; the array may be NULL).  The lengths
+ * reach the stage-I attention launches only (rfn_attn_fwd_ragged / rfn_attn_bwd_ragged: clamped to [1, L_i] on the device);
+ * the projection GEMMs still run over all B * L_i rows, so padded rows of att_feats must be FINITE; stage II and the decoder
+ * attend over thought vectors and do not change.  The backward call must get the lengths of its forward call.  The padded
+ * rows of dP1 are exact zeros, so rfn_prefix_bwd_wgrad needs no lengths.  Without lengths these are the entries above, bit
+ * for bit (they forward here).  With lengths, RFN_ERR_UNSUPPORTED -- before anything is launched -- for forms that were not
+ * taught them: RFN_PATH_OPT_PERSIST_S2_FWD / _S2_BWD, and RFN_GEMM_OPT_BF16X3 where it makes a length-carrying encoder's
+ * attention backward write dP1 as bf16 planes (rfn_attn_bwd_grouped_ks).  The two-kernel backward (rfn_attn_context_bwd_dalpha
+ * + rfn_attn_scores_bwd, what small batches with large maps take) has no ragged form either: with lengths those encoders
+ * run the one-launch rfn_attn_bwd_ragged instead (same results to the bit as the pair, rfn_attn_bwd). */
+int rfn_prefix_fwd_ex(const rfn_dims* d, int B, const float* const* params,
+                      const float* const* fc_feats, const float* const* att_feats, float* comb,
+                      float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
+                      int train, uint64_t seed, const int32_t* const* att_len, void* stream);
+int rfn_prefix_fwd_from_state_ex(const rfn_dims* d, int B, const float* const* params,
+                                 const float* const* init_h, const float* const* init_c,
+                                 const float* const* att_feats, float* comb, float* h_out, float* c_out,
+                                 float* reason_pred, void* ws, size_t ws_bytes, const int32_t* const* att_len, void* stream);
+int rfn_prefix_bwd_ex(const rfn_dims* d, int B, const float* const* params,
+                      const float* const* fc_feats, const float* const* att_feats,
+                      const float* d_comb, const float* d_h, const float* d_c,
+                      const float* d_reason_pred, float* const* grads, void* ws, size_t ws_bytes,
+                      uint64_t seed, int defer_wgrad, const int32_t* const* att_len, void* stream);
 
 /* Phase 2 = the teacher-forced decoder loop of forward() (misc/RecurrentFusionModel.py:257-281):
  * for s < S: xt = embed(ids[b,s]); decoder cell (misc/LSTMSoftAttentionCore.py:60-102);

@@ -6,6 +6,7 @@ without the built library raises, and every call that returns a non-zero status 
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 
 import torch
@@ -157,6 +158,9 @@ def _load():
         'rfn_attn_bwd_grouped': (C.c_int, [I, P, L, L, P, P, P, P, L, L, P, L, I, I, I, I, P, L, L, I, P, P, P]),
         'rfn_attn_fwd_het': (C.c_int, [I, P, P, P, P, P, I, P, I, P, P, P, P, P]),
         'rfn_attn_bwd_het': (C.c_int, [I, P, P, P, P, P, P, I, P, I, P, P, I, P, P, P]),
+        # the _het signatures + `len` (host array of device (B,) int32 pointers, NULL entries = all rows) before the stream
+        'rfn_attn_fwd_ragged': (C.c_int, [I, P, P, P, P, P, I, P, I, P, P, P, P, P, P]),
+        'rfn_attn_bwd_ragged': (C.c_int, [I, P, P, P, P, P, P, I, P, I, P, P, I, P, P, P, P]),
         'rfn_attn_small_fwd': (C.c_int, [I, P, L, L, P, P, P, P, L, L, I, I, I, I, P, P, L, P]),
         'rfn_attn_small_bwd': (C.c_int, [I, P, L, L, P, P, P, P, L, L, P, L, I, I, I, I, P, L, L, I, P, P, P, P]),
         'rfn_dropout_mask': (C.c_int, [U64, U64, L, F, P, P]),
@@ -211,6 +215,10 @@ def _load():
         'rfn_prefix_fwd_from_state': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, P]),
         'rfn_prefix_bwd': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, U64, I, P]),
         'rfn_prefix_bwd_wgrad': (C.c_int, [DP, I, P, P, P, SZ, I, I, P]),
+        # ragged attention maps: the entries above + att_len (host array of M device (B,) int32 pointers, or NULL) before the stream
+        'rfn_prefix_fwd_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, SZ, I, U64, P, P]),
+        'rfn_prefix_fwd_from_state_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, P, P]),
+        'rfn_prefix_bwd_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, U64, I, P, P]),
         'rfn_decoder_ws_bytes': (SZ, [DP, I, I, I]),
         'rfn_decoder_fwd': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, SZ, I, U64, P]),
         'rfn_decoder_fwd_begin': (C.c_int, [DP, I, I, P, P, P, P, P, SZ, I, P]),
@@ -313,6 +321,50 @@ def ptr_array(tensors):
     for i, t in enumerate(tensors):
         arr[i] = None if t is None else t.data_ptr()
     return arr
+
+
+def att_lens_arg(att_lens, att_num, B, device):
+    """`att_lens` of the model's entry points -> None, or a list of M entries, each None (a full map) or a (B,) int32 tensor on
+    `device`: the per-image count of valid rows of that encoder's attention map (rfn.h, rfn_prefix_fwd_ex).  Accepted: one
+    (B,) integer tensor or sequence for all encoders, or a list of M such values with None for an encoder whose maps are full.
+    Host values are checked for 1 <= len <= L_i here (ValueError naming encoder and image); a device tensor is converted to
+    int32 and passed without a read-back -- the kernels clamp it to [1, L_i]."""
+    if att_lens is None:
+        return None
+    M = len(att_num)
+
+    def is_one(v):     # one vector of B counts (as opposed to a list with an entry per encoder)
+        if torch.is_tensor(v):
+            return v.dim() == 1
+        return len(v) > 0 and all(isinstance(e, numbers.Integral) for e in v)
+
+    if torch.is_tensor(att_lens) and att_lens.dim() != 1:
+        raise ValueError('att_lens must be a (B,) vector or a list of %d such vectors, got shape %s' % (M, tuple(att_lens.shape)))
+    if is_one(att_lens):
+        per_enc = [att_lens] * M
+    else:
+        per_enc = list(att_lens)
+        if len(per_enc) != M:
+            raise ValueError('att_lens has %d entries, the model has %d encoders' % (len(per_enc), M))
+    out = []
+    for i, v in enumerate(per_enc):
+        if v is None:
+            out.append(None)
+            continue
+        if not torch.is_tensor(v):
+            v = torch.as_tensor(list(v))
+        if v.dim() != 1 or v.dtype.is_floating_point or v.dtype == torch.bool or v.is_complex():
+            raise ValueError('att_lens[%d] must be a (B,) integer vector, got shape %s dtype %s' % (i, tuple(v.shape), v.dtype))
+        if v.numel() != B:
+            raise ValueError('att_lens[%d] has %d entries, the batch has %d images' % (i, v.numel(), B))
+        if not v.is_cuda:
+            bad = ((v < 1) | (v > att_num[i])).nonzero()
+            if bad.numel():
+                b = int(bad[0])
+                raise ValueError('att_lens[%d][%d] = %d is outside 1 <= len <= %d (encoder %d, image %d)'
+                                 % (i, b, int(v[b]), att_num[i], i, b))
+        out.append(v.to(device=device, dtype=torch.int32).contiguous())
+    return None if all(v is None for v in out) else out
 
 
 def make_dims(M, R, A, E, T1, T2, K, V1, L, D, Fc, review_maxout=0, decoder_maxout=0, drop_fusion=0.0,

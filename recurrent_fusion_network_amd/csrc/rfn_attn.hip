@@ -36,7 +36,21 @@ struct AttnEncPtrs {
     float* dhproj[RFN_MAX_ENC];
     float* dw_part[RFN_MAX_ENC];
     char* ks_img[RFN_MAX_ENC];   // attn_scores_bwd_k<.., EMIT>: k-slow bf16 plane image that receives dproj (rfn.h, rfn_x3_split_ks)
+    const int32_t* len[RFN_MAX_ENC];   // ragged maps: (B,) valid rows per image, or NULL = all L rows (rfn.h, rfn_attn_fwd_ragged)
 };
+// Valid rows of image b: clamp(len[b], 1, L).  A block belongs to one batch row, so this is a scalar (block-uniform) trip
+// count: a ragged map is a shorter loop, never a per-lane mask.  RAGGED = false (no encoder of the launch has lengths) is the
+// instantiation without any of it: n is L itself, so launches without lengths run the code they always ran.
+template <bool RAGGED>
+__device__ __forceinline__ int attn_row_len(const int32_t* __restrict__ len, int b, int L) {
+    if constexpr (!RAGGED) return L;
+    else return len ? min(max((int)len[b], 1), L) : L;
+}
+static bool attn_any_len(int ng, const AttnEncPtrs& E) {
+    bool any = false;
+    for (int g = 0; g < ng && g < RFN_MAX_ENC; ++g) any = any || E.len[g];
+    return any;
+}
 // Per-encoder extents and strides of one grouped launch.  Encoders of one launch share A (att_hid_size) only: their maps
 // may differ in L and D (the reference ships 196 x 2048, 64 x 1536, 64 x 1280 and 49 x 2208 maps together,
 // feat_array.py:240-244); the grid is sized for the largest and the blocks past an encoder's own extent leave at once.
@@ -75,10 +89,12 @@ static int attn_dims_het(int ng, const int* L, const int* D, int A, AttnDims* ou
     return RFN_OK;
 }
 
-template <bool VEC>
+template <bool VEC, bool RAGGED = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_scores_raw_k(const AttnEncPtrs E, const AttnDims Dm, int A) {
     const int L = Dm.L[blockIdx.z];
     if ((int)blockIdx.x * SC_ROWS >= L) return;     // a shorter map of a heterogeneous launch
+    const int n = attn_row_len<RAGGED>(E.len[blockIdx.z], blockIdx.y, L);
+    if (RAGGED && (int)blockIdx.x * SC_ROWS >= n) return;     // a block wholly past this image's rows
     const long sb = Dm.psb[blockIdx.z], sl = Dm.psl[blockIdx.z];
     const float* __restrict__ proj = E.proj[blockIdx.z];
     const float* __restrict__ hproj = E.hproj[blockIdx.z];
@@ -99,7 +115,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_scores_raw_k(const AttnEncPt
     const int l0 = blockIdx.x * SC_ROWS;
     for (int r = wave; r < SC_ROWS; r += ATT_WAVES) {
         const int l = l0 + r;
-        if (l >= L) break;
+        if (l >= n) break;
         const float sc = row_tanh_dot<VEC, true>(proj + b * sb + l * sl, hp_s, w_s, A, lane) + bo;
         if (lane == 0) scores[(long)b * L + l] = sc;
     }
@@ -144,7 +160,7 @@ extern "C" int rfn_attn_scores_fwd(const float* proj, int64_t proj_sb, int64_t p
 // SOFTMAX: `alpha` holds RAW scores; every block of a batch row normalises them itself in LDS (L values: trivial,
 // same reduction order as attn_softmax_k so the weights are bit-identical) and the first block publishes them
 // to alpha_out -- the separate softmax launch of the split path disappears.
-template <bool VEC, bool SOFTMAX>
+template <bool VEC, bool SOFTMAX, bool RAGGED = false>
 __global__ __launch_bounds__(ATT_THREADS) void attn_context_fwd_k(const AttnEncPtrs E, const AttnDims Dm) {
     const int L = Dm.L[blockIdx.z], D = Dm.D[blockIdx.z];
     if ((int)blockIdx.x * ATT_THREADS * (VEC ? 4 : 1) >= D) return;     // a narrower map of a heterogeneous launch
@@ -155,28 +171,31 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_context_fwd_k(const AttnEncP
     float* __restrict__ alpha_out = E.alpha_out[blockIdx.z];
     extern __shared__ __attribute__((aligned(16))) float al_s[];
     const int b = blockIdx.y, tid = threadIdx.x;
-    for (int l = tid; l < L; l += ATT_THREADS) al_s[l] = alpha[(long)b * L + l];
+    const int n = attn_row_len<RAGGED>(E.len[blockIdx.z], b, L);   // the raw scores past n were never written
+    for (int l = tid; l < n; l += ATT_THREADS) al_s[l] = alpha[(long)b * L + l];
     if constexpr (SOFTMAX) {
         __shared__ float red[ATT_WAVES];
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         float m = -INFINITY;   // each thread re-reads exactly the entries it wrote: no barrier needed yet
-        for (int l = tid; l < L; l += ATT_THREADS) m = fmaxf(m, al_s[l]);
+        for (int l = tid; l < n; l += ATT_THREADS) m = fmaxf(m, al_s[l]);
         m = rfn_wave_max(m);
         if (lane == 0) red[wave] = m;
         __syncthreads();
         m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         __syncthreads();
         float sum = 0.f;
-        for (int l = tid; l < L; l += ATT_THREADS) sum += expf(al_s[l] - m);
+        for (int l = tid; l < n; l += ATT_THREADS) sum += expf(al_s[l] - m);
         sum = rfn_wave_sum(sum);
         if (lane == 0) red[wave] = sum;
         __syncthreads();
         const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-        for (int l = tid; l < L; l += ATT_THREADS) {
+        for (int l = tid; l < n; l += ATT_THREADS) {
             const float a = expf(al_s[l] - m) * inv;
             al_s[l] = a;
             if (blockIdx.x == 0) alpha_out[(long)b * L + l] = a;
         }
+        if (RAGGED && blockIdx.x == 0)   // the padded rows carry no weight: exact zeros
+            for (int l = n + tid; l < L; l += ATT_THREADS) alpha_out[(long)b * L + l] = 0.f;
     }
     __syncthreads();
     const float* xb = x + b * sb;
@@ -185,7 +204,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_context_fwd_k(const AttnEncP
         if (d >= D) return;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         int l = 0;
-        for (; l + 4 <= L; l += 4) {  // 4 independent 16-B loads in flight per lane
+        for (; l + 4 <= n; l += 4) {  // 4 independent 16-B loads in flight per lane
             const f32x4 x0 = att_ldx(xb + (l + 0) * sl + d);
             const f32x4 x1 = att_ldx(xb + (l + 1) * sl + d);
             const f32x4 x2 = att_ldx(xb + (l + 2) * sl + d);
@@ -195,13 +214,13 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_context_fwd_k(const AttnEncP
             acc += al_s[l + 2] * x2;
             acc += al_s[l + 3] * x3;
         }
-        for (; l < L; ++l) acc += al_s[l] * *reinterpret_cast<const f32x4*>(xb + l * sl + d);
+        for (; l < n; ++l) acc += al_s[l] * *reinterpret_cast<const f32x4*>(xb + l * sl + d);
         *reinterpret_cast<f32x4*>(z + b * ldz + d) = acc;
     } else {
         const int d = blockIdx.x * ATT_THREADS + tid;
         if (d >= D) return;
         float acc = 0.f;
-        for (int l = 0; l < L; ++l) acc += al_s[l] * xb[l * sl + d];
+        for (int l = 0; l < n; ++l) acc += al_s[l] * xb[l * sl + d];
         z[b * ldz + d] = acc;
     }
 }
@@ -225,8 +244,15 @@ template <bool SOFTMAX>
 static int launch_context_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm, int B, hipStream_t st) {
     bool vec = false;
     RFN_TRY(check_context_d<SOFTMAX>(ng, E, Dm, B, &vec));
-    if (vec)
+    const bool ragged = attn_any_len(ng, E);
+    if (vec && ragged)
+        hipLaunchKernelGGL((attn_context_fwd_k<true, SOFTMAX, true>), dim3(rfn_cdiv(Dm.maxD, 4 * ATT_THREADS), B, ng),
+                           dim3(ATT_THREADS), Dm.maxL * sizeof(float), st, E, Dm);
+    else if (vec)
         hipLaunchKernelGGL((attn_context_fwd_k<true, SOFTMAX>), dim3(rfn_cdiv(Dm.maxD, 4 * ATT_THREADS), B, ng),
+                           dim3(ATT_THREADS), Dm.maxL * sizeof(float), st, E, Dm);
+    else if (ragged)
+        hipLaunchKernelGGL((attn_context_fwd_k<false, SOFTMAX, true>), dim3(rfn_cdiv(Dm.maxD, ATT_THREADS), B, ng),
                            dim3(ATT_THREADS), Dm.maxL * sizeof(float), st, E, Dm);
     else
         hipLaunchKernelGGL((attn_context_fwd_k<false, SOFTMAX>), dim3(rfn_cdiv(Dm.maxD, ATT_THREADS), B, ng),
@@ -261,10 +287,15 @@ static int launch_scores_raw_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm,
         vec = vec && (Dm.psb[g] % 4 == 0) && (Dm.psl[g] % 4 == 0) && rfn_aligned16(E.proj[g]);
     }
     dim3 grid(rfn_cdiv(Dm.maxL, SC_ROWS), B, ng);
-    if (vec)
-        hipLaunchKernelGGL(attn_scores_raw_k<true>, grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
+    const bool ragged = attn_any_len(ng, E);
+    if (vec && ragged)
+        hipLaunchKernelGGL((attn_scores_raw_k<true, true>), grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
+    else if (vec)
+        hipLaunchKernelGGL((attn_scores_raw_k<true>), grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
+    else if (ragged)
+        hipLaunchKernelGGL((attn_scores_raw_k<false, true>), grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
     else
-        hipLaunchKernelGGL(attn_scores_raw_k<false>, grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
+        hipLaunchKernelGGL((attn_scores_raw_k<false>), grid, dim3(ATT_THREADS), lds, st, E, Dm, A);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
@@ -425,7 +456,7 @@ extern "C" int rfn_attn_context_bwd_dseq(const float* alpha, const float* dz, in
 // weight-gradient GEMM on the bf16 matrix cores reads (element (k = b * L + l, plane, column ks_col0 + a) at
 // ((k * 3 + plane) * ks_mp + ks_col0 + a) * 2 bytes): 8 bytes per lane and plane, whole rows coalesced -- the separate split
 // pass over dproj (a read of 4 and a write of 6 bytes per element) disappears.
-template <bool VEC, bool FUSED, bool EMIT = false>
+template <bool VEC, bool FUSED, bool EMIT = false, bool RAGGED = false>
 __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtrs E, const AttnDims Dm, int A, int accumulate,
                                                                int vec_x, int ks_mp, int ks_col0) {
     const int L = Dm.L[blockIdx.y], D = Dm.D[blockIdx.y];
@@ -454,6 +485,7 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
     // scalar base + this lane's column offset instead of a 64-bit per-lane pointer (fewer VGPRs: the plane-emitting
     // instantiation spilled three of its 128)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = attn_row_len<RAGGED>(E.len[blockIdx.y], b, L);   // every sweep below stops at this image's own rows
     for (int a = tid; a < A; a += SB_THREADS) {
         hp_s[a] = hproj[(long)b * A + a];
         w_s[a] = w_out[a];
@@ -465,8 +497,8 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
         float* dz_s = dal_s + Lp;                  // [D]
         for (int d = tid; d < D; d += SB_THREADS) dz_s[d] = dz[b * lddz + d];
         __syncthreads();
-        for (int l0 = wave * 4; l0 < L; l0 += SB_WAVES * 4) {   // 4 rows per wave walked together, as attn_dalpha_k
-            const int nr = min(4, L - l0);
+        for (int l0 = wave * 4; l0 < n; l0 += SB_WAVES * 4) {   // 4 rows per wave walked together, as attn_dalpha_k
+            const int nr = min(4, n - l0);
             const float* p0 = x + b * xsb + (long)l0 * xsl;
             float pt[4] = {0.f, 0.f, 0.f, 0.f};
             if (vec_x) {
@@ -495,14 +527,14 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
     }
     // softmax backward: ds = alpha * (dalpha - <alpha, dalpha>)
     float part = 0.f;
-    for (int l = tid; l < L; l += SB_THREADS) part += alpha[(long)b * L + l] * dal[l];
+    for (int l = tid; l < n; l += SB_THREADS) part += alpha[(long)b * L + l] * dal[l];
     part = rfn_wave_sum(part);
     if (lane == 0) dot_s[wave] = part;
     __syncthreads();
     float dot = 0.f;
 #pragma unroll
     for (int w2 = 0; w2 < SB_WAVES; ++w2) dot += dot_s[w2];
-    for (int l = tid; l < L; l += SB_THREADS)
+    for (int l = tid; l < n; l += SB_THREADS)
         ds_s[l] = alpha[(long)b * L + l] * (dal[l] - dot);
     __syncthreads();
 
@@ -521,12 +553,12 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
             // SB_UNROLL rows of this wave are in flight together: each lane issues its loads first, then does the
             // arithmetic and the stores (one row at a time left a single 1-KiB load in flight per wave and the sweep
             // latency-bound).  The per-column sums still add the rows in ascending order.
-            for (int l0 = wave; l0 < L; l0 += SB_WAVES * SB_UNROLL) {
+            for (int l0 = wave; l0 < n; l0 += SB_WAVES * SB_UNROLL) {
                 float xv[SB_UNROLL][W];
 #pragma unroll
                 for (int u = 0; u < SB_UNROLL; ++u) {
                     const int l = l0 + u * SB_WAVES;
-                    if (l < L) {
+                    if (l < n) {
                         const float* p = proj + b * sb + l * sl + a;
                         if constexpr (VEC) {
                             const f32x4 t = ATT_NT_P ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p))
@@ -540,7 +572,7 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
 #pragma unroll
                 for (int u = 0; u < SB_UNROLL; ++u) {
                     const int l = l0 + u * SB_WAVES;
-                    if (l < L) {
+                    if (l < n) {
                         const float dsl_v = ds_s[l];
                         float* o = dproj + b * dsb + l * dsl + a;
                         float ov[W];
@@ -580,6 +612,18 @@ __global__ __launch_bounds__(SB_THREADS) void attn_scores_bwd_k(const AttnEncPtr
                 red_w[wave * Ap + a + e] = aw[e];
             }
         }
+    }
+    // Ragged map: the padded rows of dproj become exact zeros (dproj aliases proj in the path and the weight-gradient GEMM
+    // reads all B * L rows); an accumulating call leaves them alone.  Nothing above read those rows of proj.
+    if constexpr (RAGGED && !EMIT) {
+        if (!accumulate)
+            for (int l = n + wave; l < L; l += SB_WAVES) {
+                float* o = dproj + b * dsb + l * dsl;
+                for (int a = lane * W; a < A; a += 64 * W) {
+                    if constexpr (VEC) *reinterpret_cast<f32x4*>(o + a) = f32x4{0.f, 0.f, 0.f, 0.f};
+                    else o[a] = 0.f;
+                }
+            }
     }
     __syncthreads();
     for (int a = tid; a < A; a += SB_THREADS) {
@@ -621,6 +665,10 @@ static int launch_scores_bwd_d(int ng, const AttnEncPtrs& E, const AttnDims& Dm,
             if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(k, dim3(B, ng), dim3(SB_THREADS), lds, st, E, Dm, A, 0, (int)vx, ks_mp, ks_col0);
         }
+    } else if (attn_any_len(ng, E)) {
+        auto k = vec ? attn_scores_bwd_k<true, FUSED, false, true> : attn_scores_bwd_k<false, FUSED, false, true>;
+        if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k, dim3(B, ng), dim3(SB_THREADS), lds, st, E, Dm, A, accumulate_dproj, (int)vx, 0, 0);
     } else if (vec) {
         auto k = attn_scores_bwd_k<true, FUSED>;
         if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -706,10 +754,13 @@ extern "C" int rfn_attn_bwd(const float* proj, int64_t proj_sb, int64_t proj_sl,
 // The two calls above for encoders whose maps differ in (L, D) (they share A): contiguous layouts -- proj / dproj
 // (B, L_g, A), att_seq (B, L_g, D_g), z / dz (B, D_g), alpha and the raw-score scratch (B, L_g).  Same kernels, same
 // per-row arithmetic as the per-encoder calls (bit-identical); the grid covers the largest map.
-extern "C" int rfn_attn_fwd_het(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
-                                const float* const* b_out, const float* const* att_seq, int B, const int* L, int A,
-                                const int* D, float* const* scores_scratch, float* const* alpha, float* const* z,
-                                void* stream) {
+// Ragged maps: len[g] (device, (B,) int32, or NULL = every row) is image b's valid row count in encoder g's map, clamped to
+// [1, L_g] by the kernels.  Rows past it are never loaded; their alpha is exactly 0 and, in a non-accumulating backward, so
+// is their dproj.  len == NULL or every entry NULL: the _het calls, bit for bit (they forward here).
+extern "C" int rfn_attn_fwd_ragged(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                                   const float* const* b_out, const float* const* att_seq, int B, const int* L, int A,
+                                   const int* D, float* const* scores_scratch, float* const* alpha, float* const* z,
+                                   const int32_t* const* len, void* stream) {
     if (ngroups < 1 || ngroups > RFN_MAX_ENC) return RFN_ERR_SHAPE;
     if (!proj || !hproj || !w_out || !att_seq || !scores_scratch || !alpha || !z) return RFN_ERR_ARG;
     AttnDims Dm;
@@ -727,16 +778,23 @@ extern "C" int rfn_attn_fwd_het(int ngroups, const float* const* proj, const flo
         E.alpha_in[g] = scores_scratch[g];
         E.alpha_out[g] = alpha[g];
         E.z[g] = z[g];
+        E.len[g] = len ? len[g] : nullptr;
     }
     bool vec_unused = false;
     RFN_TRY(check_context_d<true>(ngroups, E, Dm, B, &vec_unused));
     RFN_TRY(launch_scores_raw_d(ngroups, E, Dm, B, A, (hipStream_t)stream));
     return launch_context_d<true>(ngroups, E, Dm, B, (hipStream_t)stream);
 }
-extern "C" int rfn_attn_bwd_het(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
-                                const float* const* alpha, const float* const* att_seq, const float* const* dz, int B,
-                                const int* L, int A, const int* D, float* const* dproj, int accumulate_dproj,
-                                float* const* dhproj, float* const* dw_part, void* stream) {
+extern "C" int rfn_attn_fwd_het(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                                const float* const* b_out, const float* const* att_seq, int B, const int* L, int A,
+                                const int* D, float* const* scores_scratch, float* const* alpha, float* const* z,
+                                void* stream) {
+    return rfn_attn_fwd_ragged(ngroups, proj, hproj, w_out, b_out, att_seq, B, L, A, D, scores_scratch, alpha, z, nullptr, stream);
+}
+extern "C" int rfn_attn_bwd_ragged(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                                   const float* const* alpha, const float* const* att_seq, const float* const* dz, int B,
+                                   const int* L, int A, const int* D, float* const* dproj, int accumulate_dproj,
+                                   float* const* dhproj, float* const* dw_part, const int32_t* const* len, void* stream) {
     if (ngroups < 1 || ngroups > RFN_MAX_ENC) return RFN_ERR_SHAPE;
     if (!proj || !hproj || !w_out || !alpha || !att_seq || !dz || !dproj || !dhproj || !dw_part) return RFN_ERR_ARG;
     AttnDims Dm;
@@ -747,8 +805,16 @@ extern "C" int rfn_attn_bwd_het(int ngroups, const float* const* proj, const flo
         E.proj[g] = proj[g]; E.hproj[g] = hproj[g]; E.w_out[g] = w_out[g]; E.alpha_in[g] = alpha[g];
         E.x[g] = att_seq[g]; E.dz[g] = dz[g];
         E.dproj[g] = dproj[g]; E.dhproj[g] = dhproj[g]; E.dw_part[g] = dw_part[g];
+        E.len[g] = len ? len[g] : nullptr;
     }
     return launch_scores_bwd_d<true>(ngroups, E, Dm, B, A, accumulate_dproj, (hipStream_t)stream);
+}
+extern "C" int rfn_attn_bwd_het(int ngroups, const float* const* proj, const float* const* hproj, const float* const* w_out,
+                                const float* const* alpha, const float* const* att_seq, const float* const* dz, int B,
+                                const int* L, int A, const int* D, float* const* dproj, int accumulate_dproj,
+                                float* const* dhproj, float* const* dw_part, void* stream) {
+    return rfn_attn_bwd_ragged(ngroups, proj, hproj, w_out, alpha, att_seq, dz, B, L, A, D, dproj, accumulate_dproj, dhproj,
+                               dw_part, nullptr, stream);
 }
 
 // =====================================================================================================

@@ -19,6 +19,8 @@ struct S1Attn {
     const float *hp[RFN_MAX_ENC], *w[RFN_MAX_ENC], *b[RFN_MAX_ENC];
     void* img[RFN_MAX_ENC];         // k-slow plane image of encoder i's dP1 (the _KS forms)
     int L[RFN_MAX_ENC], D[RFN_MAX_ENC];
+    const int32_t* len[RFN_MAX_ENC];   // ragged maps: the caller's per-image row counts (NULL: all rows); `ragged`: any set
+    bool ragged;
     bool same_ld;                   // M > 1 encoders that share (L, D): the grouped forms
     size_t sc_floats;               // raw scores of the forward launch, laid out in the (idle) split-K scratch
 };
@@ -60,6 +62,7 @@ struct Prefix {
     float *Hs, *Cs, *h2, *c2, *rmat, *dHs, *dC, *dh2e, *dhrec, *dc2, *dz2, *dal, *dwp;
     int32_t* rarg;
     float* const* grd = nullptr;
+    const int32_t* const* att_len = nullptr;   // rfn_prefix_*_ex: per-encoder (B,) row counts of the stage-I maps, or NULL
     rfn_gemm_problem pr[64];
     rfn_gemm_seg segs[64];
 
@@ -158,7 +161,10 @@ void Prefix::s1_attn_of(int t, S1Attn* a) const {
     a->same_ld = M > 1;
     for (int i = 1; i < M; ++i) a->same_ld = a->same_ld && d->L[i] == d->L[0] && d->D[i] == d->D[0];
     a->sc_floats = 0;
+    a->ragged = false;
     for (int i = 0; i < M; ++i) {
+        a->len[i] = att_len ? att_len[i] : nullptr;
+        a->ragged = a->ragged || a->len[i];
         const long Li = d->L[i], Di = d->D[i], ti = (long)t * M + i;
         a->p[i] = W + Lo.P1[i] + (long)t * B * Li * A;
         a->hp[i] = W + Lo.hp1 + ti * BA;
@@ -203,7 +209,9 @@ int Prefix::s1_fwd_step(int t) {
     s1_attn_of(t, &a);
     if (a.sc_floats > GEMM_WS_FLOATS) return RFN_ERR_SHAPE;
     const long L0 = d->L[0], D0 = d->D[0];
-    if (a.same_ld)
+    if (a.ragged)   // per-image row counts: the contiguous-layout launch pair takes them for any mix of maps (one encoder included)
+        RFN_TRY(rfn_attn_fwd_ragged(M, a.p, a.hp, a.w, a.b, att, B, a.L, A, a.D, a.sc, a.al, a.z, a.len, st));
+    else if (a.same_ld)
         RFN_TRY(rfn_attn_fwd_grouped(M, a.p, L0 * A, (long)A, a.hp, a.w, a.b, att, L0 * D0, D0, B, (int)L0, A, (int)D0, a.sc, a.al,
                                      a.z, D0, st));
     else if (M > 1)   // maps of different (L, D): still one pair of launches
@@ -560,7 +568,9 @@ int Prefix::s1_bwd_step(int t, bool small) {
     s1_attn_of(t, &a);
     const long L0 = d->L[0], D0 = d->D[0];
     const AttnBwdForm form0 = attn_bwd_form(d, B, 0, dz_done);
-    if (form0 == AB_GROUPED_KS)   // all encoders' attention backward of this step: one launch; dP1 straight into the k-slow plane images
+    if (a.ragged && (form0 == AB_GROUPED || form0 == AB_HET))   // same launch as either form (contiguous layouts), with row counts
+        RFN_TRY(rfn_attn_bwd_ragged(M, a.p, a.hp, a.w, a.al, att, a.dz, B, a.L, A, a.D, a.p, 0, a.dhp, a.dw, a.len, st));
+    else if (form0 == AB_GROUPED_KS)   // all encoders' attention backward of this step: one launch; dP1 straight into the k-slow plane images
         RFN_TRY(rfn_attn_bwd_grouped_ks(M, a.p, L0 * A, (long)A, a.hp, a.w, a.al, att, L0 * D0, D0, a.dz, D0, B, (int)L0, A, (int)D0,
                                         a.img, x3_row_pad(T1 * A), t * A, a.dhp, a.dw, st));
     else if (form0 == AB_GROUPED)
@@ -573,7 +583,10 @@ int Prefix::s1_bwd_step(int t, bool small) {
             const long Li = a.L[i], Di = a.D[i];
             if (!dz_done) RFN_TRY(gemm1(B, (int)Di, kz[i].seg[0], a.dz[i], Di, 0, gx));
             const AttnBwdForm form = attn_bwd_form(d, B, i, dz_done);
-            if (form == AB_FUSED_KS) {   // d alpha stays in LDS, dP1 as bf16 planes
+            if (a.ragged && form != AB_FUSED_KS) {   // the one-launch form also where the two-kernel pair would run: it has no ragged form
+                RFN_TRY(rfn_attn_bwd_ragged(1, a.p + i, a.hp + i, a.w + i, a.al + i, att + i, a.dz + i, B, a.L + i, A, a.D + i, a.p + i,
+                                            0, a.dhp + i, a.dw + i, a.len + i, st));
+            } else if (form == AB_FUSED_KS) {   // d alpha stays in LDS, dP1 as bf16 planes
                 RFN_TRY(rfn_attn_bwd_grouped_ks(1, a.p + i, Li * A, (long)A, a.hp + i, a.w + i, a.al + i, att + i, Li * Di, Di, a.dz + i,
                                                 Di, B, (int)Li, A, (int)Di, a.img + i, x3_row_pad(T1 * A), t * A, a.dhp + i, a.dw + i, st));
             } else if (form == AB_FUSED) {   // d alpha stays in LDS, one launch
@@ -609,16 +622,30 @@ int Prefix::s1_bwd_tail(const float* const* fc) {
 }
 }  // namespace
 
+// Per-image row counts of the stage-I maps (rfn.h, rfn_prefix_fwd_ex): the forms that were not taught them are refused
+// here, before anything is launched -- never run with the lengths ignored.
+static int check_att_len(const rfn_dims* d, int B, const int32_t* const* att_len) {
+    bool any = false;
+    for (int i = 0; att_len && i < d->M; ++i) any = any || att_len[i];
+    if (!any) return RFN_OK;
+    if (d->path_flags & (RFN_PATH_OPT_PERSIST_S2_FWD | RFN_PATH_OPT_PERSIST_S2_BWD)) return RFN_ERR_UNSUPPORTED;
+    for (int i = 0; i < d->M; ++i)   // dP1 as bf16 planes from the attention backward (rfn_attn_bwd_grouped_ks)
+        if (att_len[i] && x3_dp_emitted(d, B, i)) return RFN_ERR_UNSUPPORTED;
+    return RFN_OK;
+}
+
 static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
                            const float* const* init_h, const float* const* init_c, const float* const* att,
                            float* comb, float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
-                           int train, RfnSeed seed, void* st) {
+                           int train, RfnSeed seed, const int32_t* const* att_len, void* st) {
     RFN_TRY(check_dims(d));
     if (B < 1) return RFN_ERR_SHAPE;
     if (!prm || (!fc && !(init_h && init_c)) || !att || !ws) return RFN_ERR_ARG;
+    RFN_TRY(check_att_len(d, B, att_len));
     const PrefixLayout Lo = prefix_layout(d, B, train);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     Prefix c(d, B, prm, att, ws, Lo, seed, st);
+    c.att_len = att_len;
     RFN_TRY(phase_gemm(d, c.W, Lo.gws, Lo.tk, true, st, &c.gx));
     RFN_TRY(c.init_state(fc, init_h, init_c));
     RFN_TRY(c.s1_projections());
@@ -633,38 +660,51 @@ static int prefix_fwd_impl(const rfn_dims* d, int B, const float* const* prm, co
     return mem_batch({{comb, c.h2 + BR, (long)T2 * BR}, {h_out, c.h2 + (long)T2 * BR, BR}, {c_out, c.c2 + (long)T2 * BR, BR}}, st);
 }
 
-extern "C" int rfn_prefix_fwd(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
-                              const float* const* att, float* comb, float* h_out, float* c_out, float* reason_pred,
-                              void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
+extern "C" int rfn_prefix_fwd_ex(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
+                                 const float* const* att, float* comb, float* h_out, float* c_out, float* reason_pred,
+                                 void* ws, size_t ws_bytes, int train, uint64_t seed, const int32_t* const* att_len, void* st) {
     if (!fc) return RFN_ERR_ARG;
     RfnSeed sd;
     RFN_TRY(path_seed(d, seed, &sd));
     return prefix_fwd_impl(d, B, prm, fc, nullptr, nullptr, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, train,
-                           sd, st);
+                           sd, att_len, st);
+}
+extern "C" int rfn_prefix_fwd(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
+                              const float* const* att, float* comb, float* h_out, float* c_out, float* reason_pred,
+                              void* ws, size_t ws_bytes, int train, uint64_t seed, void* st) {
+    return rfn_prefix_fwd_ex(d, B, prm, fc, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, train, seed, nullptr, st);
 }
 // get_thought_vectors with a caller-provided state_list (inference only: no backward through the given state)
+extern "C" int rfn_prefix_fwd_from_state_ex(const rfn_dims* d, int B, const float* const* prm, const float* const* init_h,
+                                            const float* const* init_c, const float* const* att, float* comb,
+                                            float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
+                                            const int32_t* const* att_len, void* st) {
+    if (!init_h || !init_c) return RFN_ERR_ARG;
+    return prefix_fwd_impl(d, B, prm, nullptr, init_h, init_c, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, 0,
+                           RfnSeed{}, att_len, st);
+}
 extern "C" int rfn_prefix_fwd_from_state(const rfn_dims* d, int B, const float* const* prm, const float* const* init_h,
                                          const float* const* init_c, const float* const* att, float* comb,
                                          float* h_out, float* c_out, float* reason_pred, void* ws, size_t ws_bytes,
                                          void* st) {
-    if (!init_h || !init_c) return RFN_ERR_ARG;
-    return prefix_fwd_impl(d, B, prm, nullptr, init_h, init_c, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, 0,
-                           RfnSeed{}, st);
+    return rfn_prefix_fwd_from_state_ex(d, B, prm, init_h, init_c, att, comb, h_out, c_out, reason_pred, ws, ws_bytes, nullptr, st);
 }
 
-extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
-                              const float* const* att, const float* d_comb, const float* d_h, const float* d_c,
-                              const float* d_reason, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg,
-                              int defer_wgrad, void* st) {
+extern "C" int rfn_prefix_bwd_ex(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
+                                 const float* const* att, const float* d_comb, const float* d_h, const float* d_c,
+                                 const float* d_reason, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg,
+                                 int defer_wgrad, const int32_t* const* att_len, void* st) {
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
     if (B < 1) return RFN_ERR_SHAPE;
     if (!prm || !fc || !att || !grd || !ws) return RFN_ERR_ARG;
+    RFN_TRY(check_att_len(d, B, att_len));
     const PrefixLayout Lo = prefix_layout(d, B, 1);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     Prefix c(d, B, prm, att, ws, Lo, seed, st);
     c.grd = grd;
+    c.att_len = att_len;
     RFN_TRY(phase_gemm(d, c.W, Lo.gws, Lo.tk, true, st, &c.gx));
     if (c.T1 > 64 || c.T2 > 64) return RFN_ERR_SHAPE;
     RFN_TRY(c.s2_head_bwd(d_comb, d_reason));
@@ -679,6 +719,12 @@ extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm,
         for (int part = 1; part <= 2; ++part)
             for (int i = 0; i < c.M; ++i) RFN_TRY(rfn_prefix_bwd_wgrad(d, B, att, grd, ws, ws_bytes, i, part, st));
     return RFN_OK;
+}
+extern "C" int rfn_prefix_bwd(const rfn_dims* d, int B, const float* const* prm, const float* const* fc,
+                              const float* const* att, const float* d_comb, const float* d_h, const float* d_c,
+                              const float* d_reason, float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg,
+                              int defer_wgrad, void* st) {
+    return rfn_prefix_bwd_ex(d, B, prm, fc, att, d_comb, d_h, d_c, d_reason, grd, ws, ws_bytes, seed_arg, defer_wgrad, nullptr, st);
 }
 
 // Stage-I weight gradients of ONE encoder, grouped over the T1 steps (bias gradients ride along):

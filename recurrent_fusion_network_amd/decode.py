@@ -617,16 +617,18 @@ class ScoreBuffers:
         return out
 
 
-def rescore(scorer, fc_feats, att_feats, cands, n_cand=None, opt={}):
+def rescore(scorer, fc_feats, att_feats, cands, n_cand=None, opt={}, att_lens=None):
     """n-best rescoring: score an image's m candidates with `scorer` (anything with .score: a RecurrentFusionModel, an
     EnsembleDecoder) -> (best (B,) int64, scores (B, m) f64).  cands (B, m, T) int64 as `model.candidates['seq']` after
     keep_candidates, or a sample_n call's rows viewed per image; n_cand (B,) counts the valid ones (None: all m).  scores[k, j] is
     the scorer's 'score' (opt['length_penalty'] applies), -inf for j >= n_cand[k]; best[k] is the first maximum, -1 where
-    n_cand[k] == 0 (rewards.consensus_gather writes zeros for it).  Nothing is read back."""
+    n_cand[k] == 0 (rewards.consensus_gather writes zeros for it).  Nothing is read back.  att_lens: the scorer's keyword (ragged
+    attention maps), passed on when given."""
     if cands.dim() != 3:
         raise ValueError('cands must be (B, m, T), got %s' % (tuple(cands.shape),))
     B, m = cands.size(0), cands.size(1)
-    scores = scorer.score(fc_feats, att_feats, cands, opt)['score'].view(B, m)
+    kw = {} if att_lens is None else {'att_lens': att_lens}
+    scores = scorer.score(fc_feats, att_feats, cands, opt, **kw)['score'].view(B, m)
     if n_cand is not None:
         valid = torch.arange(m, device=scores.device)[None, :] < n_cand.to(scores.device)[:, None]
         scores = torch.where(valid, scores, torch.full_like(scores, float('-inf')))

@@ -21,6 +21,8 @@ from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _dive
                      _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, keep_candidates_n)
 
 
+# Every entry point takes `att_lens` as RecurrentFusionModel's do (INTEGRATION.md "Ragged attention maps"): the per-image row counts
+# of the stage-I attention maps, handed to every member's stage I.
 class EnsembleDecoder:
     def __init__(self, models, process_group=None, total_members=None):
         """models: the members held by THIS process (same device, same vocabulary / seq_length).
@@ -53,7 +55,7 @@ class EnsembleDecoder:
         N.check(N.lib.rfn_div_2d(logit_sum.data_ptr(), V1, rows, V1, float(self.n_total), st))
 
     @torch.no_grad()
-    def sample(self, fc_feats, att_feats, opt={}):
+    def sample(self, fc_feats, att_feats, opt={}, att_lens=None):
         """Greedy ensemble decode -> (seq (B,<=S), seqLogprobs, logprobs_all (B,<=S+1,V+1)) with the reference's
         sample() conventions (finished rows masked to 0, early exit when every row has finished).  opt: the decoding
         constraints of RecurrentFusionModel.sample ('block_ngram', 'banned_ids', 'bad_endings'), applied to the averaged
@@ -63,7 +65,7 @@ class EnsembleDecoder:
         cons = _Constraints.parse(opt, V1, S)
         steppers = []
         for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
             steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
         dev = steppers[0].h.device
         st = N.stream_ptr()
@@ -89,7 +91,7 @@ class EnsembleDecoder:
         return bufs.read_back()        # nothing is read back before this: the call synchronises here, once
 
     @torch.no_grad()
-    def score(self, fc_feats, att_feats, seq, opt={}):
+    def score(self, fc_feats, att_feats, seq, opt={}, att_lens=None):
         """RecurrentFusionModel.score under the members' averaged distribution: the same arguments, the same dict.  The members
         step teacher-forced on the given tokens, each step's mean logits go through rfn_score_logits (T = 1, t0 = t) and the
         captions are summed at the end; only one step's (rows, V+1) logits exist at a time, so opt['max_rows'] has nothing to
@@ -102,7 +104,7 @@ class EnsembleDecoder:
         V1 = m0.vocab_size + 1
         steppers = []
         for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
             if n > 1:
                 comb, h, c = comb.repeat_interleave(n, dim=1), h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
             steppers.append(_Stepper(m, comb.contiguous(), h.clone(), c.clone()))
@@ -123,7 +125,7 @@ class EnsembleDecoder:
         return bufs.result()
 
     @torch.no_grad()
-    def teacher_logits(self, fc_feats, att_feats, seq):
+    def teacher_logits(self, fc_feats, att_feats, seq, att_lens=None):
         """The members' mean pre-softmax logits on the ground-truth prefix, as the `teacher` of
         RecurrentFusionModel.forward_loss: -> (B, S, V+1), S as the model's forward finds it (the first all-zero label column).
         The members step teacher-forced on seq[:, :S]; step t's mean goes straight into row block t of ONE (S, B, V+1) buffer,
@@ -138,7 +140,7 @@ class EnsembleDecoder:
         V1 = m0.vocab_size + 1
         steppers = []
         for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
             steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
         dev = steppers[0].h.device
         feed = seq[:, :S].to(dev).long().t().contiguous()      # row t = the tokens fed at step t
@@ -149,7 +151,7 @@ class EnsembleDecoder:
         return out.transpose(0, 1)
 
     @torch.no_grad()
-    def teacher_topk(self, fc_feats, att_feats, seq, k):
+    def teacher_topk(self, fc_feats, att_feats, seq, k, att_lens=None):
         """`teacher_logits` as a compact teacher: -> distill.TopKTeacher (B, S, k), the k <= min(32, V+1) best entries of every
         row of the members' mean logits, as log-probs in rfn_log_softmax_topk's order.  Each step's mean goes through that
         kernel into slice t of one (S, B, k) pair of buffers, so only ONE (B, V+1) block of logits ever exists -- never
@@ -167,7 +169,7 @@ class EnsembleDecoder:
         S = m0._decoder_steps(seq)
         steppers = []
         for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
             steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
         dev = steppers[0].h.device
         st = N.stream_ptr()
@@ -183,7 +185,7 @@ class EnsembleDecoder:
         return TopKTeacher(ids.transpose(0, 1), logp.transpose(0, 1))
 
     @torch.no_grad()
-    def sample_beam(self, fc_feats, att_feats, opt={}):
+    def sample_beam(self, fc_feats, att_feats, opt={}, att_lens=None):
         """Beam search on the members' averaged distribution -> (seq (B, S), seqLogprobs (B, S), top_seq, top_prob) with
         the conventions of RecurrentFusionModel.sample_beam (best done beam per image; per-image lists of all done beams,
         best first); `self.done_beams` as there, and with opt['group_size'] > 1 (diverse beam search) `self.diverse_beams` and the
@@ -204,7 +206,7 @@ class EnsembleDecoder:
         keep = None if keep_n is None else {'n': keep_n}
         steppers = []
         for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0)
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
             steppers.append(_Stepper(m, comb.repeat_interleave(W, dim=1).contiguous(),       # row k * W + q = image k
                                      h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous()))
         dev = steppers[0].h.device

@@ -104,7 +104,8 @@ class _PrefixFn(torch.autograd.Function):
     """Phase 1 (fc2h + fusion stages I and II) as one autograd node: rfn_prefix_fwd / rfn_prefix_bwd."""
 
     @staticmethod
-    def forward(ctx, model, save_bwd, drop, seed, M, *tensors):
+    def forward(ctx, model, save_bwd, drop, seed, M, lens, *tensors):
+        # lens: None, or M entries (None | (B,) int32 device tensor): the valid rows of each stage-I map (N.att_lens_arg)
         fc = [N.require_cuda_f32(t, 'fc_feats') for t in tensors[:M]]
         att = [N.require_cuda_f32(t, 'att_feats') for t in tensors[M:2 * M]]
         params = tensors[2 * M:]
@@ -120,10 +121,12 @@ class _PrefixFn(torch.autograd.Function):
         h = torch.empty(B, R, device=dev)
         c = torch.empty(B, R, device=dev)
         reason = torch.empty(M + 1, B, K, device=dev)
-        N.check(N.lib.rfn_prefix_fwd(C.byref(d), B, table, N.ptr_array(fc), N.ptr_array(att), comb.data_ptr(),
-                                     h.data_ptr(), c.data_ptr(), reason.data_ptr(), ws.data_ptr(), ws_bytes,
-                                     int(train), seed, N.stream_ptr()), 'rfn_prefix_fwd')
+        len_ptrs = N.ptr_array(lens) if lens is not None else None
+        model._check_ragged(N.lib.rfn_prefix_fwd_ex(C.byref(d), B, table, N.ptr_array(fc), N.ptr_array(att), comb.data_ptr(),
+                                                    h.data_ptr(), c.data_ptr(), reason.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                    int(train), seed, len_ptrs, N.stream_ptr()), lens, 'rfn_prefix_fwd')
         if train:
+            ctx.lens = lens
             ctx.model, ctx.seed, ctx.M, ctx.B, ctx.drop = model, seed, M, B, drop
             ctx.fc, ctx.att, ctx.params, ctx.consumed, ctx.snapshot = fc, att, params, False, None
             # the multi-GB workspace is a SAVED tensor, not an attribute: autograd frees it right after a non-retained
@@ -143,6 +146,7 @@ class _PrefixFn(torch.autograd.Function):
         d_comb, d_h, d_c, d_reason = cont(d_comb), cont(d_h), cont(d_c), cont(d_reason)
         ws_bytes = ws.numel()
         att_ptrs = N.ptr_array(ctx.att)
+        len_ptrs = N.ptr_array(ctx.lens) if ctx.lens is not None else None
         if ctx.consumed and ctx.snapshot is not None:
             # model.retain_activations: the activations of the ORIGINAL forward (see below).  Through .data: `ws` is a
             # saved tensor, and a versioned in-place write would make autograd refuse the NEXT backward over this graph
@@ -159,17 +163,17 @@ class _PrefixFn(torch.autograd.Function):
             R, T2, K = d.R, d.T2, d.K
             scratch = torch.empty(T2 * B * R + 2 * B * R + (M + 1) * B * K, device=dev)
             o1, o2, o3 = T2 * B * R, T2 * B * R + B * R, T2 * B * R + 2 * B * R
-            N.check(N.lib.rfn_prefix_fwd(C.byref(d), B, table, N.ptr_array(ctx.fc), att_ptrs, scratch.data_ptr(),
-                                         scratch[o1:].data_ptr(), scratch[o2:].data_ptr(), scratch[o3:].data_ptr(),
-                                         ws.data_ptr(), ws_bytes, 1, ctx.seed, N.stream_ptr()),
+            N.check(N.lib.rfn_prefix_fwd_ex(C.byref(d), B, table, N.ptr_array(ctx.fc), att_ptrs, scratch.data_ptr(),
+                                            scratch[o1:].data_ptr(), scratch[o2:].data_ptr(), scratch[o3:].data_ptr(),
+                                            ws.data_ptr(), ws_bytes, 1, ctx.seed, len_ptrs, N.stream_ptr()),
                     'rfn_prefix_fwd (recompute)')
         elif getattr(model, 'retain_activations', False):
             ctx.snapshot = ws.clone()
         ctx.consumed = True
         # everything except the per-encoder stage-I weight gradients ...
-        N.check(N.lib.rfn_prefix_bwd(C.byref(d), B, table, N.ptr_array(ctx.fc), att_ptrs, N.ptr(d_comb),
-                                     N.ptr(d_h), N.ptr(d_c), N.ptr(d_reason), gtable, ws.data_ptr(), ws_bytes,
-                                     ctx.seed, 1, N.stream_ptr()), 'rfn_prefix_bwd')
+        model._check_ragged(N.lib.rfn_prefix_bwd_ex(C.byref(d), B, table, N.ptr_array(ctx.fc), att_ptrs, N.ptr(d_comb),
+                                                    N.ptr(d_h), N.ptr(d_c), N.ptr(d_reason), gtable, ws.data_ptr(), ws_bytes,
+                                                    ctx.seed, 1, len_ptrs, N.stream_ptr()), ctx.lens, 'rfn_prefix_bwd')
         model._bucket_done('core', flats['core'])
         # ... then the per-encoder stage-I weight gradients, the BIG buckets first: part a of every encoder (H2h, z2h,
         # h_2_att_h: 277 MB each at C3, short K = B GEMMs) is produced and handed over before the first long att_2_att_h
@@ -183,7 +187,7 @@ class _PrefixFn(torch.autograd.Function):
             N.check(N.lib.rfn_prefix_bwd_wgrad(C.byref(d), B, att_ptrs, gtable, ws.data_ptr(), ws_bytes, i,
                                                part, N.stream_ptr()), 'rfn_prefix_bwd_wgrad')
             model._bucket_done('enc%d%s' % (i, tag), flats['enc%d%s' % (i, tag)])
-        return (None, None, None, None, None) + (None,) * (2 * M) + (None,) * len(ctx.params)
+        return (None, None, None, None, None, None) + (None,) * (2 * M) + (None,) * len(ctx.params)
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -629,11 +633,29 @@ class RecurrentFusionModel(nn.Module):
                     i, tuple(att_feats[i].shape), (B, self.att_num[i], self.att_feat_size[i])))
         return B
 
-    def _prefix(self, fc_feats, att_feats, drop, seed):
+    def _att_lens(self, att_lens, B, dev):
+        """The `att_lens` keyword of the entry points (INTEGRATION.md "Ragged attention maps") as _PrefixFn takes it; the forms
+        that were not taught lengths are refused by name before anything is launched."""
+        lens = N.att_lens_arg(att_lens, self.att_num, B, dev)
+        if lens is not None:
+            for bit, name in ((N.PATH_OPT_PERSIST_S2_FWD, 'RFN_PATH_OPT_PERSIST_S2_FWD'),
+                              (N.PATH_OPT_PERSIST_S2_BWD, 'RFN_PATH_OPT_PERSIST_S2_BWD')):
+                if int(self.path_flags) & bit:
+                    raise N.RfnError('att_lens: path_flags selects %s, a form that was not taught per-image lengths' % name)
+        return lens
+
+    def _check_ragged(self, rc, lens, what):
+        if rc == -2 and lens is not None and int(self.gemm_flags) & N.GEMM_OPT_BF16X3:   # RFN_ERR_UNSUPPORTED
+            raise N.RfnError('att_lens: gemm_flags selects RFN_GEMM_OPT_BF16X3, whose attention backward writes bf16 planes '
+                             '(rfn_attn_bwd_grouped_ks) and was not taught per-image lengths')
+        N.check(rc, what)
+
+    def _prefix(self, fc_feats, att_feats, drop, seed, att_lens=None):
         """-> comb (T2,B,R) time-major, h, c (B,R), reason (M+1,B,K).  `drop`: apply dropout (training mode)."""
-        self._check_inputs(fc_feats, att_feats)
+        B = self._check_inputs(fc_feats, att_feats)
         params = self._params_of(self._prefix_slots)
-        cacheable = self.reuse_prefix and not (drop and (self.drop_prob_fusion > 0 or self.drop_prob_reason > 0))
+        lens = self._att_lens(att_lens, B, fc_feats[0].device)
+        cacheable = self.reuse_prefix and not (drop and (self.drop_prob_fusion > 0 or self.drop_prob_reason > 0)) and lens is None
         if cacheable:
             ins = list(fc_feats) + list(att_feats)
             stamp = (tuple(t._version for t in ins), sum(p._version for p in params), self._weights_epoch)
@@ -641,7 +663,7 @@ class RecurrentFusionModel(nn.Module):
             if (hit is not None and not torch.is_grad_enabled() and hit[1] == stamp and len(hit[0]) == len(ins)
                     and all(r() is t for r, t in zip(hit[0], ins))):
                 return hit[2]
-        out = _PrefixFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, self.num_feat_array, *fc_feats,
+        out = _PrefixFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, self.num_feat_array, lens, *fc_feats,
                               *att_feats, *params)
         if cacheable:
             # weak references: a dead input invalidates the entry, so a recycled address can never alias it
@@ -671,8 +693,13 @@ class RecurrentFusionModel(nn.Module):
         return _fresh_seed() if train else 0
 
     # ---- reference API ----------------------------------------------------------------------------
-    def forward(self, fc_feats, att_feats, seq):
-        """misc/RecurrentFusionModel.py:198-281 -> (log_prob (B,T,V+1), reason_pred list[M+1] of (B,K))."""
+    def forward(self, fc_feats, att_feats, seq, att_lens=None):
+        """misc/RecurrentFusionModel.py:198-281 -> (log_prob (B,T,V+1), reason_pred list[M+1] of (B,K)).
+
+        att_lens (here and on forward_loss, get_thought_vectors, sample, sample_beam, sample_group, sample_distinct, score):
+        ragged attention maps -- per image, how many rows of att_feats[i] are real (INTEGRATION.md "Ragged attention maps").
+        One (B,) integer tensor or sequence for all encoders, or a list of M such values with None for an encoder whose maps
+        are full.  Stage I attends over those rows only; the padded rows must be finite.  fc_feats stays the caller's."""
         train = bool(self.training)
         seed = self._step_seed(train)
         S = self._decoder_steps(seq)          # may read `seq` back once: do it before queueing phase 1
@@ -681,18 +708,21 @@ class RecurrentFusionModel(nn.Module):
             if train and (self.drop_prob_fusion > 0 or self.drop_prob_reason > 0):
                 raise N.RfnError('dedup_seq_per_img needs drop_prob_fusion = drop_prob_reason = 0')
             rows, n_feat = seq.size(0), fc_feats[0].size(0)
+            lens_u = self._att_lens(att_lens, n_feat, fc_feats[0].device)
             if n_feat == rows and rows % g == 0:      # caption rows (the loader's layout): keep one row per image
                 fc_u, att_u = [f[::g] for f in fc_feats], [a[::g] for a in att_feats]
+                if lens_u is not None:
+                    lens_u = [None if v is None else v[::g].contiguous() for v in lens_u]
             elif n_feat * g == rows:                  # unique images already (FeatureFeeder.batch(expand=False))
                 fc_u, att_u = list(fc_feats), list(att_feats)
             else:
                 raise N.RfnError('dedup_seq_per_img = %d: %d feature rows do not match %d caption rows' % (g, n_feat, rows))
-            comb, h, c, reason = self._prefix(fc_u, att_u, train, seed)
+            comb, h, c, reason = self._prefix(fc_u, att_u, train, seed, lens_u)
             comb = comb.repeat_interleave(g, dim=1)       # autograd sums the caption rows back onto the image
             h, c = h.repeat_interleave(g, dim=0), c.repeat_interleave(g, dim=0)
             reason = reason.repeat_interleave(g, dim=1)
         else:
-            comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
+            comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed, att_lens)
         log_prob = self._decode_teacher_forced(seq[:, :S], comb, h, c, train, seed, self.ss_prob)
         return log_prob, list(reason.unbind(0))
 
@@ -725,7 +755,7 @@ class RecurrentFusionModel(nn.Module):
         return teacher.detach()
 
     def forward_loss(self, fc_feats, att_feats, seq, masks, top_words, crit, reason_weight=1.0, teacher=None, kd_alpha=0.5,
-                     kd_temperature=1.0):
+                     kd_temperature=1.0, att_lens=None):
         """The XE train step's forward AND criterion in one call (opt-in) ->
         (loss, reason_pred): the value and the gradients of
             log_prob, reason_pred = model(fc_feats, att_feats, seq)
@@ -759,7 +789,7 @@ class RecurrentFusionModel(nn.Module):
             if not (0.0 < kd_temperature < float('inf')):
                 raise N.RfnError('kd_temperature = %g must be positive and finite' % kd_temperature)
         if self.ss_prob > 0:
-            log_prob, reason = self.forward(fc_feats, att_feats, seq)
+            log_prob, reason = self.forward(fc_feats, att_feats, seq, att_lens=att_lens)
             return crit(log_prob, seq[:, 1:], masks[:, 1:], reason, top_words, reason_weight), reason
         train = bool(self.training)
         seed = self._step_seed(train)
@@ -774,7 +804,7 @@ class RecurrentFusionModel(nn.Module):
             z = self._check_teacher(teacher, seq.size(0), S, dev)
             if kd_alpha > 0.0:
                 kd, terms = (z, kd_alpha, 1.0 / kd_temperature), torch.empty(2, device=dev)
-        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed, att_lens)
         seq = seq.to(dev).long()
         masks = masks.to(dev).float()
         if seq.stride(1) != 1:
@@ -820,19 +850,19 @@ class RecurrentFusionModel(nn.Module):
                 out.append((h0, h0.clone()))
         return out
 
-    def get_thought_vectors(self, fc_feats, att_feats, state_list=None):
+    def get_thought_vectors(self, fc_feats, att_feats, state_list=None, att_lens=None):
         """misc/RecurrentFusionModel.py:283-331 -> (thought_vectors_comb (B,T2,R), reason_pred, state_review).
         `state_list`: the M (h, c) pairs of shape (1,B,R) that get_init_state returns -- used as given, like the
         reference; None recomputes them from fc_feats."""
         with torch.no_grad():
             if state_list is None:
-                comb, h, c, reason = self._prefix(fc_feats, att_feats, False, 0)
+                comb, h, c, reason = self._prefix(fc_feats, att_feats, False, 0, att_lens)
             else:
-                comb, h, c, reason = self._prefix_from_state(att_feats, state_list)
+                comb, h, c, reason = self._prefix_from_state(att_feats, state_list, att_lens)
         return (comb.transpose(0, 1).contiguous(), list(reason.unbind(0)),
                 (h.unsqueeze(0), c.unsqueeze(0)))
 
-    def _prefix_from_state(self, att_feats, state_list):
+    def _prefix_from_state(self, att_feats, state_list, att_lens=None):
         M, R = self.num_feat_array, self.rnn_size
         if len(state_list) != M or len(att_feats) != M:
             raise N.RfnError('expected %d (h, c) states and att feature tensors' % M)
@@ -847,6 +877,7 @@ class RecurrentFusionModel(nn.Module):
                 raise N.RfnError('att_feats[%d] has shape %s' % (i, tuple(att[i].shape)))
         d = self._dims_for(False)
         dev = att[0].device
+        lens = self._att_lens(att_lens, B, dev)
         K = self.top_words_count
         table = self._param_table(self._params_of(self._prefix_slots), self._prefix_slots)
         ws_bytes = N.lib.rfn_prefix_ws_bytes(C.byref(d), B, 0)
@@ -854,10 +885,11 @@ class RecurrentFusionModel(nn.Module):
         comb = torch.empty(d.T2, B, R, device=dev)
         h, c = torch.empty(B, R, device=dev), torch.empty(B, R, device=dev)
         reason = torch.empty(M + 1, B, K, device=dev)
-        N.check(N.lib.rfn_prefix_fwd_from_state(C.byref(d), B, table, N.ptr_array(hs), N.ptr_array(cs),
-                                                N.ptr_array(att), comb.data_ptr(), h.data_ptr(), c.data_ptr(),
-                                                reason.data_ptr(), ws.data_ptr(), ws_bytes, N.stream_ptr()),
-                'rfn_prefix_fwd_from_state')
+        self._check_ragged(N.lib.rfn_prefix_fwd_from_state_ex(C.byref(d), B, table, N.ptr_array(hs), N.ptr_array(cs),
+                                                              N.ptr_array(att), comb.data_ptr(), h.data_ptr(), c.data_ptr(),
+                                                              reason.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                              N.ptr_array(lens) if lens is not None else None, N.stream_ptr()),
+                           lens, 'rfn_prefix_fwd_from_state')
         return comb, h, c, reason
 
     def one_time_step(self, xt, fc_feats, thought_vectors_comb, state_decode):
@@ -872,7 +904,7 @@ class RecurrentFusionModel(nn.Module):
             logits = stepper.step(xt.contiguous(), want='logits')
             return logits, (stepper.h.unsqueeze(0), stepper.c.unsqueeze(0))
 
-    def sample(self, fc_feats, att_feats, opt={}):
+    def sample(self, fc_feats, att_feats, opt={}, att_lens=None):
         """misc/RecurrentFusionModel.py:545-658.
 
         opt['consensus'] = a rewards.CiderD scorer, with sample_max = 0 and sample_n = n > 1 (rfn.h "consensus reranking"): the n
@@ -886,7 +918,7 @@ class RecurrentFusionModel(nn.Module):
         if beam_size > 1:
             if samp is not None:
                 raise ValueError('top_k / top_p / sample_n apply to multinomial sampling, not to beam search')
-            return self.sample_beam(fc_feats, att_feats, opt)
+            return self.sample_beam(fc_feats, att_feats, opt, att_lens=att_lens)
         cons = _Constraints.parse(opt, self.vocab_size + 1, self.seq_length)
         if cons is not None and opt.get('force_ids', None) is not None:
             raise ValueError('force_ids replays given tokens: decoding constraints cannot be combined with it')
@@ -907,7 +939,7 @@ class RecurrentFusionModel(nn.Module):
         train = bool(self.training)
         seed = self._step_seed(train)
         with torch.set_grad_enabled(want_grad):
-            comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
+            comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed, att_lens)
         reason_pred = list(reason.unbind(0))
         force = opt.get('force_ids', None)
         if (not sample_max and cons is None and samp is None) or force is not None:
@@ -916,7 +948,7 @@ class RecurrentFusionModel(nn.Module):
             out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp, cs)
         return (*out, reason_pred)
 
-    def sample_group(self, fc_feats, att_feats, n, opt={}):
+    def sample_group(self, fc_feats, att_feats, n, opt={}, att_lens=None):
         """The RL trainer's sampled pass (train_rl.py:160, misc/RecurrentFusionModel.py:623-631) with n draws per image ->
         (seq (B*n, <= S), seqLogprobs, logprobs_all, reason_pred) with rows image-major (row k * n + j is draw j of image k) and
         reason_pred per image.  Stages I and II run once per image; ONE decoder node carries the n rows of every image, reads
@@ -940,13 +972,13 @@ class RecurrentFusionModel(nn.Module):
         train = bool(self.training)
         seed = self._step_seed(train)
         want_grad = torch.is_grad_enabled()
-        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed)
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed, att_lens)
         if n > 1:      # the state fans out to the rows (autograd sums it back); the thought vectors stay per image
             h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
         out = self._sample_replayed(comb, h, c, train, seed, want_grad, opt.get('temperature', 1.0), force, n)
         return (*out, list(reason.unbind(0)))
 
-    def sample_distinct(self, fc_feats, att_feats, n, opt={}):
+    def sample_distinct(self, fc_feats, att_feats, n, opt={}, att_lens=None):
         """n DISTINCT sampled captions per image by stochastic beam search (rfn.h "stochastic beam search"; Kool et al. 2019; the
         reference has nothing of the kind): one beam search of width n on Gumbel-perturbed log-probabilities, an exact sample
         without replacement from the model's distribution over captions -> (seq (B*n, S) int64, seqLogprobs (B*n, S) f32,
@@ -977,7 +1009,7 @@ class RecurrentFusionModel(nn.Module):
         drop = bool(self.training)
         seed = _fresh_seed() if drop else 0
         noise_seed = sb.seed if sb.seed is not None else _fresh_seed()
-        comb, h, c, reason = self._prefix(fc_feats, att_feats, drop, seed)
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, drop, seed, att_lens)
         dev = comb.device
         stepper = _Stepper(self, comb, h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous(),
                            drop, seed)
@@ -1045,7 +1077,7 @@ class RecurrentFusionModel(nn.Module):
         return bufs.read_back()        # waits for the loop: the call's one read-back
 
     @torch.no_grad()
-    def score(self, fc_feats, att_feats, seq, opt={}):
+    def score(self, fc_feats, att_feats, seq, opt={}, att_lens=None):
         """How likely the model finds the captions it is GIVEN (rfn.h "caption scoring"; the reference has nothing of the kind) ->
         a dict of device tensors over the caption rows (image-major):
             'token_logprobs' (rows, steps) f32   log-prob of each given token, 0 at positions that are not scored
@@ -1067,7 +1099,7 @@ class RecurrentFusionModel(nn.Module):
         rows, n, T = so.layout(seq.shape, B, self.seq_length)
         if n > 1 and int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
             raise N.RfnError('n captions per image need the hoisted decoder cell (path_flags select another form)')
-        comb, h, c, _ = self._prefix(fc_feats, att_feats, False, 0)
+        comb, h, c, _ = self._prefix(fc_feats, att_feats, False, 0, att_lens)
         dev = comb.device
         if n > 1:
             h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
@@ -1089,7 +1121,7 @@ class RecurrentFusionModel(nn.Module):
                                             sl(bufs.cap_len), ws.data_ptr(), ws_bytes, n, N.stream_ptr()), 'rfn_decoder_score')
         return bufs.result()
 
-    def sample_beam(self, fc_feats, att_feats, opt={}):
+    def sample_beam(self, fc_feats, att_feats, opt={}, att_lens=None):
         """misc/RecurrentFusionModel.py:352-543, batched and device-resident.
 
         Stages I/II run ONCE for the batch (the reference recomputes them per image on beam_size identical rows),
@@ -1138,7 +1170,7 @@ class RecurrentFusionModel(nn.Module):
         with torch.no_grad():
             drop = bool(self.training)
             seed = _fresh_seed() if drop else 0
-            comb_b, h_b, c_b, reason = self._prefix(fc_feats, att_feats, drop, seed)
+            comb_b, h_b, c_b, reason = self._prefix(fc_feats, att_feats, drop, seed, att_lens)
             dev = comb_b.device
             # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
             stepper = _Stepper(self, comb_b, h_b.repeat_interleave(W, dim=0).contiguous(),

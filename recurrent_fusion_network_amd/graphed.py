@@ -39,9 +39,16 @@ from . import _native as N
 from . import fusion_model
 
 
+def _refuse_att_lens(att_lens):
+    if att_lens is not None:
+        raise N.RfnError('GraphedTrainStep does not take att_lens: the captured step attends over every row of its static '
+                         'att_feats buffers (ragged attention maps run through model.forward_loss, uncaptured)')
+
+
 class GraphedTrainStep:
     def __init__(self, model, crit, opt, fc_feats, att_feats, labels, masks, top_words, reason_weight=1.0, warmup=3,
-                 full_length=True, device_rng=False):
+                 full_length=True, device_rng=False, att_lens=None):
+        _refuse_att_lens(att_lens)
         self.model, self.crit, self.opt, self.reason_weight = model, crit, opt, float(reason_weight)
         self.device_rng = bool(device_rng)
         self._check_capturable()
@@ -137,9 +144,10 @@ class GraphedTrainStep:
         self.opt.step(coef_dev=self.coef)
         return loss
 
-    def __call__(self, fc_feats=None, att_feats=None, labels=None, masks=None, top_words=None):
+    def __call__(self, fc_feats=None, att_feats=None, labels=None, masks=None, top_words=None, att_lens=None):
         """Replays the captured step on the given batch (None: the batch already in the static buffers) -> the loss tensor
         (a static buffer: read it before the next call)."""
+        _refuse_att_lens(att_lens)
         self._check_capturable()
         now = self._frozen_state()
         if now != self.frozen:
