@@ -97,6 +97,11 @@ typedef struct rfn_dims {
  * never writes to that location; the caller keeps its value unchanged from the forward launches of a step until the backward
  * (and recompute) launches of that step have run.  rfn_dropout_mask_dev publishes the masks of such a call. */
 #define RFN_PATH_OPT_SEED_DEV 256u
+/* Keep what the gradients of fc_feats / att_feats need (rfn_prefix_bwd_inputs, below): the training workspace holds T1 slices
+ * (B, D_i) of d z per encoder instead of one buffer reused by every step, and step t of the stage-I backward sweep writes its
+ * d z = d gates . W_z[t, i] into slice t.  Nothing else changes: forward outputs, every parameter gradient and dP1 are
+ * bit-identical to the run without the bit; without it the workspace size and every launch are what they were. */
+#define RFN_PATH_OPT_INPUT_GRADS 512u
 
 int rfn_abi_version(void);
 const char* rfn_error_string(int code);
@@ -338,6 +343,7 @@ int rfn_copy_small_f32(float* const* dst_host, const float* const* src_host, int
  *   rfn_attn_small_fwd:                                    L <= 1024 and 2 * Ap + L floats <= 64 KiB
  *   rfn_attn_small_bwd:                                    L <= 1024 and 2 * Ap + Dp + 2 * Lp floats <= 64 KiB
  *   rfn_attn_context_bwd_dseq:                             none beyond the extents.
+ *   rfn_attn_context_bwd_dseq_steps:                       T >= 1; T * min(Dp, 1024) + 32 * Tp floats <= 64 KiB (T <= 15 at D >= 1021)
  * A NULL required pointer (or host array, or array entry) is RFN_ERR_ARG; b_out, its array, and datt_seq of
  * rfn_attn_small_bwd may be NULL.
  *
@@ -378,6 +384,25 @@ int rfn_attn_context_bwd_dalpha(const float* att_seq, int64_t sb, int64_t sl, co
 /* datt_seq[b,l,:] += alpha[b,l] * dz[b,:]   (only for differentiable att_seq: stages II, decoder) */
 int rfn_attn_context_bwd_dseq(const float* alpha, const float* dz, int64_t lddz, int B, int L,
                               int D, float* datt_seq, int64_t sb, int64_t sl, void* stream);
+/* The same over T steps in ONE pass over the map (stage I: the context's share of d att_feats, rfn_prefix_bwd_inputs):
+ *   datt_seq[b,l,d] (=|+=) sum_{t < T} alpha[t * alpha_st + b * L + l] * dz[t * dz_st + b * lddz + d]
+ * Every map element is written once, and read once only when accumulate != 0; T calls of rfn_attn_context_bwd_dseq read
+ * and write the whole map T times.  Arithmetic: one fmaf chain per element, t ascending, starting from the previous value
+ * (accumulate != 0) or from 0: deterministic, and -- unlike the entries above -- the 16-byte and the scalar instantiation
+ * give the SAME bits.  datt_seq is accessed 16 bytes wide under the rule above (D % 4 == 0, sb and sl multiples of 4, a
+ * 16-byte aligned pointer); dz is read 16 bytes wide when lddz % 4 == 0, dz_st % 4 == 0 and it is 16-byte aligned, otherwise
+ * as scalars; alpha is only ever read as scalars.  The T dz rows of a block's D tile (at most 1024 columns) and the alpha of
+ * its rows (at most 32, T rounded up to Tp, a multiple of 4) are staged in LDS: T * min(Dp, 1024) + 32 * Tp floats <= 64 KiB,
+ * RFN_ERR_SHAPE beyond (nothing launched; a caller with more steps issues several calls, the later ones accumulating -- the
+ * chain is then the same).  The grid is tiled over (image, row chunk, D tile): 32
+ * rows per block, 8 when that would leave fewer than 1024 blocks.
+ * len: NULL, or a (B,) int32 DEVICE vector; n = clamp(len[b], 1, L) on the device.  Rows l >= n are written as exact zeros
+ * when accumulate == 0 and left alone otherwise; alpha and the map are never loaded there.
+ * T, B, L, D >= 1 (RFN_ERR_SHAPE); alpha, dz, datt_seq non-NULL (RFN_ERR_ARG); datt_seq must not overlap alpha or dz.
+ * (tests/test_dseq_steps_gpu.py pins all of the above.) */
+int rfn_attn_context_bwd_dseq_steps(int T, const float* alpha, int64_t alpha_st, const float* dz, int64_t dz_st, int64_t lddz,
+                                    int B, int L, int D, float* datt_seq, int64_t sb, int64_t sl, int accumulate,
+                                    const int32_t* len, void* stream);
 /* softmax + tanh backward.  ds = alpha*(dalpha - <alpha,dalpha>); dproj[b,l,a] (=|+=)
  * ds[b,l]*w[a]*(1-e^2), e = tanh(proj+hproj); dhproj[b,a] = sum_l dproj[b,l,a];
  * dw_part[b,a] = sum_l ds[b,l]*e[b,l,a]  (caller column-sums dw_part over b).
@@ -388,7 +413,8 @@ int rfn_attn_scores_bwd(const float* proj, int64_t proj_sb, int64_t proj_sl, con
                         int accumulate_dproj, float* dhproj, float* dw_part, void* stream);
 
 /* rfn_attn_context_bwd_dalpha + rfn_attn_scores_bwd in one launch, one block per batch row: dalpha never leaves
- * the CU.  Results are bit-identical to the pair.  (d att_seq is not produced: stage-I features need no gradient.) */
+ * the CU.  Results are bit-identical to the pair.  (d att_seq is not produced here: the stage-I feature gradient is a pass of its own
+ * over all steps, rfn_attn_context_bwd_dseq_steps / rfn_prefix_bwd_inputs.) */
 int rfn_attn_bwd(const float* proj, int64_t proj_sb, int64_t proj_sl, const float* hproj, const float* w_out,
                  const float* alpha, const float* att_seq, int64_t sb, int64_t sl, const float* dz, int64_t lddz,
                  int B, int L, int A, int D, float* dproj, int64_t dproj_sb, int64_t dproj_sl,
@@ -1194,6 +1220,20 @@ int rfn_prefix_bwd_ex(const rfn_dims* d, int B, const float* const* params,
                       const float* d_comb, const float* d_h, const float* d_c,
                       const float* d_reason_pred, float* const* grads, void* ws, size_t ws_bytes,
                       uint64_t seed, int defer_wgrad, const int32_t* const* att_len, void* stream);
+/* Gradients of phase 1 with respect to its INPUTS (encoder fine-tuning, saliency).  With x_i = att_feats[i]:
+ *   d x_i[b,l,:] = sum_t dP1_i[t][b,l,:] . W_att2att[t,i]     (A) the hoisted projections: one product, K = T1 * A
+ *                + sum_t alpha_i[t][b,l] * d z_i[t][b,:]      (B) the attention contexts: rfn_attn_context_bwd_dseq_steps
+ *   d fc_i       = (d h0_i + d c0_i) . W_fc2h[i]              (C) get_init_state sets c0 = h0 = fc2h(fc)
+ * Called after rfn_prefix_bwd[_ex] on the same workspace, with rfn_dims.path_flags carrying RFN_PATH_OPT_INPUT_GRADS in the
+ * forward, the backward and this call; before or after the rfn_prefix_bwd_wgrad calls (it only READS dP1, the attention
+ * rows, the d z slices and the stage-I state gradients).  d_att[i] (B, L_i, D_i) and d_fc[i] (B, F_i) are contiguous and
+ * OVERWRITTEN; either array, or any entry, may be NULL: that gradient is not produced (no launch for it -- the long product
+ * (A) included).  att_len: the lengths of the forward call; rows past an image's length come out as exact zeros.
+ * RFN_ERR_UNSUPPORTED, before anything is launched: path_flags without RFN_PATH_OPT_INPUT_GRADS (the workspace has no d z
+ * slices); RFN_GEMM_OPT_BF16X3 where it makes the attention backward write a requested encoder's dP1 as bf16 planes only;
+ * a workspace of the inference size (smaller than that: RFN_ERR_WORKSPACE). */
+int rfn_prefix_bwd_inputs(const rfn_dims* d, int B, const float* const* params, float* const* d_fc, float* const* d_att,
+                          void* ws, size_t ws_bytes, const int32_t* const* att_len, void* stream);
 
 /* Phase 2 = the teacher-forced decoder loop of forward() (misc/RecurrentFusionModel.py:257-281):
  * for s < S: xt = embed(ids[b,s]); decoder cell (misc/LSTMSoftAttentionCore.py:60-102);

@@ -27,6 +27,7 @@ PATH_OPT_NO_SMALL_TILES = 32      # rfn.h RFN_PATH_OPT_NO_SMALL_TILES (A/B hook)
 PATH_OPT_SHARED_SMALL_TILES = 64  # rfn.h RFN_PATH_OPT_SHARED_SMALL_TILES (A/B hook)
 PATH_OPT_DEC_UNHOISTED = 128      # rfn.h RFN_PATH_OPT_DEC_UNHOISTED (A/B hook: the three-launch decoder cell of rounds 3-5)
 PATH_OPT_SEED_DEV = 256           # rfn.h RFN_PATH_OPT_SEED_DEV: the `seed` argument is the device address of the dropout key
+PATH_OPT_INPUT_GRADS = 512        # rfn.h RFN_PATH_OPT_INPUT_GRADS: keep every stage-I step's d z for rfn_prefix_bwd_inputs
 CELL_VARIANT_DEEP = 256
 CAPTION_END_EXCLUDED = 1          # rfn.h RFN_CAPTION_END_EXCLUDED: a caption ends before its first 0 (validation), not after it
 GEMM_OPT_LDS_LEAN = 1
@@ -219,6 +220,9 @@ def _load():
         'rfn_prefix_fwd_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, SZ, I, U64, P, P]),
         'rfn_prefix_fwd_from_state_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, P, P]),
         'rfn_prefix_bwd_ex': (C.c_int, [DP, I, P, P, P, P, P, P, P, P, P, SZ, U64, I, P, P]),
+        # gradients of fc_feats / att_feats (rfn.h): after rfn_prefix_bwd_ex on a PATH_OPT_INPUT_GRADS workspace; and its kernel
+        'rfn_prefix_bwd_inputs': (C.c_int, [DP, I, P, P, P, P, SZ, P, P]),
+        'rfn_attn_context_bwd_dseq_steps': (C.c_int, [I, P, L, P, L, L, I, I, I, P, L, L, I, P, P]),
         'rfn_decoder_ws_bytes': (SZ, [DP, I, I, I]),
         'rfn_decoder_fwd': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, SZ, I, U64, P]),
         'rfn_decoder_fwd_begin': (C.c_int, [DP, I, I, P, P, P, P, P, SZ, I, P]),

@@ -439,6 +439,159 @@ extern "C" int rfn_attn_context_bwd_dseq(const float* alpha, const float* dz, in
     return RFN_OK;
 }
 
+// ---- datt_seq[b,l,:] (=|+=) sum_t alpha[t][b,l] * dz[t][b,:]  (stage I: the context's share of d att_feats) --------
+// All T steps in ONE pass over the map: each element is written once (and read once only when accumulating), where T calls
+// of attn_dseq_k read and write the whole map T times.  A block owns (image b, DSS_LC* rows, a D tile of <= DSS_DT
+// columns): it stages the tile's T dz rows and its rows' alpha (transposed: the T steps of a row side by side) in LDS once,
+// then every thread walks its rows in groups of DSS_RG (independent 16-B streams), reading its 4 columns of a step's dz once
+// for the whole group and a row's alpha four steps per read -- the only global accesses of the sweep are the map's own
+// (alpha straight from memory, T scalar loads per 16 bytes stored, ran at 0.29 of the copy rate; this form at 0.68 overwriting
+// and 0.88 accumulating: INTEGRATION.md "Input gradients", profiles/input_gradients.json).
+// A tile narrower than 1024 columns spreads the block over 256 / (tile / 4) rows at once, so small maps
+// do not idle most lanes.  Per element ONE fmaf chain, t ascending, whatever the instantiation: VEC and scalar give the same
+// bits.  Ragged maps (len): rows l >= n are never loaded (neither alpha nor the map); exact zeros without accumulate.
+#define DSS_DT 1024      // columns of a full D tile: ATT_THREADS x 4
+#define DSS_RG 4         // rows a thread keeps in flight
+#define DSS_LC_BIG 32    // rows per block when that still gives DSS_MIN_BLOCKS blocks ...
+#define DSS_LC_SMALL 8   // ... otherwise (small batches: B = 2 at 196 x 2048 is 100 blocks instead of 28)
+#define DSS_MIN_BLOCKS 1024
+#define DSS_LDS_BYTES (64 * 1024)
+template <bool VEC>
+__global__ __launch_bounds__(ATT_THREADS) void attn_dseq_steps_k(int T, const float* __restrict__ alpha, long alpha_st,
+                                                                const float* __restrict__ dz, long dz_st, long lddz, int dz_vec,
+                                                                int L, int D, float* __restrict__ dx, long sb, long sl,
+                                                                int accumulate, const int32_t* __restrict__ len, int LC, int nlc,
+                                                                int ndt) {
+    extern __shared__ __attribute__((aligned(16))) float dss_s[];   // alpha [LC][Tp], then dz [T][tw]
+    int bid = blockIdx.x;
+    const int dt = bid % ndt;
+    bid /= ndt;
+    const int lc = bid % nlc, b = bid / nlc, tid = threadIdx.x;
+    const int d0 = dt * DSS_DT;
+    const int nd = min(D - d0, DSS_DT);          // columns of this tile
+    const int tw = (nd + 3) & ~3, cpr = tw >> 2; // ... rounded up to whole float4s; threads per row
+    const int Tp = (T + 3) & ~3;
+    float* al_s = dss_s;
+    float* dz_s = dss_s + LC * Tp;
+    const int n = attn_row_len<true>(len, b, L);
+    const int lbeg = lc * LC, lend = min(lbeg + LC, L);
+    {   // alpha of the block's rows, transposed; rows past the image's length are not loaded (their entries are never used)
+        const int rows = min(lend, n) - lbeg;
+        const float* ab = alpha + (long)b * L + lbeg;
+        for (int i = tid; i < T * rows; i += ATT_THREADS) {
+            const int t = i / rows, r = i - t * rows;
+            al_s[r * Tp + t] = ab[t * alpha_st + r];
+        }
+    }
+    {   // the tile's dz rows -> LDS, zero behind column D
+        const int n4 = dz_vec ? nd >> 2 : 0;     // d0 is a multiple of 1024: a 16-B aligned dz row stays aligned in every tile
+        for (int i = tid; i < T * cpr; i += ATT_THREADS) {
+            const int t = i / cpr, q = i - t * cpr;
+            const float* src = dz + t * dz_st + b * lddz + d0 + 4 * q;
+            f32x4 v;
+            if (q < n4) v = *reinterpret_cast<const f32x4*>(src);
+            else
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (4 * q + e < nd) ? src[e] : 0.f;
+            *reinterpret_cast<f32x4*>(dz_s + t * tw + 4 * q) = v;
+        }
+    }
+    __syncthreads();
+    const int RP = ATT_THREADS / cpr;            // rows the block covers at once
+    const int rp = tid / cpr, q = tid - rp * cpr;
+    if (rp >= RP) return;                        // 256 is not a multiple of cpr: the leftover threads
+    const int dcol = d0 + 4 * q, left = D - dcol;   // left >= 1: columns of this thread inside the map
+    float* __restrict__ xb = dx + b * sb + dcol;
+    const float* zs = dz_s + 4 * q;
+#pragma unroll 1
+    for (int lg = lbeg + rp; lg < lend; lg += RP * DSS_RG) {
+        f32x4 acc[DSS_RG];
+        bool live[DSS_RG];
+#pragma unroll
+        for (int r = 0; r < DSS_RG; ++r) {
+            const int l = lg + r * RP;
+            live[r] = l < lend && l < n;
+            acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (live[r] && accumulate) {
+                const float* p = xb + l * sl;
+                if constexpr (VEC) acc[r] = *reinterpret_cast<const f32x4*>(p);
+                else
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (e < left) acc[r][e] = p[e];
+            }
+        }
+        const float* ar[DSS_RG];       // the row's T alphas in LDS (a row past the chunk re-reads the last one: discarded)
+#pragma unroll
+        for (int r = 0; r < DSS_RG; ++r) ar[r] = al_s + (min(lg + r * RP, lend - 1) - lbeg) * Tp;
+#pragma unroll 1
+        for (int t0 = 0; t0 < T; t0 += 4) {
+            f32x4 a4[DSS_RG];
+#pragma unroll
+            for (int r = 0; r < DSS_RG; ++r) a4[r] = *reinterpret_cast<const f32x4*>(ar[r] + t0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (t0 + j >= T) break;
+                const f32x4 g = *reinterpret_cast<const f32x4*>(zs + (t0 + j) * tw);
+#pragma unroll
+                for (int r = 0; r < DSS_RG; ++r) {
+                    if (!live[r]) continue;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[r][e] = fmaf(a4[r][j], g[e], acc[r][e]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < DSS_RG; ++r) {
+            const int l = lg + r * RP;
+            if (l >= lend || (!live[r] && accumulate)) continue;   // a padded row: zeros when overwriting, untouched otherwise
+            float* p = xb + l * sl;
+            if constexpr (VEC) *reinterpret_cast<f32x4*>(p) = acc[r];
+            else
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (e < left) p[e] = acc[r][e];
+        }
+    }
+}
+
+static int dss_tile_width(int D) {   // LDS row pitch of the widest tile: D rounded up to a float4, at most a full tile
+    const int Dp = (D + 3) & ~3;
+    return Dp < DSS_DT ? Dp : DSS_DT;
+}
+// floats of LDS: the rows' alpha (LC rows of T steps, padded to whole float4s) + T dz rows of the widest tile
+static size_t dss_lds_floats(int T, int D, int LC) { return (size_t)LC * ((T + 3) & ~3) + (size_t)T * dss_tile_width(D); }
+int rfn_attn_dseq_steps_max_t(int D) {   // the limit is stated for the 32-row chunk, whichever chunk the launch takes
+    int T = (int)(DSS_LDS_BYTES / sizeof(float)) / dss_tile_width(D);
+    while (T > 0 && dss_lds_floats(T, D, DSS_LC_BIG) * sizeof(float) > DSS_LDS_BYTES) --T;
+    return T;
+}
+
+extern "C" int rfn_attn_context_bwd_dseq_steps(int T, const float* alpha, int64_t alpha_st, const float* dz, int64_t dz_st,
+                                               int64_t lddz, int B, int L, int D, float* datt_seq, int64_t sb, int64_t sl,
+                                               int accumulate, const int32_t* len, void* stream) {
+    if (T <= 0 || B <= 0 || L <= 0 || D <= 0) return RFN_ERR_SHAPE;
+    if (!alpha || !dz || !datt_seq) return RFN_ERR_ARG;
+    if (T > rfn_attn_dseq_steps_max_t(D)) return RFN_ERR_SHAPE;
+    const int ndt = rfn_cdiv(D, DSS_DT);
+    const int LC = (long)B * ndt * rfn_cdiv(L, DSS_LC_BIG) >= DSS_MIN_BLOCKS ? DSS_LC_BIG : DSS_LC_SMALL;
+    const size_t lds = dss_lds_floats(T, D, LC) * sizeof(float);
+    const int nlc = rfn_cdiv(L, LC);
+    const long blocks = (long)B * nlc * ndt;
+    if (blocks > 0x7fffffffL) return RFN_ERR_SHAPE;
+    const bool vec = (D % 4 == 0) && rfn_aligned16(datt_seq) && (sb % 4 == 0) && (sl % 4 == 0);
+    const int dz_vec = rfn_aligned16(dz) && (lddz % 4 == 0) && (dz_st % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL(attn_dseq_steps_k<true>, dim3((unsigned)blocks), dim3(ATT_THREADS), lds, st, T, alpha, (long)alpha_st, dz,
+                           (long)dz_st, (long)lddz, dz_vec, L, D, datt_seq, (long)sb, (long)sl, accumulate, len, LC, nlc, ndt);
+    else
+        hipLaunchKernelGGL(attn_dseq_steps_k<false>, dim3((unsigned)blocks), dim3(ATT_THREADS), lds, st, T, alpha, (long)alpha_st, dz,
+                           (long)dz_st, (long)lddz, dz_vec, L, D, datt_seq, (long)sb, (long)sl, accumulate, len, LC, nlc, ndt);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
 // ---- backward of scores: softmax bwd + tanh bwd, writes dproj (may alias proj) -------------------
 // One block per batch row.  For each 64*W-wide chunk of A (W = 4 with 16-B accesses) every wave
 // sweeps its rows l = wave, wave+4, ... keeping the chunk's column sums (dhproj, dw) in registers;

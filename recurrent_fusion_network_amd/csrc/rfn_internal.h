@@ -26,6 +26,9 @@ int rfn_dec_attn_bwd_args(const float* proj, int64_t psb, int64_t psl, const flo
 bool rfn_dec_attn_bwd_fast_ok(const DecAttnBwdArgs& a);
 int rfn_cg_launch_with_rows(const CgPrepared& pz, const DecAttnBwdArgs& rows_args, int rows, void* stream);
 
+// the most steps one rfn_attn_context_bwd_dseq_steps call takes at feature width D (its LDS tile, rfn.h)
+int rfn_attn_dseq_steps_max_t(int D);
+
 struct AttnSmallPrepared {   // rfn_attn_small_fwd / _bwd's launch, not launched (rfn_attn.hip)
     AttnSmallArgs a;
     int B, ngroups;

@@ -243,6 +243,8 @@ const size_t STEP_GEMM_WS_FLOATS = GEMM_WS_FLOATS;   // the free-running step ma
 
 struct PrefixLayout {
     size_t P1[RFN_MAX_ENC], al1[RFN_MAX_ENC], z1[RFN_MAX_ENC], P2[RFN_MAX_ENC], dz1[RFN_MAX_ENC];
+    size_t dz1_st[RFN_MAX_ENC];   // float stride between the stage-I steps' d z slices: 0 (one buffer, reused by every step) unless
+                                  // RFN_PATH_OPT_INPUT_GRADS keeps all T1 of them for rfn_prefix_bwd_inputs
     size_t Hs, Cs, hp1, g1, rmat, rarg, h2, c2, hp2, al2, z2, g2;
     size_t dHs, dHpart, dC, dal, dwp, dhp1, dh2e, dhrec, dc2, dz2, dhp2;
     size_t gws;

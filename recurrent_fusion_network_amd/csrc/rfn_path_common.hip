@@ -219,7 +219,13 @@ PrefixLayout prefix_layout(const rfn_dims* d, int B, int train) {
         for (int i = 0; i < d->M; ++i)
             if (x3_takes(d, B, i)) L.x3p[i] = b.take(rfn_x3_image_bytes(d->T1 * d->A, B * d->L[i]) / 4 + 64);
     if (train) {
-        for (int i = 0; i < d->M; ++i) L.dz1[i] = b.take(Bz * d->D[i]);
+        // RFN_PATH_OPT_INPUT_GRADS: every step's d z is kept (slice t at dz1 + t * dz1_st, each 256-B aligned like the single
+        // buffer, so that the launches that write and read it decide their alignment cases as without the bit)
+        const bool keep_dz = (d->path_flags & RFN_PATH_OPT_INPUT_GRADS) != 0;
+        for (int i = 0; i < d->M; ++i) {
+            L.dz1_st[i] = keep_dz ? (Bz * d->D[i] + 63) & ~(size_t)63 : 0;
+            L.dz1[i] = b.take(keep_dz ? T1 * L.dz1_st[i] : Bz * d->D[i]);
+        }
         L.dHs = b.take((T1 + 1) * Bz * M * R);
         L.dHpart = b.take(M * Bz * M * R);       // small batches: the M partial products d gates_j . W_H_j of a stage-I step
         L.dC = b.take(Bz * M * R);

@@ -174,7 +174,7 @@ void Prefix::s1_attn_of(int t, S1Attn* a) const {
         a->sc_floats += a->same_ld ? (size_t)B * Li : ((size_t)B * Li + 3) & ~(size_t)3;
         a->al[i] = W + Lo.al1[i] + (long)t * B * Li;
         a->z[i] = W + Lo.z1[i] + (long)t * B * Di;
-        a->dz[i] = W + Lo.dz1[i];
+        a->dz[i] = W + Lo.dz1[i] + t * Lo.dz1_st[i];
         a->dhp[i] = W + Lo.dhp1 + ti * BA;
         a->dw[i] = dwp + ti * BA;
         a->img[i] = W + Lo.x3p[i];
@@ -497,7 +497,7 @@ int Prefix::mean_and_s1_heads_bwd(const float* d_reason) {
 // Taken while the X launch's 32-row tiles do not outnumber the CUs two to one and every product fits the cell GEMM.
 void Prefix::s1_dz_of(int t, rfn_cell_out* kz) const {   // dz_i = dgates_i . W_z[t,i], an output each
     for (int i = 0; i < M; ++i) {
-        kz[i] = cell_out(W + Lo.dz1[i], d->D[i], d->D[i], 0);
+        kz[i] = cell_out(W + Lo.dz1[i] + t * Lo.dz1_st[i], d->D[i], d->D[i], 0);
         cell_dx(kz[i], W + Lo.g1 + ((long)t * M + i) * B * 4 * R, 4 * R, prm[P.s1(t, i, 8)], d->D[i], 4 * R);
     }
 }
@@ -819,5 +819,49 @@ extern "C" int rfn_prefix_bwd_wgrad(const rfn_dims* d, int B, const float* const
         pr[t] = prob_dw(grd[P.s1(t, i, 2)], R, nullptr, W + Lo.dhp1 + ((long)t * M + i) * BA, A, Hs + t * BMR + i * R, MR, B);
     RFN_TRY(gemm_groups(A, R, T1, pr, 0, gx));
     if (parts & 2) RFN_TRY(part_b());
+    return RFN_OK;
+}
+
+// Gradients of the inputs (rfn.h): reads what rfn_prefix_bwd left in a workspace laid out with RFN_PATH_OPT_INPUT_GRADS.
+extern "C" int rfn_prefix_bwd_inputs(const rfn_dims* d, int B, const float* const* prm, float* const* d_fc, float* const* d_att,
+                                     void* ws, size_t ws_bytes, const int32_t* const* att_len, void* st) {
+    RFN_TRY(check_dims(d));
+    if (B < 1) return RFN_ERR_SHAPE;
+    if (!prm || !ws) return RFN_ERR_ARG;
+    if (!(d->path_flags & RFN_PATH_OPT_INPUT_GRADS)) return RFN_ERR_UNSUPPORTED;   // one d z buffer, overwritten by every step
+    const int M = d->M, R = d->R, A = d->A, T1 = d->T1;
+    for (int i = 0; i < M; ++i)   // dP1 exists as bf16 planes only (rfn_attn_bwd_grouped_ks): product (A) has no operand
+        if (d_att && d_att[i] && x3_dp_emitted(d, B, i)) return RFN_ERR_UNSUPPORTED;
+    const PrefixLayout Lo = prefix_layout(d, B, 1);
+    if (ws_bytes < Lo.total * sizeof(float))
+        return ws_bytes >= prefix_layout(d, B, 0).total * sizeof(float) ? RFN_ERR_UNSUPPORTED : RFN_ERR_WORKSPACE;
+    const PIdx P(d);
+    const long MR = (long)M * R;
+    float* W = (float*)ws;
+    GemmCtx gx;
+    RFN_TRY(phase_gemm(d, W, Lo.gws, Lo.tk, false, st, &gx));   // the tickets are zero: rfn_prefix_bwd left them so
+    // (C) dHs[0] holds d h0 + d c0 (s1_bwd_tail)
+    for (int i = 0; d_fc && i < M; ++i)
+        if (d_fc[i])
+            RFN_TRY(gemm1(B, d->F[i], seg_dx(W + Lo.dHs + (long)i * R, MR, prm[P.fc_w(i)], d->F[i], R), d_fc[i], d->F[i], 0, gx));
+    rfn_gemm_seg segs[64];
+    for (int i = 0; d_att && i < M; ++i) {
+        if (!d_att[i]) continue;
+        const int Li = d->L[i], Di = d->D[i];
+        const long BL = (long)B * Li;
+        // The streaming kernel OVERWRITES and the GEMM accumulates: the map is then written once by (B) and read once and
+        // written once by the GEMM epilogue.  The other order costs the same bytes only on full maps; this one also gives the
+        // padded rows of a ragged map their exact zeros for free (the kernel writes them, the GEMM adds dP1's zero rows), and
+        // the kernel never has to read a map whose every byte it replaces.
+        // (B): T1 is cut so that a call's dz rows fit the kernel's LDS tile; later calls continue the same fmaf chain.
+        const int tmax = rfn_attn_dseq_steps_max_t(Di);
+        for (int t0 = 0; t0 < T1; t0 += tmax)
+            RFN_TRY(rfn_attn_context_bwd_dseq_steps(T1 - t0 < tmax ? T1 - t0 : tmax, W + Lo.al1[i] + t0 * BL, BL,
+                                                    W + Lo.dz1[i] + t0 * Lo.dz1_st[i], (long)Lo.dz1_st[i], Di, B, Li, Di, d_att[i],
+                                                    (long)Li * Di, Di, t0 > 0, att_len ? att_len[i] : nullptr, st));
+        // (A): T1 K-segments dP1_i[t] (B * L_i, A) . W_att2att[t, i] (A, D_i)
+        for (int t = 0; t < T1; ++t) segs[t] = seg_dx(W + Lo.P1[i] + t * BL * A, A, prm[P.s1(t, i, 0)], Di, A);
+        RFN_TRY(gemm_segs((int)BL, Di, T1, segs, d_att[i], Di, 1, gx));
+    }
     return RFN_OK;
 }

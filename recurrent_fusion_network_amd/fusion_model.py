@@ -109,8 +109,11 @@ class _PrefixFn(torch.autograd.Function):
         fc = [N.require_cuda_f32(t, 'fc_feats') for t in tensors[:M]]
         att = [N.require_cuda_f32(t, 'att_feats') for t in tensors[M:2 * M]]
         params = tensors[2 * M:]
-        d = model._dims_for(drop)
         train = bool(save_bwd)
+        # a feature tensor that requires grad: the workspace keeps every stage-I step's d z (RFN_PATH_OPT_INPUT_GRADS) for
+        # rfn_prefix_bwd_inputs; the forward launches and their results are the same either way
+        input_grads = train and any(ctx.needs_input_grad[6:6 + 2 * M])
+        d = model._dims_for(drop, input_grads)
         B = fc[0].shape[0]
         dev = fc[0].device
         R, T2, K = d.R, d.T2, d.K
@@ -127,7 +130,7 @@ class _PrefixFn(torch.autograd.Function):
                                                     int(train), seed, len_ptrs, N.stream_ptr()), lens, 'rfn_prefix_fwd')
         if train:
             ctx.lens = lens
-            ctx.model, ctx.seed, ctx.M, ctx.B, ctx.drop = model, seed, M, B, drop
+            ctx.model, ctx.seed, ctx.M, ctx.B, ctx.drop, ctx.input_grads = model, seed, M, B, drop, input_grads
             ctx.fc, ctx.att, ctx.params, ctx.consumed, ctx.snapshot = fc, att, params, False, None
             # the multi-GB workspace is a SAVED tensor, not an attribute: autograd frees it right after a non-retained
             # backward instead of keeping it for as long as anything references the graph (a trainer's `loss` variable)
@@ -138,7 +141,7 @@ class _PrefixFn(torch.autograd.Function):
     def backward(ctx, d_comb, d_h, d_c, d_reason):
         model, M, B = ctx.model, ctx.M, ctx.B
         ws, = ctx.saved_tensors
-        d = model._dims_for(ctx.drop)
+        d = model._dims_for(ctx.drop, ctx.input_grads)      # the forward's flags: the workspace layout (and the recompute's)
         dev = ctx.fc[0].device
         table = model._param_table(ctx.params, model._prefix_slots)
         flats, by_slot, gtable = model._grad_buffers(model._prefix_buckets, dev)
@@ -187,7 +190,17 @@ class _PrefixFn(torch.autograd.Function):
             N.check(N.lib.rfn_prefix_bwd_wgrad(C.byref(d), B, att_ptrs, gtable, ws.data_ptr(), ws_bytes, i,
                                                part, N.stream_ptr()), 'rfn_prefix_bwd_wgrad')
             model._bucket_done('enc%d%s' % (i, tag), flats['enc%d%s' % (i, tag)])
-        return (None, None, None, None, None, None) + (None,) * (2 * M) + (None,) * len(ctx.params)
+        # gradients of the features that asked for one (rfn_prefix_bwd_inputs reads dP1, the attention rows, the d z slices
+        # and d h0 / d c0 out of the workspace; no buffer, no launch for the others)
+        d_in = [None] * (2 * M)
+        if ctx.input_grads:
+            feats = ctx.fc + ctx.att
+            for j, need in enumerate(ctx.needs_input_grad[6:6 + 2 * M]):
+                if need:
+                    d_in[j] = torch.empty_like(feats[j])
+            N.check(N.lib.rfn_prefix_bwd_inputs(C.byref(d), B, table, N.ptr_array(d_in[:M]), N.ptr_array(d_in[M:]), ws.data_ptr(),
+                                                ws_bytes, len_ptrs, N.stream_ptr()), 'rfn_prefix_bwd_inputs')
+        return (None, None, None, None, None, None) + tuple(d_in) + (None,) * len(ctx.params)
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -514,14 +527,17 @@ class RecurrentFusionModel(nn.Module):
         arr = (C.c_void_p * len(events))(*[int(e.cuda_event) for e in events])
         self._probe = (arr, list(events))
 
-    def _dims_for(self, train: bool) -> N.Dims:
-        d = self._dims_cached(train)
+    def _dims_for(self, train: bool, input_grads: bool = False) -> N.Dims:
+        """`input_grads`: phase 1 of a pass whose fc_feats / att_feats require grad (RFN_PATH_OPT_INPUT_GRADS)."""
+        d = self._dims_cached(train, input_grads)
         probe = getattr(self, '_probe', None)
         d.probe_events = C.cast(probe[0], C.c_void_p) if probe is not None else None
         return d
 
-    def _dims_cached(self, train: bool) -> N.Dims:
+    def _dims_cached(self, train: bool, input_grads: bool = False) -> N.Dims:
         path_flags = int(self.path_flags) | (N.PATH_OPT_SEED_DEV if getattr(self, '_seed_dev', None) is not None else 0)
+        if input_grads:
+            path_flags |= N.PATH_OPT_INPUT_GRADS
         key = (bool(train), int(self.gemm_flags), path_flags)
         if key not in self._dims:
             self._dims[key] = N.make_dims(
@@ -655,6 +671,11 @@ class RecurrentFusionModel(nn.Module):
         B = self._check_inputs(fc_feats, att_feats)
         params = self._params_of(self._prefix_slots)
         lens = self._att_lens(att_lens, B, fc_feats[0].device)
+        if (torch.is_grad_enabled() and int(self.gemm_flags) & N.GEMM_OPT_BF16X3
+                and any(t.requires_grad for t in list(fc_feats) + list(att_feats))):
+            raise N.RfnError('feature gradients: gemm_flags selects RFN_GEMM_OPT_BF16X3, whose attention backward may leave the '
+                             'projection gradients as bf16 planes only (rfn_attn_bwd_grouped_ks); fc_feats / att_feats that '
+                             'require grad need the exact-f32 path')
         cacheable = self.reuse_prefix and not (drop and (self.drop_prob_fusion > 0 or self.drop_prob_reason > 0)) and lens is None
         if cacheable:
             ins = list(fc_feats) + list(att_feats)
@@ -840,6 +861,54 @@ class RecurrentFusionModel(nn.Module):
                 break
         self._steps_cache = (key, seq, S)     # holds `seq` so its storage cannot be recycled under the key
         return S
+
+    def saliency(self, fc_feats, att_feats, seq, masks=None, att_lens=None, mode='grad_x_input'):
+        """Which regions does a caption rest on: the gradient of each caption's log-likelihood with respect to the attention
+        maps (INTEGRATION.md "Input gradients").  Per caption s_b = sum_t mask[b, t] * log p(seq[b, t + 1] | seq[b, :t + 1])
+        through `forward`, differentiated with backward(ones), so row b of every result belongs to caption b alone.
+        -> a list of M tensors: (B, L_i) maps -- sum_d grad * att_feats ('grad_x_input') or the L2 norm of each region's
+        gradient ('grad_norm') -- or the (B, L_i, D_i) gradients themselves ('raw').
+        masks: (B, >= S + 1) as the criterion takes them (column t + 1 weighs target seq[:, t + 1]); None: every target up to and
+        including the caption's first END (0).  The model runs in the mode it is in: call it under eval() unless the dropout
+        masks are wanted in the gradient.
+        The path's backward hands parameter gradients over by assigning `.grad` (not through autograd's return values), so this
+        method SAVES every parameter's `.grad` (and the flat-buffer registry and the grad_ready_hook) before the pass and
+        RESTORES them after it: `.grad` tensors are the same objects with the same values as before the call, None stays
+        None, and no hook fires."""
+        if mode not in ('grad_x_input', 'grad_norm', 'raw'):
+            raise ValueError("saliency: mode must be 'grad_x_input', 'grad_norm' or 'raw', got %r" % (mode,))
+        att = [a.detach().requires_grad_(True) for a in att_feats]
+        fc = [f.detach() for f in fc_feats]
+        params = list(self.parameters())
+        kept = ([p.grad for p in params], dict(self._last_flat_grads), self.grad_ready_hook)
+        self.grad_ready_hook, self._last_flat_grads = None, {}
+        for p in params:      # the pass starts from no gradients: nothing it produces is added INTO a buffer the caller holds
+            p.grad = None
+        try:
+            with torch.enable_grad():
+                log_prob, _ = self.forward(fc, att, seq, att_lens=att_lens)
+                S = min(log_prob.size(1), seq.size(1) - 1)
+                tgt = seq[:, 1:S + 1].to(log_prob.device).long()
+                lp = log_prob[:, :S].gather(2, tgt.unsqueeze(2)).squeeze(2)
+                if masks is None:
+                    ended = (tgt == 0).long()
+                    m = ((ended.cumsum(1) - ended) == 0).to(lp.dtype)
+                else:
+                    if masks.size(1) < S + 1:
+                        raise N.RfnError('saliency: masks need %d columns for %d decoder steps' % (S + 1, S))
+                    m = masks[:, 1:S + 1].to(lp.device).to(lp.dtype)
+                s = (lp * m).sum(1)
+                grads = torch.autograd.grad(s, att, grad_outputs=torch.ones_like(s))
+        finally:
+            for p, g in zip(params, kept[0]):
+                p.grad = g
+            self._last_flat_grads = kept[1]
+            self.grad_ready_hook = kept[2]
+        if mode == 'raw':
+            return list(grads)
+        if mode == 'grad_norm':
+            return [g.norm(dim=2) for g in grads]
+        return [(g * a.detach()).sum(2) for g, a in zip(grads, att)]
 
     def get_init_state(self, fc_feats):
         """misc/RecurrentFusionModel.py:333-343 (inference helper, no autograd)."""

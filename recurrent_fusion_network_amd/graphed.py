@@ -45,10 +45,20 @@ def _refuse_att_lens(att_lens):
                          'att_feats buffers (ragged attention maps run through model.forward_loss, uncaptured)')
 
 
+def _refuse_feature_grads(fc_feats, att_feats):
+    for name, feats in (('fc_feats', fc_feats), ('att_feats', att_feats)):
+        for i, t in enumerate(feats or ()):
+            if t.requires_grad:
+                raise N.RfnError('GraphedTrainStep: %s[%d] requires grad; the captured step copies its batch into static buffers '
+                                 'and produces no feature gradients (encoder fine-tuning and saliency run through '
+                                 'model.forward / forward_loss, uncaptured)' % (name, i))
+
+
 class GraphedTrainStep:
     def __init__(self, model, crit, opt, fc_feats, att_feats, labels, masks, top_words, reason_weight=1.0, warmup=3,
                  full_length=True, device_rng=False, att_lens=None):
         _refuse_att_lens(att_lens)
+        _refuse_feature_grads(fc_feats, att_feats)
         self.model, self.crit, self.opt, self.reason_weight = model, crit, opt, float(reason_weight)
         self.device_rng = bool(device_rng)
         self._check_capturable()
@@ -148,6 +158,7 @@ class GraphedTrainStep:
         """Replays the captured step on the given batch (None: the batch already in the static buffers) -> the loss tensor
         (a static buffer: read it before the next call)."""
         _refuse_att_lens(att_lens)
+        _refuse_feature_grads(fc_feats, att_feats)
         self._check_capturable()
         now = self._frozen_state()
         if now != self.frozen:
