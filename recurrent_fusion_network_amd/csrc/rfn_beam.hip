@@ -13,63 +13,10 @@
 // Nothing is read back per step; the host sorts the (few) done beams once at the end.
 // The diverse search (beam groups with a Hamming penalty, which the reference does not have) is the second kernel below, the
 // lexically constrained search (required words: one beam per subset of satisfied sets) the third.
-#include "rfn_rows.h"
+#include "rfn_beam_step.h"   // BEAM_MAX_W / BEAM_MAX_S and the scaffolding shared with rfn_sbs.hip; rfn_rows.h through it
 
-#define BEAM_MAX_W 32     /* beams per image; the full-row form (rfn_beam_step: phase 1 below) serves up to BEAM_WAVES of them */
-#define BEAM_MAX_S 64     /* decode steps a block keeps the beams' histories for (seq_length) */
 #define BEAM_THREADS 1024
 #define BEAM_WAVES 16
-
-// Phase 2b of a step (all threads of the block): the forked columns and the done beams of the beams b0 .. b0+nb-1 of image k
-// (the whole image, or one group of a diverse search).  sel_ci[vix] is the candidate that becomes beam b0 + vix (vix < nnew),
-// cand_q its source beam within the image, slot_s[vix] its done slot or -1; prev_* is the snapshot of the image's beams before
-// the step.  Needs nthr >= nb.
-__device__ __forceinline__ void beam_fork_write(int k, int tid, int nthr, int W, int b0, int nb, int nnew, int S, int t, int NB,
-                                                int MAXD, int64_t* __restrict__ bs, float* __restrict__ bl,
-                                                float* __restrict__ bsum, int32_t* __restrict__ order, int64_t* __restrict__ nxt,
-                                                int64_t* __restrict__ done_seq, float* __restrict__ done_lp,
-                                                const int (*prev_seq)[BEAM_MAX_W], const float (*prev_lp)[BEAM_MAX_W],
-                                                const float* cand_p, const float* cand_r, const int* cand_c, const int* cand_q,
-                                                const int* sel_ci, const int* slot_s) {
-    for (int i = tid; i < nnew * S; i += nthr) {
-        const int vix = i / S, s = i - vix * S;
-        const int ci = sel_ci[vix], qq = cand_q[ci];
-        int64_t tok;
-        float lp;
-        const long at = ((long)s * NB + k) * W + b0 + vix;
-        if (s < t - 1) {
-            tok = prev_seq[s][qq];
-            lp = prev_lp[s][qq];
-            bs[at] = tok;
-            bl[at] = lp;
-        } else if (s == t - 1) {
-            tok = cand_c[ci];
-            lp = cand_r[ci];
-            bs[at] = tok;
-            bl[at] = lp;
-        } else {  // columns this search has not reached yet (still the initial zeros)
-            tok = bs[at];
-            lp = bl[at];
-        }
-        const int slot = slot_s[vix];
-        if (slot >= 0) {
-            done_seq[((long)k * MAXD + slot) * S + s] = tok;
-            done_lp[((long)k * MAXD + slot) * S + s] = lp;
-        }
-    }
-    if (tid < nb) {
-        const int vix = tid, row = k * W + b0 + vix;
-        if (vix < nnew) {
-            const int ci = sel_ci[vix];
-            order[row] = k * W + cand_q[ci];
-            nxt[row] = cand_c[ci];
-            bsum[row] = cand_p[ci];                  // every read of these beams' bsum happened before the caller's barrier
-        } else {  // keeps its previous state and tokens (new_state = clone(state), :485)
-            order[row] = row;
-            nxt[row] = bs[((long)(t - 1) * NB + k) * W + b0 + vix];
-        }
-    }
-}
 
 // One block per image.  Phase 1: top `cols` columns of every live beam row -- each row is cut over 16 / rows waves,
 // every lane keeps a sorted top-LW list of its strided share in registers (one pass over the row), the wave merges
@@ -97,13 +44,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
     __shared__ int nnew_s;
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cols = min(W, V1);
-    if (!active[k]) {  // this image's search has ended: keep its rows inert
-        if (tid < W) {
-            order[k * W + tid] = k * W + tid;
-            nxt[k * W + tid] = 0;
-        }
-        return;
-    }
+    if (!active[k]) return beam_rows_inert(order, nxt, k, W, 0, W, tid);   // this image's search has ended
     // ---- phase 1: top `cols` of every live beam row (descending, lowest index first on ties) -----------------
     const int live_rows = (t == 1) ? 1 : W;
     const int wpr = topv ? 1 : BEAM_WAVES / live_rows;   // waves per row (full-row form: >= 1, the host checks W <= BEAM_WAVES)
@@ -127,19 +68,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
             }
         }
     }
-    // ---- snapshot of the beams before this step (forks read the OLD columns, :488-489) ----------------------
-    for (int i = tid; i < (t - 1) * W; i += (int)blockDim.x) {
-        const int s = i / W, w = i - s * W;
-        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
-        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
-    }
+    beam_snapshot(prev_seq, prev_lp, bs, bl, k, W, NB, t, tid, (int)blockDim.x);
     __syncthreads();
     if (topv) {
-        for (int i = tid; i < live_rows * cols; i += (int)blockDim.x) {
-            const int qq = i / cols, c = i - qq * cols;
-            ys[qq][c] = topv[(long)(k * W + qq) * W + c];
-            ix[qq][c] = topi[(long)(k * W + qq) * W + c];
-        }
+        beam_load_lists(ys, ix, topv, topi, k, W, live_rows, cols, tid, (int)blockDim.x);
     } else if (tid < live_rows) {                    // merge the row's wave lists (each already sorted)
         int pos[BEAM_WAVES];
         for (int p = 0; p < wpr; ++p) pos[p] = 0;
@@ -190,24 +122,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_k(
             if (vix >= nnew) continue;
             const int ci = cand_ord[vix];
             sel_ci[vix] = ci;
-            if ((cand_c[ci] == 0 || t == S) && n < MAXD) {  // :508-514, appended in construction order
-                slot_s[vix] = n;
-                done_p[(long)k * MAXD + n] = cand_p[ci];
-                ++n;
-            }
+            slot_s[vix] = beam_take_done_slot(cand_c[ci], cand_p[ci], t, S, k, MAXD, n, done_p);
         }
         done_n[k] = n;
         nnew_s = (nc == 0) ? -1 : nnew;
     }
     __syncthreads();
     const int nnew = nnew_s;
-    if (nnew < 0) {  // no candidate left: the image stops, its rows stay inert
-        if (tid < W) {
-            order[k * W + tid] = k * W + tid;
-            nxt[k * W + tid] = 0;
-        }
-        return;
-    }
+    if (nnew < 0) return beam_rows_inert(order, nxt, k, W, 0, W, tid);   // no candidate left: the image stops
     beam_fork_write(k, tid, (int)blockDim.x, W, 0, W, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp, prev_seq,
                     prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
 }
@@ -289,23 +211,9 @@ __global__ __launch_bounds__(BEAM_DIV_THREADS) void beam_step_div_k(
     __shared__ int nl_s, npen_s;
     const int k = blockIdx.x, tid = threadIdx.x;
     const int cols = min(W, V1), Wg = W / G;
-    if (!active[k]) {  // this image's search has ended: keep its rows inert
-        if (tid < W) {
-            order[k * W + tid] = k * W + tid;
-            nxt[k * W + tid] = 0;
-        }
-        return;
-    }
-    for (int i = tid; i < W * cols; i += BEAM_DIV_THREADS) {
-        const int q = i / cols, c = i - q * cols;
-        ys[q][c] = topv[(long)(k * W + q) * W + c];
-        ix[q][c] = topi[(long)(k * W + q) * W + c];
-    }
-    for (int i = tid; i < (t - 1) * W; i += BEAM_DIV_THREADS) {  // the beams before this step (forks read the OLD columns)
-        const int s = i / W, w = i - s * W;
-        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
-        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
-    }
+    if (!active[k]) return beam_rows_inert(order, nxt, k, W, 0, W, tid);   // this image's search has ended
+    beam_load_lists(ys, ix, topv, topi, k, W, W, cols, tid, BEAM_DIV_THREADS);
+    beam_snapshot(prev_seq, prev_lp, bs, bl, k, W, NB, t, tid, BEAM_DIV_THREADS);
     __syncthreads();
     int npen = 0, n = 0, any = 0;                    // thread 0's: penalised tokens so far, done beams so far, a group had a candidate
     if (tid == 0) n = done_n[k];
@@ -340,11 +248,10 @@ __global__ __launch_bounds__(BEAM_DIV_THREADS) void beam_step_div_k(
         __syncthreads();
         for (int i = tid; i < nc; i += BEAM_DIV_THREADS) {
             const float ki = cand_key[i];
-            int rank = 0;
-            for (int j = 0; j < nc && rank < Wg; ++j) {
+            const int rank = beam_rank(nc, Wg, i, [](int) { return true; }, [&](int j, int me) {
                 const float kj = cand_key[j];
-                rank += (kj > ki) || (kj == ki && j < i);
-            }
+                return (kj > ki) || (kj == ki && j < me);
+            });
             if (rank < Wg) sel_ci[rank] = i;
         }
         __syncthreads();
@@ -354,22 +261,16 @@ __global__ __launch_bounds__(BEAM_DIV_THREADS) void beam_step_div_k(
                 slot_s[vix] = -1;
                 if (vix >= nnew) continue;
                 const int ci = sel_ci[vix], tok = cand_c[ci];
-                if ((tok == 0 || t == S) && n < MAXD) {  // appended in construction order: group, then vix
-                    slot_s[vix] = n;
-                    done_p[(long)k * MAXD + n] = cand_p[ci];
-                    done_group[(long)k * MAXD + n] = g;
-                    ++n;
-                }
+                const int slot = beam_take_done_slot(tok, cand_p[ci], t, S, k, MAXD, n, done_p);   // in order: group, then vix
+                slot_s[vix] = slot;
+                if (slot >= 0) done_group[(long)k * MAXD + slot] = g;
                 if (tok != 0) pen_tok[npen++] = tok;     // END is never counted
             }
             any |= nc > 0;
         }
         __syncthreads();
-        if (nc == 0) {  // no candidate left: the group's rows stay inert
-            if (tid < Wg) {
-                order[k * W + b0 + tid] = k * W + b0 + tid;
-                nxt[k * W + b0 + tid] = 0;
-            }
+        if (nc == 0) {  // no candidate left for the group
+            beam_rows_inert(order, nxt, k, W, b0, Wg, tid);
         } else {
             beam_fork_write(k, tid, BEAM_DIV_THREADS, W, b0, Wg, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp,
                             prev_seq, prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
@@ -439,18 +340,8 @@ __global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
     __shared__ int nvalid_s, first_s, nnew_s;
     const int k = blockIdx.x, tid = threadIdx.x;
     const int G = 1 << C, Wb = W / G, cols = min(W, V1);
-    if (!active[k]) {  // this image's search has ended: keep its rows inert
-        if (tid < W) {
-            order[k * W + tid] = k * W + tid;
-            nxt[k * W + tid] = 0;
-        }
-        return;
-    }
-    for (int i = tid; i < W * cols; i += BEAM_LEX_THREADS) {
-        const int q = i / cols, c = i - q * cols;
-        ys[q][c] = topv[(long)(k * W + q) * W + c];
-        ix[q][c] = topi[(long)(k * W + q) * W + c];
-    }
+    if (!active[k]) return beam_rows_inert(order, nxt, k, W, 0, W, tid);   // this image's search has ended
+    beam_load_lists(ys, ix, topv, topi, k, W, W, cols, tid, BEAM_LEX_THREADS);
     for (int i = tid; i < W * NW; i += BEAM_LEX_THREADS) {
         const int q = i / NW, j = i - q * NW;
         wv[q][j] = wantv[(long)(k * W + q) * NW + j];
@@ -460,11 +351,7 @@ __global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
         wid[tid] = id;
         wb[tid] = (id >= 1 && id < V1) ? (want_bits[k * NW + tid] & (G - 1)) : 0;
     }
-    for (int i = tid; i < (t - 1) * W; i += BEAM_LEX_THREADS) {  // the beams before this step (forks read the OLD columns)
-        const int s = i / W, w = i - s * W;
-        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
-        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
-    }
+    beam_snapshot(prev_seq, prev_lp, bs, bl, k, W, NB, t, tid, BEAM_LEX_THREADS);
     if (tid < W) prev_sum[tid] = bsum[k * W + tid];
     if (tid < G) {   // before step 1 only the first row of the initial state is occupied
         int n = (t == 1) ? (tid == (init_state[k] & (G - 1)) ? 1 : 0) : state_n[k * G + tid];
@@ -526,11 +413,10 @@ __global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
         for (int i = tid; i < total; i += BEAM_LEX_THREADS) {
             if (cand_q[i] < 0) continue;
             const float pi = cand_p[i];
-            int rank = 0;
-            for (int j = 0; j < total && rank < Wb; ++j) {
+            const int rank = beam_rank(total, Wb, i, [&](int j) { return cand_q[j] >= 0; }, [&](int j, int me) {
                 const float pj = cand_p[j];
-                rank += (cand_q[j] >= 0) && ((pj > pi) || (pj == pi && j < i));
-            }
+                return (pj > pi) || (pj == pi && j < me);
+            });
             if (rank < Wb) sel_ci[rank] = i;
         }
         __syncthreads();
@@ -541,12 +427,9 @@ __global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
                 if (vix >= nnew) continue;
                 if (sel_ci[vix] < 0) sel_ci[vix] = first_s;   // only under NaN keys: stay on a valid slot
                 const int ci = sel_ci[vix];
-                if ((cand_c[ci] == 0 || t == S) && n < MAXD) {  // appended in construction order: state, then rank
-                    slot_s[vix] = n;
-                    done_p[(long)k * MAXD + n] = cand_p[ci];
-                    done_state[(long)k * MAXD + n] = s;
-                    ++n;
-                }
+                const int slot = beam_take_done_slot(cand_c[ci], cand_p[ci], t, S, k, MAXD, n, done_p);   // in order: state, then rank
+                slot_s[vix] = slot;
+                if (slot >= 0) done_state[(long)k * MAXD + slot] = s;
             }
             state_n[k * G + s] = nnew;
             any |= nvalid > 0;
@@ -556,11 +439,8 @@ __global__ __launch_bounds__(BEAM_LEX_THREADS) void beam_step_lex_k(
         const int nnew = nnew_s;
         beam_fork_write(k, tid, BEAM_LEX_THREADS, W, b0, nnew, nnew, S, t, NB, MAXD, bs, bl, bsum, order, nxt, done_seq, done_lp,
                         prev_seq, prev_lp, cand_p, cand_r, cand_c, cand_q, sel_ci, slot_s);
-        if (tid >= nnew && tid < Wb) {               // the state's unoccupied rows: inert, nothing stale is kept
-            order[k * W + b0 + tid] = k * W + b0 + tid;
-            nxt[k * W + b0 + tid] = 0;
-        }
-        __syncthreads();                             // the next state reuses the candidate arrays
+        beam_rows_inert(order, nxt, k, W, b0 + nnew, Wb - nnew, tid);   // the state's unoccupied rows: nothing stale is kept
+        __syncthreads();                            // the next state reuses the candidate arrays
     }
     if (tid == 0) {
         done_n[k] = n;

@@ -46,8 +46,7 @@ extern "C" int rfn_log_softmax_fwd(const float* logits, int64_t ldl, int rows, i
 // sample_beam only ever looks at the W best log-probs of a beam row (misc/RecurrentFusionModel.py:463-466: a full sort, of
 // which columns 0 .. beam_size-1 are read).  topv[r, c] / topi[r, c], c < W: the c-th largest log-prob of row r and its
 // token, ordered (value descending, token ascending) -- the order the reference's descending sort lists them -- computed
-// from the same log-prob bits rfn_log_softmax_fwd writes.  W <= 32.
-#define LSM_TOPW 32
+// from the same log-prob bits rfn_log_softmax_fwd writes.  W <= LSM_TOPW (rfn_rows.h).
 // MASK (rfn_log_softmax_topk_masked): the row's block list (blk[r, :blk_n[r]], duplicates allowed) becomes a bit per token in
 // LDS; the log-sum-exp above it is still taken over ALL logits, and a blocked token then enters the selection as -inf, so the
 // list is the one a stable descending sort of the masked log-prob row gives (short rows are filled with the lowest -inf ids).
@@ -78,14 +77,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
     const float lse = log_softmax_row<VEC>(x, V1, xr, red);
     const int cols = min(W, V1);
     if constexpr (MASK) {
-        for (int i = threadIdx.x; i < (V1 + 31) / 32; i += 256) lsm_bits[i] = 0u;
-        __syncthreads();
-        const int nb = blk_n[r];
-        for (int i = threadIdx.x; i < nb; i += 256) {
-            const int id = blk[r * ld_blk + i];
-            if (id >= 0 && id < V1) atomicOr(&lsm_bits[id >> 5], 1u << (id & 31));
-        }
-        __syncthreads();
+        row_mask_build(lsm_bits, V1, blk, ld_blk, blk_n, r);
         if constexpr (VEC) {
 #pragma unroll
             for (int j = 0; j < LSM_R4; ++j) {
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
             float lp = -INFINITY;
             if (id >= 0 && id < V1) {
                 bool blocked = false;
-                if constexpr (MASK) blocked = (lsm_bits[id >> 5] >> (id & 31)) & 1u;
+                if constexpr (MASK) blocked = row_mask_has(lsm_bits, id);
                 if (!blocked) lp = x[id] - lse;
             }
             wt.wantv[(long)r * wt.NW + threadIdx.x] = lp;
@@ -114,7 +106,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_k(const float* __restric
     // the logit of token v as the selection sees it (the non-VEC form re-reads the row)
     auto xat = [&](int v) {
         if constexpr (MASK) {
-            if ((lsm_bits[v >> 5] >> (v & 31)) & 1u) return -INFINITY;
+            if (row_mask_has(lsm_bits, v)) return -INFINITY;
         }
         return x[v];
     };
@@ -216,33 +208,19 @@ static int log_softmax_topk_launch(const float* logits, int64_t ldl, int rows, i
                                    const int32_t* blk_n, float* topv, int32_t* topi, void* stream,
                                    const int32_t* want = nullptr, int64_t ld_want = 0, int NW = 0, int row_div = 1,
                                    float* wantv = nullptr) {
-    if (rows <= 0 || V1 <= 0 || W < 1 || W > LSM_TOPW) return RFN_ERR_SHAPE;
-    if (!logits || !topv || !topi) return RFN_ERR_ARG;
-    if (blk && (!blk_n || ld_blk < 1)) return RFN_ERR_ARG;
-    const size_t bits = blk ? (size_t)((V1 + 31) / 32) * sizeof(unsigned) : 0;
-    if (bits > 48 * 1024) return RFN_ERR_SHAPE;     // one bit per token in LDS
+    size_t bits;
+    RFN_TRY(lsm_topk_check(rows, V1, W, logits && topv && topi, blk, ld_blk, blk_n, &bits));
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0);
-#define LSM_LAUNCH3(VECV, LWV, MASKV)                                                                                       \
-    do {                                                                                                                    \
-        if (want)                                                                                                           \
-            hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV, true>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, \
-                               V1, W, topv, topi, blk, (long)ld_blk, blk_n, LsmWant{want, (long)ld_want, NW, row_div, wantv});  \
-        else                                                                                                                \
-            hipLaunchKernelGGL((log_softmax_topk_k<VECV, LWV, MASKV>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, \
-                               W, topv, topi, blk, (long)ld_blk, blk_n, LsmNoWant{});                                       \
-    } while (0)
-#define LSM_LAUNCH(VECV, LWV)                                                                                               \
-    do {                                                                                                                    \
-        if (blk) LSM_LAUNCH3(VECV, LWV, true);                                                                              \
-        else LSM_LAUNCH3(VECV, LWV, false);                                                                                 \
-    } while (0)
-    if (W <= 4) { if (vec) LSM_LAUNCH(true, 4); else LSM_LAUNCH(false, 4); }
-    else if (W <= 8) { if (vec) LSM_LAUNCH(true, 8); else LSM_LAUNCH(false, 8); }
-    else if (W <= 16) { if (vec) LSM_LAUNCH(true, 16); else LSM_LAUNCH(false, 16); }
-    else { if (vec) LSM_LAUNCH(true, 32); else LSM_LAUNCH(false, 32); }
-#undef LSM_LAUNCH
-#undef LSM_LAUNCH3
+    lsm_topk_dispatch(lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0), W, blk != nullptr, [&](auto vec, auto lw, auto mask) {
+        constexpr bool VEC = decltype(vec)::value, MASK = decltype(mask)::value;
+        constexpr int LW = decltype(lw)::value;
+        if (want)
+            hipLaunchKernelGGL((log_softmax_topk_k<VEC, LW, MASK, true>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, W,
+                               topv, topi, blk, (long)ld_blk, blk_n, LsmWant{want, (long)ld_want, NW, row_div, wantv});
+        else
+            hipLaunchKernelGGL((log_softmax_topk_k<VEC, LW, MASK>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, W, topv,
+                               topi, blk, (long)ld_blk, blk_n, LsmNoWant{});
+    });
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

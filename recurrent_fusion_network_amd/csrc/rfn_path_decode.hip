@@ -1,6 +1,7 @@
 // The free-running decoder: one step on caller-held state (sample / beam / one_time_step) and the whole decode loops queued by
 // one call.  Every step is the cell of the teacher-forced pass (decoder_cell_core, rfn_path_decoder.hip).
 #include "rfn_path.h"
+#include "rfn_beam_step.h"   // BEAM_MAX_W / BEAM_MAX_S: the limits of the beam-step kernels
 
 // =============================================================================================
 // free-running decoder step (sample / beam / one_time_step)
@@ -40,13 +41,27 @@ extern "C" int rfn_decoder_prepare(const rfn_dims* d, int B, const float* const*
 // h2h + z2h accumulated onto it, same split-K scratch size, same dropout stream (seed, OFF_DECODER + step)), so the
 // distribution a host samples from here IS the one the teacher-forced gradient pass differentiates
 // (misc/RecurrentFusionModel.py:260-270, 623-631: the reference samples from the dropout-affected outputs themselves).
+//
+// StepLists: what the step hands to a search that drives it, beyond logits / logp.  The default is "no lists" (rfn_decoder_step).
+struct StepLists {
+    float* topv = nullptr;                      // the rows' W best log-probs and their tokens, no full rows (rfn_log_softmax_topk*)
+    int32_t* topi = nullptr;
+    int W = 0;
+    int row_div = 1;                            // rows that read one thought vector (comb / cproj hold B / row_div of them)
+    const int32_t* blk = nullptr;               // decoding constraints: the rows' block lists mask the lists
+    int64_t ld_blk = 0;
+    const int32_t* blk_n = nullptr;
+    const int32_t* want = nullptr;              // lexical search: the image's n_want required ids, whose log-probs go to wantv
+    int n_want = 0;
+    float* wantv = nullptr;
+    const rfn_beam_stochastic* sbs = nullptr;   // stochastic search: the W best Gumbel-perturbed entries of the live rows,
+    uint64_t sbs_offset = 0;                    // with the noise of (sbs->seed, sbs_offset)
+};
 static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, const float* comb, const float* cproj,
                              const int64_t* ids, const float* xt, int64_t ld_xt, float* h, float* c, float* logits,
                              float* logp, int64_t ld_logp, void* ws, size_t ws_bytes, uint64_t seed_arg, int step,
-                             void* st, float* topv = nullptr, int32_t* topi = nullptr, int topw = 0, int row_div = 1,
-                             const int32_t* blk = nullptr, int64_t ld_blk = 0, const int32_t* blk_n = nullptr,
-                             const int32_t* want = nullptr, int n_want = 0, float* wantv = nullptr,
-                             const rfn_beam_stochastic* sbs = nullptr, uint64_t sbs_offset = 0) {
+                             void* st, const StepLists& ls = {}) {
+    const int row_div = ls.row_div;
     RFN_TRY(check_dims(d));
     RfnSeed seed;
     RFN_TRY(path_seed(d, seed_arg, &seed));
@@ -72,22 +87,20 @@ static int decoder_step_impl(const rfn_dims* d, int B, const float* const* prm, 
                   g, GD, 0, gx_whole));
     RFN_TRY(decoder_cell_core(d, B, prm, comb, cproj, cproj + cproj_u_off(d, B / row_div), row_div, h, c, h, c, hp, al, z, g, gx,
                               seed, step, st));
-    if (logits || logp || topv) {
+    if (logits || logp || ls.topv) {
         RFN_TRY(gemm_logits(B, V1, h, R, prm[P.logit_w()], prm[P.logit_b()], lg, gx_whole));
         if (logp) {
             if (ld_logp < V1) return RFN_ERR_SHAPE;
             RFN_TRY(rfn_log_softmax_fwd(lg, V1, B, V1, B, ld_logp, 0, logp, st));
         }
-        // beam search: W best per row, no full rows (blk: of the rows masked by their block lists)
-        // (want: plus the log-probs of the image's required tokens, for the lexically constrained search)
-        // (sbs: the W best Gumbel-perturbed entries of the live rows, for the stochastic search)
-        if (topv && sbs)
-            RFN_TRY(rfn_log_softmax_topk_gumbel(lg, V1, B, V1, topw, blk, ld_blk, blk_n, sbs->live, sbs->seed, sbs_offset, sbs->topk64,
-                                                topv, topi, st));
-        else if (topv && want)
-            RFN_TRY(rfn_log_softmax_topk_want(lg, V1, B, V1, topw, row_div, want, n_want, n_want, blk, ld_blk, blk_n, topv, topi, wantv,
-                                              st));
-        else if (topv) RFN_TRY(rfn_log_softmax_topk_masked(lg, V1, B, V1, topw, blk, ld_blk, blk_n, topv, topi, st));
+        if (ls.topv && ls.sbs)
+            RFN_TRY(rfn_log_softmax_topk_gumbel(lg, V1, B, V1, ls.W, ls.blk, ls.ld_blk, ls.blk_n, ls.sbs->live, ls.sbs->seed,
+                                                ls.sbs_offset, ls.sbs->topk64, ls.topv, ls.topi, st));
+        else if (ls.topv && ls.want)
+            RFN_TRY(rfn_log_softmax_topk_want(lg, V1, B, V1, ls.W, row_div, ls.want, ls.n_want, ls.n_want, ls.blk, ls.ld_blk, ls.blk_n,
+                                              ls.topv, ls.topi, ls.wantv, st));
+        else if (ls.topv)
+            RFN_TRY(rfn_log_softmax_topk_masked(lg, V1, B, V1, ls.W, ls.blk, ls.ld_blk, ls.blk_n, ls.topv, ls.topi, st));
     }
     return RFN_OK;
 }
@@ -146,6 +159,8 @@ extern "C" int rfn_decoder_loop_ex2(const rfn_dims* d, int B, int steps, const f
     if (n_img > 1 && !dec_hoisted(d)) return RFN_ERR_UNSUPPORTED;   // the three-launch cell reads comb per row
     if (trunc && (!(samp->top_p > 0.f) || !(inv_temperature > 0.f))) return RFN_ERR_SHAPE;
     if (hipMemsetAsync(ids, 0, (size_t)B * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;   // BOS
+    StepLists ls;
+    ls.row_div = n_img;   // n_img = 1: rfn_decoder_step
     for (int t = 0; t < steps; ++t) {
         if (t >= 1) {
             float* prev = logp_all + (long)(t - 1) * ld_t;
@@ -161,7 +176,7 @@ extern "C" int rfn_decoder_loop_ex2(const rfn_dims* d, int B, int steps, const f
                                     ld_lp, t > 1 ? unf + (long)(t - 1) * B : nullptr, unf + (long)t * B, st));
         }
         RFN_TRY(decoder_step_impl(d, B, prm, comb, cproj, ids, nullptr, 0, h, c, nullptr, logp_all + (long)t * ld_t, ld_b, ws,
-                                  ws_bytes, seed, t, st, nullptr, nullptr, 0, n_img));   // n_img = 1: rfn_decoder_step
+                                  ws_bytes, seed, t, st, ls));
     }
     return RFN_OK;
 }
@@ -213,6 +228,39 @@ extern "C" int rfn_decoder_fwd_sampled(const rfn_dims* d, int B, int S, const fl
                                       ws_bytes, train, seed, 1, st);
 }
 
+// one group is the plain search, with the same launches
+static bool beam_diverse(const rfn_beam_diversity* div) { return div && div->groups > 1; }
+// rfn_beam_loop_ex4's refusals, in the order tests/test_native_abi.py pins.  ptrs_ok: every buffer all four searches need is there.
+static int check_beam_loop(const rfn_dims* d, int NB, int W, int S, bool ptrs_ok, uint64_t seed, const int64_t* beam_seq,
+                           const float* beam_lp, const rfn_decode_constraints* cons, const rfn_beam_diversity* div,
+                           const rfn_beam_lexical* lex, const rfn_beam_stochastic* sbs) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed_checked;
+    RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps resolve it again
+    if (NB < 1 || W < 1 || S < 1) return RFN_ERR_SHAPE;
+    if (!ptrs_ok) return RFN_ERR_ARG;
+    if (W > BEAM_MAX_W) return RFN_ERR_SHAPE;
+    RFN_TRY(check_constraints(cons, S));
+    if (cons && !beam_seq) return RFN_ERR_ARG;
+    if (div && (div->groups < 1 || W % div->groups || !(div->lambda >= 0.f))) return RFN_ERR_SHAPE;
+    const bool diverse = beam_diverse(div);
+    if (diverse && !div->done_group) return RFN_ERR_ARG;
+    if (lex) {
+        if (diverse) return RFN_ERR_UNSUPPORTED;
+        const int C = lex->n_sets, NW = lex->n_want;
+        if (C < 1 || C > RFN_LEX_MAX_SETS || W % (1 << C) || NW < 1 || NW > RFN_LEX_MAX_IDS || NW > W - W / (1 << C) || S > BEAM_MAX_S)
+            return RFN_ERR_SHAPE;
+        if (!lex->want || !lex->want_bits || !lex->init_state || !lex->wantv || !lex->state_n || !lex->done_state || !beam_seq)
+            return RFN_ERR_ARG;
+    }
+    if (sbs) {
+        if (diverse || lex) return RFN_ERR_UNSUPPORTED;
+        if (S > BEAM_MAX_S) return RFN_ERR_SHAPE;
+        if (!sbs->phi || !sbs->gumbel || !sbs->live || !sbs->weight || !sbs->n_live || !sbs->topk64 || !beam_seq || !beam_lp)
+            return RFN_ERR_ARG;
+    }
+    return RFN_OK;
+}
 // sample_beam's search (misc/RecurrentFusionModel.py:451-531) for all images at once, queued by one call: per step the
 // device-side bookkeeping (rfn_beam_step), the re-gather of the recurrent state rows and one decoder step on the
 // NB * W beam rows.  h / c are ping-ponged with h_alt / c_alt; on return the live state is in h / c again.
@@ -228,36 +276,20 @@ extern "C" int rfn_beam_loop_ex4(const rfn_dims* d, int NB, int W, int S, const 
                                  void* ws, size_t ws_bytes, uint64_t seed, const rfn_decode_constraints* cons,
                                  const rfn_beam_diversity* div, const rfn_beam_lexical* lex, const rfn_beam_stochastic* sbs,
                                  void* st) {
+    RFN_TRY(check_beam_loop(d, NB, W, S, prm && comb && cproj && h && c && h_alt && c_alt && logp && ids && order && ws, seed, beam_seq,
+                            beam_lp, cons, div, lex, sbs));
+    const int rows = NB * W, V1 = d->V1, R = d->R;
+    const bool diverse = beam_diverse(div);
     // `logp` holds, per beam row, its W best log-probs and their tokens (2 * W values): the search never looks at more
     // (:463-466), so the full (rows, V+1) log-prob matrix is neither written nor read back
-    RFN_TRY(check_dims(d));
-    RfnSeed seed_checked;
-    RFN_TRY(path_seed(d, seed, &seed_checked));   // the steps below resolve it again
-    if (NB < 1 || W < 1 || S < 1) return RFN_ERR_SHAPE;
-    if (!prm || !comb || !cproj || !h || !c || !h_alt || !c_alt || !logp || !ids || !order || !ws) return RFN_ERR_ARG;
-    const int rows = NB * W, V1 = d->V1, R = d->R;
-    if (W > 32) return RFN_ERR_SHAPE;
-    RFN_TRY(check_constraints(cons, S));
-    if (cons && !beam_seq) return RFN_ERR_ARG;
-    if (div && (div->groups < 1 || W % div->groups || !(div->lambda >= 0.f))) return RFN_ERR_SHAPE;
-    const bool diverse = div && div->groups > 1;     // one group: the plain search, same launches
-    if (diverse && !div->done_group) return RFN_ERR_ARG;
-    if (lex) {
-        if (diverse) return RFN_ERR_UNSUPPORTED;
-        const int C = lex->n_sets, NW = lex->n_want;
-        if (C < 1 || C > RFN_LEX_MAX_SETS || W % (1 << C) || NW < 1 || NW > RFN_LEX_MAX_IDS || NW > W - W / (1 << C) || S > 64)
-            return RFN_ERR_SHAPE;
-        if (!lex->want || !lex->want_bits || !lex->init_state || !lex->wantv || !lex->state_n || !lex->done_state || !beam_seq)
-            return RFN_ERR_ARG;
-    }
-    if (sbs) {
-        if (diverse || lex) return RFN_ERR_UNSUPPORTED;
-        if (S > 64) return RFN_ERR_SHAPE;
-        if (!sbs->phi || !sbs->gumbel || !sbs->live || !sbs->weight || !sbs->n_live || !sbs->topk64 || !beam_seq || !beam_lp)
-            return RFN_ERR_ARG;
-    }
     float* topv = logp;
     int32_t* topi = (int32_t*)(logp + (size_t)rows * W);
+    StepLists ls;
+    ls.topv = topv, ls.topi = topi, ls.W = W;
+    ls.row_div = W;   // the W rows of an image share its thought vectors (comb / cproj: NB rows)
+    if (cons) ls.blk = cons->blk, ls.ld_blk = RFN_DECODE_MAX_IDS + S, ls.blk_n = cons->blk_n;
+    if (lex) ls.want = lex->want, ls.n_want = lex->n_want, ls.wantv = lex->wantv;
+    ls.sbs = sbs;
     float *hc = h, *cc = c, *ha = h_alt, *ca = c_alt;
     if (hipMemsetAsync(ids, 0, (size_t)rows * sizeof(int64_t), (hipStream_t)st) != hipSuccess) return RFN_ERR_LAUNCH;
     if (sbs) RFN_TRY(rfn_beam_sbs_begin(NB, W, V1, sbs->seed, sbs->offset0, sbs->phi, sbs->gumbel, sbs->live, st));
@@ -285,11 +317,8 @@ extern "C" int rfn_beam_loop_ex4(const rfn_dims* d, int NB, int W, int S, const 
         if (cons)   // the lists for step t + 1, which reads this step's log-probs: rfn_beam_step has forked the beam arrays
             RFN_TRY(rfn_decode_blocklist(beam_seq, 1, rows, nullptr, rows, S, t + 1, cons->block_ngram, cons->banned, cons->n_banned,
                                          cons->bad_endings, cons->n_bad, V1, cons->blk, cons->blk_n, st));
-        RFN_TRY(decoder_step_impl(d, rows, prm, comb, cproj, ids, nullptr, 0, hc, cc, nullptr, nullptr, 0, ws, ws_bytes, seed, t, st,
-                                  topv, topi, W, W,   // the W rows of an image share its thought vectors (comb / cproj: NB rows)
-                                  cons ? cons->blk : nullptr, RFN_DECODE_MAX_IDS + S, cons ? cons->blk_n : nullptr,
-                                  lex ? lex->want : nullptr, lex ? lex->n_want : 0, lex ? lex->wantv : nullptr, sbs,
-                                  sbs ? sbs->offset0 + (uint64_t)(t + 1) : 0));   // this step's lists are read by step t + 1
+        if (sbs) ls.sbs_offset = sbs->offset0 + (uint64_t)(t + 1);   // this step's lists are read by step t + 1
+        RFN_TRY(decoder_step_impl(d, rows, prm, comb, cproj, ids, nullptr, 0, hc, cc, nullptr, nullptr, 0, ws, ws_bytes, seed, t, st, ls));
     }
     if (hc != h) {   // an odd number of swaps: bring the live state home
         RFN_TRY(mem_batch({{h, hc, (long)rows * R}, {c, cc, (long)rows * R}}, st));

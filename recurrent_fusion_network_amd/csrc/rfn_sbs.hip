@@ -3,10 +3,8 @@
 // log-softmax of a beam row with its W best PERTURBED entries (one block per row, the structure of log_softmax_topk_k in
 // rfn_logsoftmax.hip), and the per-image bookkeeping of one step (one block per image, the structure of beam_step_div_k in
 // rfn_beam.hip).  Everything the definition states in fp64 is computed in fp64 here.
-#include "rfn_rows.h"
+#include "rfn_beam_step.h"   // the scaffolding shared with rfn_beam.hip; rfn_rows.h through it
 
-#define SBS_TOPW 32       /* entries a row hands over = beams per image */
-#define SBS_MAX_S 64      /* decode steps a block keeps the beams' histories for (seq_length) */
 #define SBS_THREADS 256
 
 // e = -ln(-ln u), u = (n + 0.5) / 2^24 with n the 24 bits rfn_philox_uniform turns into its float: that float is n * 2^-24
@@ -15,59 +13,6 @@ __device__ __forceinline__ double sbs_gumbel(uint64_t seed, uint64_t offset, uin
     const double u = (double)rfn_philox_uniform(seed, offset, idx) + 0x1p-25;
     return -log(-log(u));
 }
-
-// (key descending, token ascending)
-__device__ __forceinline__ bool key_before(double x, int i, double y, int j) { return x > y || (x == y && i < j); }
-
-// RowTopList (rfn_rows.h) with fp64 keys.
-template <int LW>
-struct KeyTopList {
-    double v[LW];
-    int i[LW];
-    __device__ __forceinline__ void fill() {
-#pragma unroll
-        for (int j = 0; j < LW; ++j) {
-            v[j] = -INFINITY;
-            i[j] = 0x7fffffff;
-        }
-    }
-    __device__ __forceinline__ void offer(double x, int tok) {
-        if (key_before(x, tok, v[LW - 1], i[LW - 1])) {
-#pragma unroll
-            for (int j = 0; j < LW; ++j) {
-                const bool fwd = key_before(x, tok, v[j], i[j]);
-                const double ov = v[j];
-                const int oi = i[j];
-                v[j] = fwd ? x : ov;
-                i[j] = fwd ? tok : oi;
-                x = fwd ? ov : x;
-                tok = fwd ? oi : tok;
-            }
-        }
-    }
-    __device__ __forceinline__ void wave_pop(double& best, int& bi) {
-        best = v[0];
-        bi = i[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (key_before(ob, oi, best, bi)) {
-                best = ob;
-                bi = oi;
-            }
-        }
-        if (i[0] == bi && bi != 0x7fffffff) {
-#pragma unroll
-            for (int j = 0; j + 1 < LW; ++j) {
-                v[j] = v[j + 1];
-                i[j] = i[j + 1];
-            }
-            v[LW - 1] = -INFINITY;
-            i[LW - 1] = 0x7fffffff;
-        }
-    }
-};
 
 // ---- log-softmax + the W best perturbed entries of every live row -------------------------------------------------------
 // The log-sum-exp is log_softmax_row's, taken the way rfn_log_softmax_fwd takes it for this row (VEC or not), so x_v = x[v] - lse
@@ -81,8 +26,8 @@ __global__ __launch_bounds__(256) void log_softmax_topk_gumbel_k(const float* __
                                                                  uint64_t seed, uint64_t offset, double* __restrict__ topk64,
                                                                  float* __restrict__ topv, int* __restrict__ topi) {
     __shared__ float red[4];
-    __shared__ double wv[4][SBS_TOPW];
-    __shared__ int wi[4][SBS_TOPW];
+    __shared__ double wv[4][LSM_TOPW];
+    __shared__ int wi[4][LSM_TOPW];
     extern __shared__ unsigned lsm_bits[];       // MASK: (V1 + 31) / 32 words
     const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (!live[r]) return;                        // the whole block: nothing of this row is written
@@ -90,21 +35,12 @@ __global__ __launch_bounds__(256) void log_softmax_topk_gumbel_k(const float* __
     f32x4 xr[LSM_R4];
     const float lse = log_softmax_row<VEC>(x, V1, xr, red);
     const int cols = min(W, V1);
-    if constexpr (MASK) {
-        for (int i = threadIdx.x; i < (V1 + 31) / 32; i += 256) lsm_bits[i] = 0u;
-        __syncthreads();
-        const int nb = blk_n[r];
-        for (int i = threadIdx.x; i < nb; i += 256) {
-            const int id = blk[r * ld_blk + i];
-            if (id >= 0 && id < V1) atomicOr(&lsm_bits[id >> 5], 1u << (id & 31));
-        }
-        __syncthreads();
-    }
+    if constexpr (MASK) row_mask_build(lsm_bits, V1, blk, ld_blk, blk_n, r);
     const uint64_t base = (uint64_t)r * (uint64_t)V1;
     // key_v, or -inf for a token that is no candidate (blocked, or a log-prob that is -inf or NaN)
     auto key_of = [&](int v) -> double {
         if constexpr (MASK) {
-            if ((lsm_bits[v >> 5] >> (v & 31)) & 1u) return -INFINITY;
+            if (row_mask_has(lsm_bits, v)) return -INFINITY;
         }
         const float lp = x[v] - lse;
         if (!(lp > -INFINITY)) return -INFINITY;
@@ -113,7 +49,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_gumbel_k(const float* __
     // No threshold pass in front of the insert, unlike log_softmax_topk_k: there an entry costs one subtraction and the inserts
     // dominate; here a key costs ten Philox rounds and two fp64 logarithms, so evaluating every key once and letting the list's
     // own last entry turn most of them away is the cheaper order.
-    KeyTopList<LW> top;
+    RowTopList<LW, double> top;
     top.fill();
     for (int v = threadIdx.x; v < V1; v += 256) {
         const double key = key_of(v);
@@ -136,7 +72,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_gumbel_k(const float* __
             if (c < cols)
                 for (int p = 0; p < 4; ++p) {
                     if (pos[p] >= cols || wi[p][pos[p]] == 0x7fffffff) continue;
-                    if (bp < 0 || key_before(wv[p][pos[p]], wi[p][pos[p]], wv[bp][pos[bp]], wi[bp][pos[bp]])) bp = p;
+                    if (bp < 0 || row_before(wv[p][pos[p]], wi[p][pos[p]], wv[bp][pos[bp]], wi[bp][pos[bp]])) bp = p;
                 }
             const long at = (long)r * W + c;
             if (bp < 0) {                        // fewer candidates than W: the slot says so
@@ -157,27 +93,14 @@ __global__ __launch_bounds__(256) void log_softmax_topk_gumbel_k(const float* __
 extern "C" int rfn_log_softmax_topk_gumbel(const float* logits, int64_t ldl, int rows, int V1, int W, const int32_t* blk,
                                            int64_t ld_blk, const int32_t* blk_n, const int32_t* live, uint64_t seed,
                                            uint64_t offset, double* topk64, float* topv, int32_t* topi, void* stream) {
-    if (rows <= 0 || V1 <= 0 || W < 1 || W > SBS_TOPW) return RFN_ERR_SHAPE;
-    if (!logits || !topv || !topi || !topk64 || !live) return RFN_ERR_ARG;
-    if (blk && (!blk_n || ld_blk < 1)) return RFN_ERR_ARG;
-    const size_t bits = blk ? (size_t)((V1 + 31) / 32) * sizeof(unsigned) : 0;
-    if (bits > 48 * 1024) return RFN_ERR_SHAPE;     // one bit per token in LDS
+    size_t bits;
+    RFN_TRY(lsm_topk_check(rows, V1, W, logits && topv && topi && topk64 && live, blk, ld_blk, blk_n, &bits));
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0);
-#define SBS_LAUNCH3(VECV, LWV, MASKV)                                                                                        \
-    hipLaunchKernelGGL((log_softmax_topk_gumbel_k<VECV, LWV, MASKV>), dim3(rows), dim3(256), bits, st, logits, (long)ldl, V1, W, \
-                       blk, (long)ld_blk, blk_n, live, seed, offset, topk64, topv, topi)
-#define SBS_LAUNCH(VECV, LWV)                                                                                                \
-    do {                                                                                                                     \
-        if (blk) SBS_LAUNCH3(VECV, LWV, true);                                                                               \
-        else SBS_LAUNCH3(VECV, LWV, false);                                                                                  \
-    } while (0)
-    if (W <= 4) { if (vec) SBS_LAUNCH(true, 4); else SBS_LAUNCH(false, 4); }
-    else if (W <= 8) { if (vec) SBS_LAUNCH(true, 8); else SBS_LAUNCH(false, 8); }
-    else if (W <= 16) { if (vec) SBS_LAUNCH(true, 16); else SBS_LAUNCH(false, 16); }
-    else { if (vec) SBS_LAUNCH(true, 32); else SBS_LAUNCH(false, 32); }
-#undef SBS_LAUNCH
-#undef SBS_LAUNCH3
+    lsm_topk_dispatch(lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0), W, blk != nullptr, [&](auto vec, auto lw, auto mask) {
+        hipLaunchKernelGGL((log_softmax_topk_gumbel_k<decltype(vec)::value, decltype(lw)::value, decltype(mask)::value>), dim3(rows),
+                           dim3(256), bits, st, logits, (long)ldl, V1, W, blk, (long)ld_blk, blk_n, live, seed, offset, topk64, topv,
+                           topi);
+    });
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }
@@ -195,7 +118,7 @@ __global__ __launch_bounds__(256) void beam_sbs_begin_k(int rows, int W, int V1,
 }
 extern "C" int rfn_beam_sbs_begin(int NB, int W, int V1, uint64_t seed, uint64_t offset0, double* phi, double* gumbel,
                                   int32_t* live, void* stream) {
-    if (NB < 1 || W < 1 || W > SBS_TOPW || V1 < 1) return RFN_ERR_SHAPE;
+    if (NB < 1 || W < 1 || W > BEAM_MAX_W || V1 < 1) return RFN_ERR_SHAPE;
     if (!phi || !gumbel || !live) return RFN_ERR_ARG;
     const int rows = NB * W;
     hipLaunchKernelGGL(beam_sbs_begin_k, dim3(rfn_cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, rows, W, V1, seed, offset0,
@@ -218,22 +141,18 @@ __global__ __launch_bounds__(SBS_THREADS) void beam_step_sbs_k(const double* __r
                                                                int32_t* __restrict__ live, int32_t* __restrict__ order,
                                                                int64_t* __restrict__ nxt, double* __restrict__ weight,
                                                                int32_t* __restrict__ n_live) {
-    __shared__ int prev_seq[SBS_MAX_S][SBS_TOPW];
-    __shared__ float prev_lp[SBS_MAX_S][SBS_TOPW];
-    __shared__ double p_phi[SBS_TOPW], p_g[SBS_TOPW];
-    __shared__ int p_live[SBS_TOPW];
-    __shared__ double c_g[SBS_TOPW * SBS_TOPW], c_phi[SBS_TOPW * SBS_TOPW];
-    __shared__ float c_lp[SBS_TOPW * SBS_TOPW];
-    __shared__ int c_tok[SBS_TOPW * SBS_TOPW], c_q[SBS_TOPW * SBS_TOPW];
-    __shared__ int sel[SBS_TOPW];
+    __shared__ int prev_seq[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ float prev_lp[BEAM_MAX_S][BEAM_MAX_W];
+    __shared__ double p_phi[BEAM_MAX_W], p_g[BEAM_MAX_W];
+    __shared__ int p_live[BEAM_MAX_W];
+    __shared__ double c_g[BEAM_MAX_W * BEAM_MAX_W], c_phi[BEAM_MAX_W * BEAM_MAX_W];
+    __shared__ float c_lp[BEAM_MAX_W * BEAM_MAX_W];
+    __shared__ int c_tok[BEAM_MAX_W * BEAM_MAX_W], c_q[BEAM_MAX_W * BEAM_MAX_W];
+    __shared__ int sel[BEAM_MAX_W];
     __shared__ int nc_s;
     const int k = blockIdx.x, tid = threadIdx.x;
     const int cols = min(W, V1), total = W * cols;
-    for (int i = tid; i < (t - 1) * W; i += SBS_THREADS) {  // the beams before this step (forks read the OLD columns)
-        const int s = i / W, w = i - s * W;
-        prev_seq[s][w] = (int)bs[((long)s * NB + k) * W + w];
-        prev_lp[s][w] = bl[((long)s * NB + k) * W + w];
-    }
+    beam_snapshot(prev_seq, prev_lp, bs, bl, k, W, NB, t, tid, SBS_THREADS);
     if (tid < W) {
         p_phi[tid] = phi[k * W + tid];
         p_g[tid] = gum[k * W + tid];
@@ -284,13 +203,11 @@ __global__ __launch_bounds__(SBS_THREADS) void beam_step_sbs_k(const double* __r
         if (qi < 0) continue;
         const double gi = c_g[i];
         const int ti = c_tok[i];
-        int rank = 0;
-        for (int j = 0; j < total && rank < W; ++j) {
+        const int rank = beam_rank(total, W, i, [&](int j) { return c_q[j] >= 0; }, [&](int j, int) {
             const int qj = c_q[j];
-            if (qj < 0) continue;
             const double gj = c_g[j];
-            rank += (gj > gi) || (gj == gi && (qj < qi || (qj == qi && c_tok[j] < ti)));
-        }
+            return (gj > gi) || (gj == gi && (qj < qi || (qj == qi && c_tok[j] < ti)));
+        });
         if (rank < W) sel[rank] = i;
     }
     __syncthreads();
@@ -342,7 +259,7 @@ __global__ __launch_bounds__(SBS_THREADS) void beam_step_sbs_k(const double* __r
 extern "C" int rfn_beam_step_sbs(const double* topk64, const float* topv, const int32_t* topi, int V1, int W, int S, int t, int NB,
                                  int64_t* beam_seq, float* beam_lp, double* phi, double* gumbel, int32_t* live, int32_t* order,
                                  int64_t* next_ids, double* weight, int32_t* n_live, void* stream) {
-    if (W < 1 || W > SBS_TOPW || S < 1 || S > SBS_MAX_S || t < 1 || t > S || NB < 1 || V1 < 1) return RFN_ERR_SHAPE;
+    if (W < 1 || W > BEAM_MAX_W || S < 1 || S > BEAM_MAX_S || t < 1 || t > S || NB < 1 || V1 < 1) return RFN_ERR_SHAPE;
     if (!topk64 || !topv || !topi || !beam_seq || !beam_lp || !phi || !gumbel || !live || !order || !next_ids || !weight || !n_live)
         return RFN_ERR_ARG;
     hipLaunchKernelGGL(beam_step_sbs_k, dim3(NB), dim3(SBS_THREADS), 0, (hipStream_t)stream, topk64, topv, topi, V1, W, S, t, NB,

@@ -11,6 +11,9 @@ import torch
 
 from . import _native as N
 
+MAX_BEAM = 32        # rows per image of a beam search, and entries of a row's top list (csrc: BEAM_MAX_W, LSM_TOPW)
+MAX_STEPS = 64       # decode steps a beam-step block keeps the histories for (csrc: BEAM_MAX_S)
+
 
 class _Stepper:
     """Free-running decoder state for sample / beam / one_time_step: rfn_decoder_prepare + rfn_decoder_step."""
@@ -125,20 +128,35 @@ def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
                                        N.stream_ptr()), 'rfn_decoder_loop_ex2')
 
 
-class BeamBuffers:
-    """The state of a beam search over B images x W beams x S steps.  The rows' top-W lists are uninitialised storage, as
-    one float buffer (`top_flat`, rfn_beam_loop) or as values and indices (`top_lists`, a host-stepped search).  `done_group`
-    (the group of every done beam) exists only for a diverse search (groups > 1), `state_n` / `done_state` (the occupied rows of
-    every state, the state of every done beam) only for a lexically constrained one (states = 2^C > 1; W then counts all rows)."""
+class _BeamArrays:
+    """The arrays every beam search over B images x W rows x S steps keeps: the rows' tokens and log-probs so far (`bs`, `bl`), the
+    fork order and the tokens fed next.  The rows' top-W lists are uninitialised storage, one float buffer (`top_flat`,
+    rfn_beam_loop).  What a search does not keep reads as None (the stochastic search has no sums and no done beams)."""
 
-    def __init__(self, B, W, S, dev, groups=1, states=1):
+    bsum = done_seq = done_lp = done_p = done_n = active = None
+
+    def __init__(self, B, W, S, dev):
         self.B, self.W, self.S, self.dev = B, W, S, dev
-        self.rows, self.max_done = rows, max_done = B * W, W * S
+        self.rows, self.max_done = B * W, W * S
         self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
         self.bl = torch.zeros(S, B, W, device=dev)
+        self.order = torch.zeros(self.rows, dtype=torch.int32, device=dev)
+        self.ids = torch.zeros(self.rows, dtype=torch.long, device=dev)
+
+    def top_flat(self):
+        return torch.empty(2 * self.rows * self.W, device=self.dev)
+
+
+class BeamBuffers(_BeamArrays):
+    """The state of a beam search with done beams.  A host-stepped search takes the rows' top-W lists as values and indices
+    (`top_lists`) and advances with `step`.  `done_group` (the group of every done beam) exists only for a diverse search
+    (groups > 1), `state_n` / `done_state` (the occupied rows of every state, the state of every done beam) only for a lexically
+    constrained one (states = 2^C > 1; W then counts all rows)."""
+
+    def __init__(self, B, W, S, dev, groups=1, states=1):
+        super().__init__(B, W, S, dev)
+        max_done = self.max_done
         self.bsum = torch.zeros(B, W, device=dev)
-        self.order = torch.zeros(rows, dtype=torch.int32, device=dev)
-        self.ids = torch.zeros(rows, dtype=torch.long, device=dev)
         self.done_seq = torch.zeros(B, max_done, S, dtype=torch.long, device=dev)
         self.done_lp = torch.zeros(B, max_done, S, device=dev)
         self.done_p = torch.zeros(B, max_done, device=dev)
@@ -148,29 +166,40 @@ class BeamBuffers:
         self.state_n = torch.zeros(B, states, dtype=torch.int32, device=dev) if states > 1 else None
         self.done_state = torch.zeros(B, max_done, dtype=torch.int32, device=dev) if states > 1 else None
 
-    def top_flat(self):
-        return torch.empty(2 * self.rows * self.W, device=self.dev)
-
     def top_lists(self):
         return torch.empty(self.rows, self.W, device=self.dev), torch.empty(self.rows, self.W, dtype=torch.int32, device=self.dev)
 
+    def step(self, topv, topi, V1, t, div=None):
+        """One step of a host-stepped search (the ensemble's) on the rows' top-W lists: rfn_beam_step_topk, or rfn_beam_step_div
+        with a parsed _Diversity."""
+        tail = (self.S, t, self.B, self.max_done, self.bs.data_ptr(), self.bl.data_ptr(), self.bsum.data_ptr(), self.order.data_ptr(),
+                self.ids.data_ptr(), self.done_seq.data_ptr(), self.done_lp.data_ptr(), self.done_p.data_ptr(), self.done_n.data_ptr())
+        if div is not None:
+            N.check(N.lib.rfn_beam_step_div(topv.data_ptr(), topi.data_ptr(), V1, self.W, div.groups, div.lam, *tail,
+                                            self.done_group.data_ptr(), self.active.data_ptr(), N.stream_ptr()), 'rfn_beam_step_div')
+        else:
+            N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, self.W, *tail, self.active.data_ptr(),
+                                             N.stream_ptr()), 'rfn_beam_step_topk')
 
-def run_beam_loop(stepper, bufs, cons, div=None, lex=None):
-    """The whole search in one call: S x (bookkeeping, state re-gather, decoder step on the B * W rows).  cons: a parsed
-    _Constraints or None; div: a parsed _Diversity or None (bufs then holds done_group); lex: a parsed _Lexical or None (bufs then
-    holds state_n / done_state)."""
+
+def run_beam_loop(stepper, bufs, cons, div=None, lex=None, sbs_seed=None):
+    """The whole search in one call (rfn_beam_loop_ex4): S x (bookkeeping, state re-gather, decoder step on the B * W rows).
+    cons: a parsed _Constraints or None; div: a parsed _Diversity or None (bufs then holds done_group); lex: a parsed _Lexical or
+    None (bufs then holds state_n / done_state); sbs_seed: the 64-bit key of the Gumbel noise of a stochastic search (bufs is then
+    a StochasticBuffers; the stepper's own seed keys the dropout masks, as everywhere)."""
     b, logp = bufs, bufs.top_flat()
     h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
-    N.check(N.lib.rfn_beam_loop_ex3(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
+    N.check(N.lib.rfn_beam_loop_ex4(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
                                     stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
-                                    c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(),
-                                    b.order.data_ptr(), b.ids.data_ptr(), b.done_seq.data_ptr(), b.done_lp.data_ptr(),
-                                    b.done_p.data_ptr(), b.done_n.data_ptr(), b.active.data_ptr(), b.max_done,
+                                    c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), N.ptr(b.bsum),
+                                    b.order.data_ptr(), b.ids.data_ptr(), N.ptr(b.done_seq), N.ptr(b.done_lp),
+                                    N.ptr(b.done_p), N.ptr(b.done_n), N.ptr(b.active), b.max_done,
                                     stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
                                     C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None,
                                     C.byref(div.struct(b)) if div is not None else None,
-                                    C.byref(lex.struct(b)) if lex is not None else None, N.stream_ptr()),
-            'rfn_beam_loop_ex3')
+                                    C.byref(lex.struct(b)) if lex is not None else None,
+                                    C.byref(b.struct(sbs_seed)) if sbs_seed is not None else None, N.stream_ptr()),
+            'rfn_beam_loop_ex4')
 
 
 class _Stochastic:
@@ -181,7 +210,7 @@ class _Stochastic:
     (force_ids) applies."""
 
     KEYS = ('seed', 'block_ngram', 'banned_ids', 'bad_endings')
-    MAX_N = 32
+    MAX_N = MAX_BEAM
 
     @classmethod
     def parse(cls, opt, n, S):
@@ -191,7 +220,7 @@ class _Stochastic:
             raise ValueError('sample_distinct takes %s, not %s' % (', '.join(cls.KEYS), ', '.join(map(repr, bad))))
         if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= cls.MAX_N:
             raise ValueError('sample_distinct draws 1 <= n <= %d captions per image, got %r' % (cls.MAX_N, n))
-        if S > 64:
+        if S > MAX_STEPS:
             raise N.RfnError('stochastic beam search supports seq_length <= 64')
         seed = opt.get('seed', None)
         if seed is not None and (isinstance(seed, bool) or int(seed) != seed):
@@ -201,16 +230,12 @@ class _Stochastic:
         return s
 
 
-class StochasticBuffers:
-    """The state of a stochastic beam search over B images x W rows x S steps: the beam arrays of BeamBuffers that the search uses
-    (it has no done beams: finished rows stay in the beam), and phi / gumbel / live, weight / n_live and the rows' keys."""
+class StochasticBuffers(_BeamArrays):
+    """The state of a stochastic beam search over B images x W rows x S steps: the beam arrays (it has no done beams: finished rows
+    stay in the beam), and phi / gumbel / live, weight / n_live and the rows' keys."""
 
     def __init__(self, B, W, S, dev):
-        self.B, self.W, self.S, self.dev, self.rows = B, W, S, dev, B * W
-        self.bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
-        self.bl = torch.zeros(S, B, W, device=dev)
-        self.order = torch.zeros(self.rows, dtype=torch.int32, device=dev)
-        self.ids = torch.zeros(self.rows, dtype=torch.long, device=dev)
+        super().__init__(B, W, S, dev)
         self.phi = torch.zeros(B, W, dtype=torch.float64, device=dev)
         self.gumbel = torch.zeros(B, W, dtype=torch.float64, device=dev)
         self.live = torch.zeros(B, W, dtype=torch.int32, device=dev)       # the loop sets the three (rfn_beam_sbs_begin)
@@ -218,29 +243,10 @@ class StochasticBuffers:
         self.n_live = torch.zeros(B, dtype=torch.int32, device=dev)
         self.topk64 = torch.empty(self.rows, W, dtype=torch.float64, device=dev)
 
-    def top_flat(self):
-        return torch.empty(2 * self.rows * self.W, device=self.dev)
-
     def struct(self, seed, offset0=0):
         self._struct = N.BeamStochastic(seed, offset0, self.phi.data_ptr(), self.gumbel.data_ptr(), self.live.data_ptr(),
                                         self.weight.data_ptr(), self.n_live.data_ptr(), self.topk64.data_ptr())
         return self._struct
-
-
-def run_stochastic_loop(stepper, bufs, cons, noise_seed):
-    """The whole stochastic search in one call (rfn_beam_loop_ex4): S x (bookkeeping, state re-gather, decoder step on the B * W
-    rows ending in the Gumbel top-W).  cons: a parsed _Constraints or None; noise_seed: the 64-bit key of the Gumbel noise (the
-    stepper's own seed keys the dropout masks, as everywhere)."""
-    b, logp = bufs, bufs.top_flat()
-    h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
-    N.check(N.lib.rfn_beam_loop_ex4(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
-                                    stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),
-                                    c_alt.data_ptr(), logp.data_ptr(), b.bs.data_ptr(), b.bl.data_ptr(), None,
-                                    b.order.data_ptr(), b.ids.data_ptr(), None, None, None, None, None, b.W * b.S,
-                                    stepper.ws.data_ptr(), stepper.ws_bytes, stepper.seed,
-                                    C.byref(cons.bind(b.rows, b.dev).struct) if cons is not None else None, None, None,
-                                    C.byref(b.struct(noise_seed)), N.stream_ptr()),
-            'rfn_beam_loop_ex4')
 
 
 class _Constraints:
@@ -274,7 +280,7 @@ class _Constraints:
             raise ValueError('token 0 (END) cannot be banned')
         if not (n or banned or bad):
             return None
-        if S > 64:
+        if S > MAX_STEPS:
             raise N.RfnError('decoding constraints support seq_length <= 64')
         c = cls()
         c.n, c.banned, c.bad, c.V1, c.S = n, banned, bad, V1, S
@@ -360,14 +366,6 @@ class _Diversity:
         self._struct = N.BeamDiversity(self.groups, self.lam, bufs.done_group.data_ptr())
         return self._struct
 
-    def step(self, bufs, topv, topi, V1, t):
-        """One step of a host-stepped search (the ensemble's): rfn_beam_step_div on the rows' top-W lists."""
-        b = bufs
-        N.check(N.lib.rfn_beam_step_div(topv.data_ptr(), topi.data_ptr(), V1, b.W, self.groups, self.lam, b.S, t, b.B, b.max_done,
-                                        b.bs.data_ptr(), b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
-                                        b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(), b.done_n.data_ptr(),
-                                        b.done_group.data_ptr(), b.active.data_ptr(), N.stream_ptr()), 'rfn_beam_step_div')
-
 
 class _Lexical:
     """Lexically constrained beam search of one call (rfn.h "lexically constrained beam search"): opt['require'] names, per image,
@@ -401,7 +399,7 @@ class _Lexical:
         if nsets > N.LEX_MAX_SETS:
             raise ValueError('require holds %d sets for an image, at most %d are supported' % (nsets, N.LEX_MAX_SETS))
         W = Wb << nsets
-        if W > 32:
+        if W > MAX_BEAM:
             raise ValueError('beam_size %d with %d required sets needs %d rows per image, at most 32 are supported' % (Wb, nsets, W))
         want, bits, init = [], [], []
         for img in req:
@@ -710,10 +708,9 @@ def _length_penalty(opt):
     return alpha
 
 
-def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_penalty=0.0, done_group=None, consensus=None,
-                       groups=1, keep=None, done_state=None, lex=None):
-    """Done beams sorted by -p, stably, as the reference's sorted(..., key=-p) (:529) -- on the device, for all images at
-    once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
+def _sorted_done_beams(bufs, length_penalty=0.0, consensus=None, groups=1, keep=None, lex=None):
+    """The done beams of a finished search (bufs: its BeamBuffers) sorted by -p, stably, as the reference's
+    sorted(..., key=-p) (:529) -- on the device, for all images at once: the caller returns with everything queued and nothing read back, so the host's next batch (and its stage-I/II
     GEMMs) starts while this one is still decoding.  -> (seq (B, S) best done beam per image, its log-probs, and the
     per-image Python structures top_seq / top_prob / done_beams: thousands of small objects that need the done counts on
     the host, so they are lists that fill themselves on first access -- a loop that only consumes the returned captions
@@ -723,8 +720,8 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     ties keep construction order, and `p` / top_prob stay the raw sums.  len^alpha comes from a host table of S + 1 doubles
     and the quotient is one IEEE division in fp64, so a host re-sort of the same (p, len) reproduces the order exactly.
 
-    done_group (a diverse search): every done beam's group goes through the same gather, and every done_beams dict gets it as
-    'group'.
+    bufs.done_group (a diverse search): every done beam's group goes through the same gather, and every done_beams dict gets
+    it as 'group'.
 
     consensus (a parsed _Consensus): the returned seq and its log-probs are the consensus pick among the ranked beams
     (_consensus_beams) instead of the first of them; the lists keep their meaning and order, and nothing more is read back.
@@ -732,9 +729,11 @@ def _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, length_pe
     keep (a dict, with keep['n'] = keep_candidates_n): it receives 'seq' (B, m, S) int64 and 'n_cand' (B,) int32, the candidate
     set the consensus pick chooses from (_beam_candidates), on the device; with or without `consensus`.
 
-    done_state (a lexically constrained search): the done beams are ordered by the number of satisfied sets descending first, then
-    as above; every done_beams dict gets its 'state', and lex (a dict) receives 'state' (B,) int32, the returned caption's."""
-    dev, B = done_p.device, done_p.size(0)
+    bufs.done_state (a lexically constrained search): the done beams are ordered by the number of satisfied sets descending
+    first, then as above; every done_beams dict gets its 'state', and lex (a dict) receives 'state' (B,) int32, the returned caption's."""
+    done_seq, done_lp, done_p, done_n, done_group, done_state = (bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
+                                                                 bufs.done_group, bufs.done_state)
+    dev, B, S, max_done = bufs.dev, bufs.B, bufs.S, bufs.max_done
     score = done_p
     if length_penalty:
         ended = done_seq == 0

@@ -17,8 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _length_penalty,
-                     _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, keep_candidates_n)
+from .decode import (MAX_BEAM, MAX_STEPS, BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity,
+                     _length_penalty, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, keep_candidates_n)
 
 
 # Every entry point takes `att_lens` as RecurrentFusionModel's do (INTEGRATION.md "Ragged attention maps"): the per-image row counts
@@ -40,6 +40,20 @@ class EnsembleDecoder:
         for m in self.models:
             if m.vocab_size != m0.vocab_size or m.seq_length != m0.seq_length:
                 raise N.RfnError('ensemble members disagree on vocab_size / seq_length')
+
+    def _steppers(self, fc_feats, att_feats, att_lens, rows_per_image=1):
+        """One _Stepper per member, on the member's own thought vectors and initial state.  rows_per_image = n > 1: n rows per image,
+        image-major (row k * n + j = image k), the thought vectors repeated physically -- a host-stepped stepper's rows do not
+        share them."""
+        n, steppers = rows_per_image, []
+        for m in self.models:
+            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
+            if n > 1:
+                comb, h, c = comb.repeat_interleave(n, dim=1), h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
+            else:
+                h, c = h.clone(), c.clone()
+            steppers.append(_Stepper(m, comb, h, c))
+        return steppers
 
     def _averaged_step(self, steppers, ids, logit_sum, logit_m):
         """One decoder step of every member on the SAME tokens (each embeds them with its own table): logit_sum becomes the
@@ -63,10 +77,7 @@ class EnsembleDecoder:
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
         cons = _Constraints.parse(opt, V1, S)
-        steppers = []
-        for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
-            steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
+        steppers = self._steppers(fc_feats, att_feats, att_lens)
         dev = steppers[0].h.device
         st = N.stream_ptr()
         logit_sum = torch.empty(B, V1, device=dev)
@@ -102,12 +113,7 @@ class EnsembleDecoder:
         B = m0._check_inputs(fc_feats, att_feats)
         rows, n, T = so.layout(seq.shape, B, m0.seq_length)
         V1 = m0.vocab_size + 1
-        steppers = []
-        for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
-            if n > 1:
-                comb, h, c = comb.repeat_interleave(n, dim=1), h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
-            steppers.append(_Stepper(m, comb.contiguous(), h.clone(), c.clone()))
+        steppers = self._steppers(fc_feats, att_feats, att_lens, n)
         dev = steppers[0].h.device
         st = N.stream_ptr()
         bufs = ScoreBuffers(so, seq, rows, T, m0.seq_length, dev)
@@ -138,10 +144,7 @@ class EnsembleDecoder:
             raise N.RfnError('seq has shape %s, the features hold %d rows' % (tuple(seq.shape), B))
         S = m0._decoder_steps(seq)
         V1 = m0.vocab_size + 1
-        steppers = []
-        for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
-            steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
+        steppers = self._steppers(fc_feats, att_feats, att_lens)
         dev = steppers[0].h.device
         feed = seq[:, :S].to(dev).long().t().contiguous()      # row t = the tokens fed at step t
         out = torch.empty(S, B, V1, device=dev)
@@ -167,10 +170,7 @@ class EnsembleDecoder:
         if not 1 <= k <= min(MAX_K, V1):
             raise ValueError('k = %d: 1 <= k <= min(%d, V+1 = %d)' % (k, MAX_K, V1))
         S = m0._decoder_steps(seq)
-        steppers = []
-        for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
-            steppers.append(_Stepper(m, comb, h.clone(), c.clone()))
+        steppers = self._steppers(fc_feats, att_feats, att_lens)
         dev = steppers[0].h.device
         st = N.stream_ptr()
         feed = seq[:, :S].to(dev).long().t().contiguous()      # row t = the tokens fed at step t
@@ -195,7 +195,7 @@ class EnsembleDecoder:
         W = opt.get('beam_size', 10)
         m0 = self.models[0]
         B, S, V1 = fc_feats[0].size(0), m0.seq_length, m0.vocab_size + 1
-        if W > 32 or S > 64 or W > V1:
+        if W > MAX_BEAM or S > MAX_STEPS or W > V1:
             raise N.RfnError('beam search supports beam_size <= 32 (and <= V+1) and seq_length <= 64')
         if opt.get('require', None) is not None:
             raise ValueError('require (lexically constrained beam search) is RecurrentFusionModel.sample_beam\'s: the ensemble\'s '
@@ -204,11 +204,7 @@ class EnsembleDecoder:
         cs = _Consensus.parse(opt, V1, S, W)
         keep_n = keep_candidates_n(opt, W)
         keep = None if keep_n is None else {'n': keep_n}
-        steppers = []
-        for m in self.models:
-            comb, h, c, _ = m._prefix(fc_feats, att_feats, False, 0, att_lens)
-            steppers.append(_Stepper(m, comb.repeat_interleave(W, dim=1).contiguous(),       # row k * W + q = image k
-                                     h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous()))
+        steppers = self._steppers(fc_feats, att_feats, att_lens, W)       # row k * W + q = image k
         dev = steppers[0].h.device
         st = N.stream_ptr()
         b = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
@@ -220,13 +216,7 @@ class EnsembleDecoder:
             cons.bind(rows, dev)
         for t in range(S + 1):
             if t >= 1:
-                if div is not None:
-                    div.step(b, topv, topi, V1, t)
-                else:
-                    N.check(N.lib.rfn_beam_step_topk(topv.data_ptr(), topi.data_ptr(), V1, W, S, t, B, b.max_done, b.bs.data_ptr(),
-                                                     b.bl.data_ptr(), b.bsum.data_ptr(), b.order.data_ptr(), b.ids.data_ptr(),
-                                                     b.done_seq.data_ptr(), b.done_lp.data_ptr(), b.done_p.data_ptr(),
-                                                     b.done_n.data_ptr(), b.active.data_ptr(), st), 'rfn_beam_step_topk')
+                b.step(topv, topi, V1, t, div)
                 if t == S:
                     break                      # the reference runs one more decoder step whose output is never used
                 for sp in steppers:
@@ -238,9 +228,7 @@ class EnsembleDecoder:
             else:
                 N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
                         'rfn_log_softmax_topk')
-        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b.done_seq, b.done_lp, b.done_p, b.done_n, S,
-                                                                             b.max_done, alpha, b.done_group, cs,
-                                                                             div.groups if div is not None else 1, keep)
+        seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b, alpha, cs, div.groups if div is not None else 1, keep)
         self.consensus = cs.result if cs is not None else None
         self.candidates = None if keep is None else {'seq': keep['seq'], 'n_cand': keep['n_cand']}
         self.diverse_beams = _diverse_beams(self.done_beams, div.groups) if div is not None else None

@@ -22,9 +22,9 @@ import torch.nn as nn
 
 from . import _native as N
 from .distill import TopKTeacher
-from .decode import (BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList, _length_penalty, _Lexical,
-                     _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit, keep_candidates_n, run_beam_loop,
-                     run_greedy_loop, run_stochastic_loop, _Stochastic, StochasticBuffers)
+from .decode import (MAX_BEAM, MAX_STEPS, BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList,
+                     _length_penalty, _Lexical, _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit,
+                     keep_candidates_n, run_beam_loop, run_greedy_loop, _Stochastic, StochasticBuffers)
 
 _INIT = 0.1
 
@@ -92,6 +92,10 @@ class _DecoderParams(nn.Module):
         self.att_h_2_out = nn.Linear(att_hid, 1)
         for lin in (self.i2h, self.h2h, self.z2h, self.att_2_att_h, self.h_2_att_h, self.att_h_2_out):
             _uniform(lin.weight, lin.bias)
+
+
+# path_flags under which the decoder cell reads the thought vectors per row: rows cannot share them (_need_hoisted)
+_NOT_HOISTED = N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD
 
 
 def _fresh_seed() -> int:
@@ -1017,6 +1021,11 @@ class RecurrentFusionModel(nn.Module):
             out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp, cs)
         return (*out, reason_pred)
 
+    def _need_hoisted(self, what, flags=_NOT_HOISTED, error=N.RfnError):
+        """Refuse a call whose rows share thought vectors when path_flags select a decoder form that reads them per row."""
+        if int(self.path_flags) & flags:
+            raise error('%s the hoisted decoder cell (path_flags select another form)' % what)
+
     def sample_group(self, fc_feats, att_feats, n, opt={}, att_lens=None):
         """The RL trainer's sampled pass (train_rl.py:160, misc/RecurrentFusionModel.py:623-631) with n draws per image ->
         (seq (B*n, <= S), seqLogprobs, logprobs_all, reason_pred) with rows image-major (row k * n + j is draw j of image k) and
@@ -1036,8 +1045,8 @@ class RecurrentFusionModel(nn.Module):
         B = self._check_inputs(fc_feats, att_feats)
         if force is not None and (force.dim() != 2 or force.size(0) != B * n or force.size(1) < self.seq_length):
             raise ValueError('force_ids must be (%d, >= %d), got %s' % (B * n, self.seq_length, tuple(force.shape)))
-        if n > 1 and int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
-            raise N.RfnError('n draws per image need the hoisted decoder cell (path_flags select another form)')
+        if n > 1:
+            self._need_hoisted('n draws per image need')
         train = bool(self.training)
         seed = self._step_seed(train)
         want_grad = torch.is_grad_enabled()
@@ -1072,8 +1081,7 @@ class RecurrentFusionModel(nn.Module):
         cons = _Constraints.parse(opt, V1, S)
         if torch.is_grad_enabled():
             raise N.RfnError('stochastic beam search is not differentiated: call sample_distinct under no_grad')
-        if int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
-            raise N.RfnError('n rows per image need the hoisted decoder cell (path_flags select another form)')
+        self._need_hoisted('n rows per image need')
         W = sb.n
         drop = bool(self.training)
         seed = _fresh_seed() if drop else 0
@@ -1083,7 +1091,7 @@ class RecurrentFusionModel(nn.Module):
         stepper = _Stepper(self, comb, h.repeat_interleave(W, dim=0).contiguous(), c.repeat_interleave(W, dim=0).contiguous(),
                            drop, seed)
         bufs = StochasticBuffers(B, W, S, dev)
-        run_stochastic_loop(stepper, bufs, cons, noise_seed)
+        run_beam_loop(stepper, bufs, cons, sbs_seed=noise_seed)
         cands = bufs.bs.permute(1, 2, 0).contiguous()                                # (B, n, S)
         self.stochastic_beams = {'logprob': bufs.phi, 'gumbel': bufs.gumbel, 'weight': bufs.weight, 'n_live': bufs.n_live}
         self.candidates = {'seq': cands, 'n_cand': bufs.n_live}
@@ -1166,8 +1174,8 @@ class RecurrentFusionModel(nn.Module):
         so = _Scoring.parse(opt)
         B = self._check_inputs(fc_feats, att_feats)
         rows, n, T = so.layout(seq.shape, B, self.seq_length)
-        if n > 1 and int(self.path_flags) & (N.PATH_OPT_DEC_UNHOISTED | N.PATH_OPT_PERSIST_DEC_FWD | N.PATH_OPT_PERSIST_DEC_BWD):
-            raise N.RfnError('n captions per image need the hoisted decoder cell (path_flags select another form)')
+        if n > 1:
+            self._need_hoisted('n captions per image need')
         comb, h, c, _ = self._prefix(fc_feats, att_feats, False, 0, att_lens)
         dev = comb.device
         if n > 1:
@@ -1222,7 +1230,7 @@ class RecurrentFusionModel(nn.Module):
         beam_size = opt.get('beam_size', 10)
         B, S, V1 = fc_feats[0].size(0), self.seq_length, self.vocab_size + 1
         assert beam_size <= V1, 'lets assume this for now'
-        if beam_size > 32 or S > 64:
+        if beam_size > MAX_BEAM or S > MAX_STEPS:
             raise N.RfnError('beam search supports beam_size <= 32 and seq_length <= 64')
         lex = _Lexical.parse(opt, B, V1, beam_size)
         W = lex.W if lex is not None else beam_size
@@ -1230,8 +1238,8 @@ class RecurrentFusionModel(nn.Module):
         cs = _Consensus.parse(opt, V1, S, beam_size)
         if lex is not None and (div is not None or cs is not None):
             raise ValueError('require cannot be combined with group_size > 1 or consensus')
-        if lex is not None and int(self.path_flags) & N.PATH_OPT_DEC_UNHOISTED:
-            raise ValueError('require needs the hoisted decoder cell (path_flags select another form)')
+        if lex is not None:
+            self._need_hoisted('require needs', N.PATH_OPT_DEC_UNHOISTED, ValueError)
         keep_n = keep_candidates_n(opt, beam_size)
         keep = None if keep_n is None else {'n': keep_n}
         if (cons is not None or alpha) and opt.get('force_ids', None) is not None:
@@ -1247,10 +1255,8 @@ class RecurrentFusionModel(nn.Module):
             bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1, lex.G if lex is not None else 1)
             run_beam_loop(stepper, bufs, cons, div, lex.bind(dev) if lex is not None else None)
             lex_out = {} if lex is not None else None
-            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs.done_seq, bufs.done_lp, bufs.done_p, bufs.done_n,
-                                                                            S, bufs.max_done, alpha, bufs.done_group, cs,
-                                                                            div.groups if div is not None else 1, keep,
-                                                                            bufs.done_state, lex_out)
+            seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs, alpha, cs, div.groups if div is not None else 1, keep,
+                                                                            lex_out)
             heads = reason.unsqueeze(2).expand(-1, -1, W, -1)                       # (M+1, B, W, K) broadcast view
         self.done_beams = done_beams
         self.consensus = cs.result if cs is not None else None

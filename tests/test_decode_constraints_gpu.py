@@ -285,22 +285,16 @@ def host_sample(models, fc, att, cons, u=None, inv_temp=1.0):
 @torch.no_grad()
 def host_beam(models, fc, att, W, cons, alpha=0.0):
     """sample_beam stepped from the host with rfn_beam_step in its full-row form on the masked log-prob rows."""
-    from recurrent_fusion_network_amd.decode import _sorted_done_beams
+    from recurrent_fusion_network_amd.decode import BeamBuffers, _sorted_done_beams
     N = nat()
     m0 = models[0]
     B, S, V1 = fc[0].size(0), m0.seq_length, m0.vocab_size + 1
     dev = fc[0].device
     st = N.stream_ptr()
     steppers = _members(models, fc, att, repeat=W)
-    rows, max_done = B * W, W * S
-    bs = torch.zeros(S, B, W, dtype=torch.long, device=dev)
-    bl, bsum = torch.zeros(S, B, W, device=dev), torch.zeros(B, W, device=dev)
-    order = torch.zeros(rows, dtype=torch.int32, device=dev)
-    ids = torch.zeros(rows, dtype=torch.long, device=dev)
-    done_seq = torch.zeros(B, max_done, S, dtype=torch.long, device=dev)
-    done_lp, done_p = torch.zeros(B, max_done, S, device=dev), torch.zeros(B, max_done, device=dev)
-    done_n = torch.zeros(B, dtype=torch.int32, device=dev)
-    active = torch.ones(B, dtype=torch.int32, device=dev)
+    b = BeamBuffers(B, W, S, dev)
+    rows, max_done, bs, bl, bsum, order, ids = b.rows, b.max_done, b.bs, b.bl, b.bsum, b.order, b.ids
+    done_seq, done_lp, done_p, done_n, active = b.done_seq, b.done_lp, b.done_p, b.done_n, b.active
     logit_sum, logit_m, logp = (torch.empty(rows, V1, device=dev) for _ in range(3))
     for t in range(S + 1):
         if t >= 1:
@@ -314,7 +308,7 @@ def host_beam(models, fc, att, W, cons, alpha=0.0):
         _averaged_logp(N, steppers, ids, logit_sum, logit_m, logp)
         hist = bs.cpu().numpy()[:t].reshape(t, rows).T                          # row k * W + w continues beam (k, w)
         logp.copy_(torch.from_numpy(D.mask_rows(logp.cpu().numpy(), hist, t + 1, **cons)).to(dev))
-    return _sorted_done_beams(done_seq, done_lp, done_p, done_n, S, max_done, alpha)
+    return _sorted_done_beams(b, alpha)
 
 
 def cons_of(opt):
