@@ -1653,6 +1653,85 @@ int rfn_decoder_score(const rfn_dims* d, int B, int S, const float* const* param
                       float* tok_lp, int32_t* tok_rank, float* tok_ent, int64_t ld_out, double* cap_lp, int32_t* cap_len,
                       void* ws, size_t ws_bytes, int rows_per_image, void* stream);
 
+/* ---- mixture of softmaxes (opts.py --use_mos / --num_expert; misc/MixtureOfSoftmax.py) ------------------------------------------
+ * An output head that replaces log_softmax(logit(h)): K experts tanh(Linear(h)) share one vocabulary projection, a softmax prior
+ * over the experts mixes their softmaxes.  Per hidden row h (R floats), with the reference's state_dict names:
+ *   c_k    = prior.weight[k] . h                           log pi_k = c_k - LSE_j c_j
+ *   z_k    = tanh(latent.k.0.weight . h + latent.k.0.bias)                                  (E floats)
+ *   x_kv   = decoder.weight[v] . z_k + decoder.bias[v]     lse_k = LSE_v x_kv
+ *   a_kv   = log pi_k + x_kv - lse_k
+ *   logp_v = LSE_k a_kv
+ * The reference takes log(sum_k pi_k softmax(x_k)) in linear f32 space, which is -inf where the sum underflows; the log-sum-exp
+ * form is the same function and stays finite for every finite input.
+ * Backward, G_v = dL / dlogp_v:  r_kv = exp(a_kv - logp_v), p_kv = exp(x_kv - lse_k), s_k = sum_v G_v r_kv,
+ *   dx_kv = G_v r_kv - p_kv s_k,  dc_k = s_k - pi_k sum_j s_j;  dz, dh and the parameter gradients follow by the chain rule.
+ * Loss form: G_v = -(g / B) * mask * q_v with q the one-hot or label-smoothed target of rfn_xe_logits_* (targets clamped alike).
+ *
+ * Parameters and gradients: arrays of device pointers in state_dict order -- prior.weight (K, R); latent.k.0.weight (E, R) and
+ * latent.k.0.bias (E) for k < K; decoder.weight (V1, E); decoder.bias (V1) -- rfn_mos_param_count = 2 K + 3 slots, names and
+ * shapes as rfn_param_name / rfn_param_shape give them (cols = 1 for a bias).  1 <= K <= RFN_MOS_MAXK, R, E >= 1, V1 >= 2:
+ * RFN_ERR_SHAPE otherwise (rfn_mos_ws_bytes: 0).
+ *
+ * Workspace (rfn_mos_ws_bytes(md, rows, train) bytes, 16-B aligned; every slab rounded up to 64 floats):
+ *   c (rows, K) | log pi (rows, K) | lse (K, rows) | z (K, rows, E) | x (K, rows, V1)
+ *   train: + d z (K, rows, E) | d c (rows, K) | 64 MiB of split-K scratch for the weight gradients.
+ * Expert k's rows lie at row k * rows + r of z and x, so the vocabulary projection is ONE product over K * rows rows.  No softmax
+ * of any expert is written: the mix kernels (one block of 256 per hidden row) take the K log-sum-exps, then stream the K expert
+ * rows once more, 16 B per lane when V1 % 4 == 0, V1 <= 10240 and the outputs are 16-B aligned with strides % 4 == 0, element-wise
+ * otherwise.  Reductions run in a fixed order: results are bitwise reproducible.
+ *
+ * rfn_mos_fwd: h (rows, ldh >= R) -> logp, row r at logp + (r % inner) * out_s_inner + (r / inner) * out_s_outer (the remap of
+ *   rfn_log_softmax_fwd: time-major rows r = s * B + b reach a (B, S, V1) tensor with inner = B, strides S * V1 and V1).  The
+ *   workspace keeps c, log pi, lse, z and x for rfn_mos_bwd whatever `train` is; `train` only sizes the backward's slabs.
+ * rfn_mos_loss_fwd: the masked, label-smoothed NLL of rfn_xe_logits_fwd straight from x, for time-major rows r = t * B + b:
+ *   loss_out[0] (+)= -sum mask * q . logp / B, summed in rfn_xe_logits_fwd's order; logp is never written.  scratch: B * T floats.
+ * rfn_mos_bwd: from d_logp (laid out as rfn_mos_fwd's logp) on the workspace either forward left.  Writes d x over x, then
+ *   d_h (rows, R) and every gradient slot (overwritten).  rfn_mos_loss_bwd: the same from (target, mask, eps, gscale *
+ *   gscale_dev[0]) on rfn_mos_loss_fwd's (or rfn_mos_fwd's) workspace; a row whose mask is 0 gets exactly zero in d x, d c and d_h.
+ *   Both need a workspace of the train size.
+ * RFN_ERR_SHAPE: rows (B, T) < 1, ldh < R, inner < 1, eps outside [0, 1).  RFN_ERR_ARG: a NULL pointer (gscale_dev may be
+ * NULL), a workspace that is not 16-B aligned.  RFN_ERR_WORKSPACE: ws_bytes below rfn_mos_ws_bytes. */
+#define RFN_MOS_MAXK 16
+typedef struct rfn_mos_dims {
+    int32_t R, E, K, V1;
+} rfn_mos_dims;
+int rfn_mos_param_count(const rfn_mos_dims* md);
+int rfn_mos_param_name(const rfn_mos_dims* md, int idx, char* buf, size_t buflen);
+int rfn_mos_param_shape(const rfn_mos_dims* md, int idx, int64_t* rows, int64_t* cols);
+size_t rfn_mos_ws_bytes(const rfn_mos_dims* md, int64_t rows, int train);
+/* addresses inside a workspace of `rows` rows: lse (K, rows), log pi (rows, K), x (K, rows, V1), d c (rows, K; train) */
+float* rfn_mos_ws_lse(const rfn_mos_dims* md, int64_t rows, void* ws);
+float* rfn_mos_ws_logpi(const rfn_mos_dims* md, int64_t rows, void* ws);
+float* rfn_mos_ws_x(const rfn_mos_dims* md, int64_t rows, void* ws);
+float* rfn_mos_ws_dc(const rfn_mos_dims* md, int64_t rows, void* ws);
+int rfn_mos_fwd(const rfn_mos_dims* md, int rows, const float* h, int64_t ldh, const float* const* params, int inner,
+                int64_t out_s_inner, int64_t out_s_outer, float* logp, void* ws, size_t ws_bytes, int train, void* stream);
+int rfn_mos_loss_fwd(const rfn_mos_dims* md, int B, int T, const float* h, int64_t ldh, const float* const* params,
+                     const int64_t* target, int64_t ld_target, const float* mask, int64_t ld_mask, float eps, float* scratch,
+                     float* loss_out, int accumulate_loss, void* ws, size_t ws_bytes, void* stream);
+int rfn_mos_bwd(const rfn_mos_dims* md, int rows, const float* h, int64_t ldh, const float* const* params, const float* d_logp,
+                int inner, int64_t s_inner, int64_t s_outer, float* d_h, float* const* grads, void* ws, size_t ws_bytes,
+                void* stream);
+int rfn_mos_loss_bwd(const rfn_mos_dims* md, int B, int T, const float* h, int64_t ldh, const float* const* params,
+                     const int64_t* target, int64_t ld_target, const float* mask, int64_t ld_mask, float eps, float gscale,
+                     const float* gscale_dev, float* d_h, float* const* grads, void* ws, size_t ws_bytes, void* stream);
+
+/* The decoder path beside such a head (additive; rfn_decoder_fwd_ex / _bwd_ex keep their launches and bits):
+ * rfn_decoder_fwd_hidden is rfn_decoder_fwd_ex (one row per image) stopped before the logit product; rfn_decoder_hidden returns
+ * the address of the (S * B, R) time-major rows r = s * B + b the logit layer would read -- under dropout the dropped-out
+ * outputs (misc/LSTMSoftAttentionCore.py:98-101).  rfn_decoder_bwd_hidden is rfn_decoder_bwd_ex started from d_hidden (S * B, R)
+ * in place of the log-softmax and logit-layer backward: the logit.* gradient slots are zero-filled, everything else is
+ * overwritten as there.  The workspace is rfn_decoder_ws_bytes's.  RFN_ERR_UNSUPPORTED with RFN_PATH_OPT_DEC_UNHOISTED or a
+ * persistent decoder chain (RFN_PATH_OPT_PERSIST_DEC_*). */
+int rfn_decoder_fwd_hidden(const rfn_dims* d, int B, int S, const float* const* params, const float* comb, const float* h0,
+                           const float* c0, const int64_t* ids, int64_t ld_ids, void* ws, size_t ws_bytes, int train,
+                           uint64_t seed, void* stream);
+float* rfn_decoder_hidden(const rfn_dims* d, int B, int S, int train, void* ws);
+int rfn_decoder_bwd_hidden(const rfn_dims* d, int B, int S, const float* const* params, const float* comb, const float* h0,
+                           const float* c0, const int64_t* ids, int64_t ld_ids, const float* d_hidden, float* d_comb,
+                           float* d_h0, float* d_c0, float* const* grads, void* ws, size_t ws_bytes, uint64_t seed,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,9 @@ from .show_tell import ShowTellModel, LanguageModelCriterion  # noqa: F401
 from .graphed import GraphedTrainStep  # noqa: F401
 from .distill import TopKTeacher  # noqa: F401
 from .decode import labels_from_seq  # noqa: F401
+from .mos import MixtureOfSoftmax  # noqa: F401
 
 __all__ = ['RecurrentFusionModel', 'ReviewNetEnsembleCriterion', 'ReviewNetRewardCriterion', 'clip_gradient',
            'FusedClampAdam', 'setup', 'FeatureFeeder', 'read_image_features', 'eval_step', 'unique_image_rows', 'ShowTellModel',
            'LanguageModelCriterion', 'GraphedTrainStep', 'eval_split', 'LanguageEval', 'DiversityEval',
-           'TopKTeacher', 'labels_from_seq']
+           'TopKTeacher', 'labels_from_seq', 'MixtureOfSoftmax']

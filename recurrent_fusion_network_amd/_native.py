@@ -110,6 +110,12 @@ class BeamStochastic(C.Structure):
                 ('weight', C.c_void_p), ('n_live', C.c_void_p), ('topk64', C.c_void_p)]
 
 
+class MosDims(C.Structure):
+    """rfn_mos_dims (rfn.h, "mixture of softmaxes")."""
+    _fields_ = [('R', C.c_int32), ('E', C.c_int32), ('K', C.c_int32), ('V1', C.c_int32)]
+
+
+MOS_MAXK = 16
 DECODE_MAX_IDS = 64
 LEX_MAX_SETS, LEX_MAX_IDS = 3, 16
 
@@ -126,6 +132,7 @@ def _load():
     P, I, L, F, SZ, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
     DP, CP, SP = C.POINTER(Dims), C.POINTER(DecodeConstraints), C.POINTER(DecodeSampling)
     BDP, BLP, BSP = C.POINTER(BeamDiversity), C.POINTER(BeamLexical), C.POINTER(BeamStochastic)
+    MP = C.POINTER(MosDims)
     sig = {
         'rfn_param_count': (C.c_int, [DP]),
         'rfn_param_name': (C.c_int, [DP, I, C.c_char_p, SZ]),
@@ -287,6 +294,22 @@ def _load():
         'rfn_score_captions': (C.c_int, [P, L, P, L, I, I, I, I, P, P, P]),
         'rfn_decoder_score_ws_bytes': (SZ, [DP, I, I, I]),
         'rfn_decoder_score': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, L, I, P, P, P, L, P, P, P, SZ, I, P]),
+        # mixture of softmaxes (rfn.h): the head, and the decoder pass without its output layer
+        'rfn_mos_param_count': (C.c_int, [MP]),
+        'rfn_mos_param_name': (C.c_int, [MP, I, C.c_char_p, SZ]),
+        'rfn_mos_param_shape': (C.c_int, [MP, I, C.POINTER(L), C.POINTER(L)]),
+        'rfn_mos_ws_bytes': (SZ, [MP, L, I]),
+        'rfn_mos_ws_lse': (P, [MP, L, P]),
+        'rfn_mos_ws_logpi': (P, [MP, L, P]),
+        'rfn_mos_ws_x': (P, [MP, L, P]),
+        'rfn_mos_ws_dc': (P, [MP, L, P]),
+        'rfn_mos_fwd': (C.c_int, [MP, I, P, L, P, I, L, L, P, P, SZ, I, P]),
+        'rfn_mos_loss_fwd': (C.c_int, [MP, I, I, P, L, P, P, L, P, L, F, P, P, I, P, SZ, P]),
+        'rfn_mos_bwd': (C.c_int, [MP, I, P, L, P, P, I, L, L, P, P, P, SZ, P]),
+        'rfn_mos_loss_bwd': (C.c_int, [MP, I, I, P, L, P, P, L, P, L, F, F, P, P, P, P, SZ, P]),
+        'rfn_decoder_fwd_hidden': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, SZ, I, U64, P]),
+        'rfn_decoder_hidden': (P, [DP, I, I, I, P]),
+        'rfn_decoder_bwd_hidden': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, P, P, P, P, SZ, U64, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -507,3 +530,91 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias=None) -> torch.Tensor:
     y = torch.empty(rows, N, device=x.device, dtype=torch.float32)
     gemm(rows, N, [(y, N, [(x, K, 1, weight, K, 1, K, bias)])])
     return y
+
+
+# ---- mixture-of-softmaxes head (rfn.h "mixture of softmaxes") ----------------------------------------------------------
+def mos_dims(R, E, K, V1) -> MosDims:
+    md = MosDims()
+    md.R, md.E, md.K, md.V1 = int(R), int(E), int(K), int(V1)
+    return md
+
+
+def mos_param_names(md: MosDims):
+    n = lib.rfn_mos_param_count(C.byref(md))
+    if n < 0:
+        check(n, 'rfn_mos_param_count')
+    buf = C.create_string_buffer(64)
+    out = []
+    for i in range(n):
+        check(lib.rfn_mos_param_name(C.byref(md), i, buf, 64), 'rfn_mos_param_name')
+        out.append(buf.value.decode())
+    return out
+
+
+def mos_param_shape(md: MosDims, idx: int):
+    r, c = C.c_int64(), C.c_int64()
+    check(lib.rfn_mos_param_shape(C.byref(md), idx, C.byref(r), C.byref(c)), 'rfn_mos_param_shape')
+    return r.value, c.value
+
+
+def mos_workspace(md: MosDims, rows: int, train: bool, device) -> torch.Tensor:
+    n = lib.rfn_mos_ws_bytes(C.byref(md), rows, int(train))
+    if n == 0:
+        raise RfnError('rfn_mos_ws_bytes: unsupported dimensions (R %d, E %d, K %d, V1 %d, rows %d)'
+                       % (md.R, md.E, md.K, md.V1, rows))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _mos_view(fn, md, rows, ws, shape):
+    """A float32 view of one slab of a head workspace (no copy)."""
+    off = fn(C.byref(md), rows, ws.data_ptr()) - ws.data_ptr()
+    n = 1
+    for s in shape:
+        n *= s
+    return ws[off:off + 4 * n].view(torch.float32).view(*shape)
+
+
+def mos_ws_lse(md, rows, ws):
+    return _mos_view(lib.rfn_mos_ws_lse, md, rows, ws, (md.K, rows))
+
+
+def mos_ws_logpi(md, rows, ws):
+    return _mos_view(lib.rfn_mos_ws_logpi, md, rows, ws, (rows, md.K))
+
+
+def mos_ws_x(md, rows, ws):
+    return _mos_view(lib.rfn_mos_ws_x, md, rows, ws, (md.K, rows, md.V1))
+
+
+def mos_ws_dc(md, rows, ws):
+    return _mos_view(lib.rfn_mos_ws_dc, md, rows, ws, (rows, md.K))
+
+
+def mos_fwd(md, h, params, logp, ws, inner=None, s_inner=None, s_outer=0, train=False):
+    """h (rows, R) with any row stride -> logp; by default row r of a contiguous (rows, V1) tensor."""
+    rows = h.shape[0]
+    if inner is None:
+        inner, s_inner, s_outer = rows, md.V1, 0
+    check(lib.rfn_mos_fwd(C.byref(md), rows, h.data_ptr(), h.stride(0), ptr_array(params), inner, s_inner, s_outer,
+                          logp.data_ptr(), ws.data_ptr(), ws.numel(), int(train), stream_ptr()), 'rfn_mos_fwd')
+
+
+def mos_bwd(md, h, params, d_logp, d_h, grads, ws, inner=None, s_inner=None, s_outer=0):
+    rows = h.shape[0]
+    if inner is None:
+        inner, s_inner, s_outer = rows, md.V1, 0
+    check(lib.rfn_mos_bwd(C.byref(md), rows, h.data_ptr(), h.stride(0), ptr_array(params), d_logp.data_ptr(), inner, s_inner,
+                          s_outer, d_h.data_ptr(), ptr_array(grads), ws.data_ptr(), ws.numel(), stream_ptr()), 'rfn_mos_bwd')
+
+
+def mos_loss_fwd(md, B, T, h, params, target, mask, eps, scratch, loss_out, ws, accumulate=False):
+    """h: (T * B, R) time-major rows; target (B, >= T) int64, mask (B, >= T) float32; loss_out: one float."""
+    check(lib.rfn_mos_loss_fwd(C.byref(md), B, T, h.data_ptr(), h.stride(0), ptr_array(params), target.data_ptr(),
+                               target.stride(0), mask.data_ptr(), mask.stride(0), float(eps), scratch.data_ptr(),
+                               loss_out.data_ptr(), int(accumulate), ws.data_ptr(), ws.numel(), stream_ptr()), 'rfn_mos_loss_fwd')
+
+
+def mos_loss_bwd(md, B, T, h, params, target, mask, eps, gscale, gscale_dev, d_h, grads, ws):
+    check(lib.rfn_mos_loss_bwd(C.byref(md), B, T, h.data_ptr(), h.stride(0), ptr_array(params), target.data_ptr(),
+                               target.stride(0), mask.data_ptr(), mask.stride(0), float(eps), float(gscale), ptr(gscale_dev),
+                               d_h.data_ptr(), ptr_array(grads), ws.data_ptr(), ws.numel(), stream_ptr()), 'rfn_mos_loss_bwd')

@@ -153,7 +153,7 @@ static int decoder_fwd_begin(const rfn_dims* d, int B, int n, const float* const
 // == NULL stops at the time-major logits (W + Lo.logits), with any n: rfn_decoder_score reads them there.
 static int decoder_fwd_body(const rfn_dims* d, int B, int S, int n, const float* const* prm, const float* comb, const float* h0,
                             const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob, float* W,
-                            const DecoderLayout& Lo, RfnSeed seed, void* st) {
+                            const DecoderLayout& Lo, RfnSeed seed, void* st, bool head = true) {
     const PIdx P(d);
     const int R = d->R, E = d->E, V1 = d->V1;
     const int GD = gate_width(d->decoder_maxout, R);
@@ -175,6 +175,7 @@ static int decoder_fwd_body(const rfn_dims* d, int B, int S, int n, const float*
             for (int s = 0; s < S; ++s) RFN_TRY(decoder_fwd_cell(d, B, 1, s, prm, comb, W, Lo, gx, seed, st));
         }
     }
+    if (!head) return RFN_OK;   // rfn_decoder_fwd_hidden: another output layer reads the rows at W + Lo.hd + B * R
     // logits of all steps, then log-softmax written in the reference's (B, S, V+1) layout
     RFN_TRY(gemm_logits(S * B, V1, W + Lo.hd + (long)B * R, R, prm[P.logit_w()], prm[P.logit_b()], W + Lo.logits, gx_whole));
     if (log_prob) RFN_TRY(rfn_log_softmax_fwd(W + Lo.logits, V1, S * B, V1, B, (long)S * V1, V1, log_prob, st));
@@ -224,6 +225,25 @@ extern "C" int rfn_decoder_fwd(const rfn_dims* d, int B, int S, const float* con
                                const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, float* log_prob,
                                void* ws, size_t ws_bytes, int train, uint64_t seed_arg, void* st) {
     return rfn_decoder_fwd_ex(d, B, S, prm, comb, h0, c0, ids, ld_ids, log_prob, ws, ws_bytes, train, seed_arg, 1, st);
+}
+
+// ---- the pass without its output layer (rfn.h "mixture of softmaxes"): the same launches as far as the last cell step -------
+extern "C" int rfn_decoder_fwd_hidden(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb, const float* h0,
+                                      const float* c0, const int64_t* ids, int64_t ld_ids, void* ws, size_t ws_bytes, int train,
+                                      uint64_t seed_arg, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    if (!dec_hoisted(d)) return RFN_ERR_UNSUPPORTED;
+    if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, 1);
+    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    return decoder_fwd_body(d, B, S, 1, prm, comb, h0, c0, ids, ld_ids, nullptr, (float*)ws, Lo, seed, st, false);
+}
+extern "C" float* rfn_decoder_hidden(const rfn_dims* d, int B, int S, int train, void* ws) {
+    if (check_dims(d) != RFN_OK || B < 1 || S < 1 || !ws) return nullptr;
+    return (float*)ws + decoder_layout(d, B, S, train).hd + (size_t)B * d->R;
 }
 
 extern "C" float* rfn_decoder_logits(const rfn_dims* d, int B, int S, int train, void* ws) {
@@ -519,4 +539,28 @@ extern "C" int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* 
     RFN_TRY(gemm_logits_dx(S * B, R, V1, dlg, prm[P.logit_w()], c.dhe, c.gx));
     RFN_TRY(dec_hoisted(d) ? c.sweep_hoisted() : c.sweep_unhoisted());
     return c.tail(dec_hoisted(d));
+}
+// The same sweep from a given d hidden (rfn.h "mixture of softmaxes"): the output layer's backward ran elsewhere.
+extern "C" int rfn_decoder_bwd_hidden(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                      const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, const float* d_hidden,
+                                      float* d_comb, float* d_h0, float* d_c0, float* const* grd, void* ws, size_t ws_bytes,
+                                      uint64_t seed_arg, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    if (!dec_hoisted(d)) return RFN_ERR_UNSUPPORTED;
+    if (!prm || !comb || !ids || !d_hidden || !d_comb || !d_h0 || !d_c0 || !grd || !ws) return RFN_ERR_ARG;
+    (void)h0; (void)c0;
+    const DecoderLayout Lo = decoder_layout(d, B, S, 1, 1);
+    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    float* W = (float*)ws;
+    DecBwd c{d, PIdx(d), B, 1, B, S, d->R, d->A, d->E, d->T2, d->V1, gate_width(d->decoder_maxout, d->R), (long)B * d->R, (long)B * d->A,
+             prm, comb, ids, ld_ids, d_comb, d_h0, d_c0, grd, W, Lo, seed, st, GemmCtx{},
+             W + Lo.hd, W + Lo.cd, W + Lo.gd, W + Lo.dhe, W + Lo.dhrec, W + Lo.dc, W + Lo.dz, W + Lo.dPd};
+    RFN_TRY(phase_gemm(d, W, Lo.gws, Lo.tk, true, st, &c.gx));
+    const PIdx& P = c.P;
+    RFN_TRY(mem_batch({{c.dhe, d_hidden, (long)S * c.BR}, {grd[P.logit_w()], nullptr, (long)d->V1 * d->R}, {grd[P.logit_b()], nullptr, (long)d->V1}}, st));
+    RFN_TRY(c.sweep_hoisted());
+    return c.tail(true);
 }

@@ -36,6 +36,17 @@ class _Stepper:
                                           self.cproj.data_ptr(), N.stream_ptr()), 'rfn_decoder_prepare')
         self.ws_bytes = N.lib.rfn_decoder_step_ws_bytes(C.byref(self.d), self.B)
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        # a mixture-of-softmaxes model (opt.use_mos): the cell runs with no logits and the head turns the new h into mixture
+        # log-probs, handed out in the place of the logits -- their log-softmax is themselves up to rounding, so the
+        # log-softmax / top-W / constraint kernels apply to them unchanged
+        self.mos = getattr(model, 'mos', None) if getattr(model, 'use_mos', 0) else None
+        if self.mos is not None:
+            model._mos_refuse_path_flags()
+            self.mos_params = model._params_of(model._mos_slots)
+            self.mos_ws = N.mos_workspace(self.mos.md, self.B, False, dev)
+
+    def _head(self, out):
+        N.mos_fwd(self.mos.md, self.h, self.mos_params, out, self.mos_ws, self.B, out.stride(0), 0)
 
     def step(self, ids, out=None, want='logp'):
         """ids: int64 token ids (B,) -- or an already embedded float input (B, E), as the reference's one_time_step."""
@@ -44,8 +55,9 @@ class _Stepper:
             raise N.RfnError('a stepper whose rows share thought vectors (beam search) is driven by rfn_beam_loop only')
         if out is None:
             out = torch.empty(self.B, V1, device=self.h.device)
-        logits_ptr = out.data_ptr() if want == 'logits' else None
-        logp_ptr = out.data_ptr() if want == 'logp' else None
+        head = self.mos is not None
+        logits_ptr = out.data_ptr() if want == 'logits' and not head else None
+        logp_ptr = out.data_ptr() if want == 'logp' and not head else None
         if ids.is_floating_point():
             xt = N.require_cuda_f32(ids, 'xt')
             if tuple(xt.shape) != (self.B, self.d.E):
@@ -57,6 +69,8 @@ class _Stepper:
                                                     self.t, N.stream_ptr()),
                     'rfn_decoder_step_embedded')
             self.t += 1
+            if head:
+                self._head(out)
             return out
         if ids.dtype != torch.long or not ids.is_contiguous():
             ids = ids.long().contiguous()
@@ -65,6 +79,8 @@ class _Stepper:
                                        logits_ptr, logp_ptr, out.stride(0), self.ws.data_ptr(), self.ws_bytes,
                                        self.seed, self.t, N.stream_ptr()), 'rfn_decoder_step')
         self.t += 1
+        if head:
+            self._head(out)
         return out
 
     def reorder(self, order):
@@ -113,11 +129,73 @@ class GreedyBuffers:
         return seq[:, :t_stop - 1], seq_lp[:, :t_stop - 1], logp[:, :t_stop].contiguous()
 
 
+def _refuse_mos_device_loop(stepper, what):
+    if getattr(stepper, 'mos', None) is not None:
+        raise N.RfnError('use_mos: %s runs the logit layer inside the device loop; a mixture-of-softmaxes model decodes through '
+                         'the host-stepped loops' % what)
+
+
+def host_greedy_loop(step, B, S, V1, dev, cons=None):
+    """The greedy free-running loop stepped from the host (the ensemble's, and a mixture-of-softmaxes model's): step(ids, out)
+    runs one decoder step of every row on the tokens `ids` (B,) and leaves the rows' pre-softmax logits in out (B, V1); the
+    log-softmax, the constraints and the pick are kernels, and nothing is read back -> the filled GreedyBuffers (read_back()
+    is the call's one synchronisation).  cons: a parsed _Constraints or None, applied to the log-probs."""
+    st = N.stream_ptr()
+    logits = torch.empty(B, V1, device=dev)
+    bufs = GreedyBuffers(B, S, V1, dev, bos=True)      # `it` = the BOS token fed at t = 0
+    logp_all, seq, seq_lp, unf, it = bufs.logp_all, bufs.seq, bufs.seq_lp, bufs.unf, bufs.it
+    if cons is not None:
+        cons.bind(B, dev)
+    for t in range(S + 1):
+        if t >= 1:
+            prev = logp_all[:, t - 1]
+            if cons is not None:
+                cons.blocklist(seq, seq.stride(0), 1, t)
+                cons.mask(prev)
+            N.check(N.lib.rfn_greedy_pick(prev.data_ptr(), prev.stride(0), B, V1, t, it.data_ptr(),
+                                          seq[:, t - 1].data_ptr(), seq.stride(0), seq_lp[:, t - 1].data_ptr(),
+                                          seq_lp.stride(0), unf[t - 1].data_ptr() if t > 1 else None,
+                                          unf[t].data_ptr(), st), 'rfn_greedy_pick')
+        step(it, logits)
+        out = logp_all[:, t]
+        N.check(N.lib.rfn_log_softmax_fwd(logits.data_ptr(), V1, B, V1, B, out.stride(0), 0, out.data_ptr(), st))
+    return bufs
+
+
+def host_beam_loop(step, reorder, B, W, S, V1, dev, cons=None, div=None):
+    """The beam search stepped from the host on B * W rows (row k * W + q = image k): step(ids, out) as in host_greedy_loop on
+    out (B * W, V1); reorder(order) re-gathers the rows' decoder state after a fork.  The candidate / stable-sort / fork /
+    done-beam rules run on the device (rfn_beam_step_topk / _div) on the W best entries of each row's log-softmax
+    (rfn_log_softmax_topk, masked under constraints) -> the filled BeamBuffers for _sorted_done_beams."""
+    st = N.stream_ptr()
+    b = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
+    rows = b.rows
+    topv, topi = b.top_lists()
+    logits = torch.empty(rows, V1, device=dev)
+    if cons is not None:
+        cons.bind(rows, dev)
+    for t in range(S + 1):
+        if t >= 1:
+            b.step(topv, topi, V1, t, div)
+            if t == S:
+                break                      # the reference runs one more decoder step whose output is never used
+            reorder(b.order)
+        step(b.ids, logits)
+        if cons is not None:     # the lists of step t + 1 from the beam arrays rfn_beam_step_topk has just forked
+            cons.blocklist(b.bs, 1, rows, t + 1)
+            cons.topk(logits, W, topv, topi)
+        else:
+            N.check(N.lib.rfn_log_softmax_topk(logits.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
+                    'rfn_log_softmax_topk')
+    return b
+
+
 def run_greedy_loop(stepper, bufs, mode, inv_temp, u, cons, samp=None):
     """The whole free-running loop (pick, embed, cell, logit, log-softmax) in one call.  mode 0: greedy; 1: draw with the
     uniforms u (S, B) at inverse temperature inv_temp.  cons: a parsed _Constraints or None; samp: a parsed _Sampling or None
     (with samp.n > 1 the stepper's B rows are n per thought vector, image-major)."""
     b, B = bufs, stepper.B
+    _refuse_mos_device_loop(stepper, 'rfn_decoder_loop')
     N.check(N.lib.rfn_decoder_loop_ex2(C.byref(stepper.d), B, b.S + 1, stepper.table, stepper.comb.data_ptr(),
                                        stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), mode, inv_temp,
                                        N.ptr(u), b.logp_all.data_ptr(), b.logp_all.stride(0), b.logp_all.stride(1),
@@ -188,6 +266,7 @@ def run_beam_loop(stepper, bufs, cons, div=None, lex=None, sbs_seed=None):
     None (bufs then holds state_n / done_state); sbs_seed: the 64-bit key of the Gumbel noise of a stochastic search (bufs is then
     a StochasticBuffers; the stepper's own seed keys the dropout masks, as everywhere)."""
     b, logp = bufs, bufs.top_flat()
+    _refuse_mos_device_loop(stepper, 'rfn_beam_loop')
     h_alt, c_alt = torch.empty_like(stepper.h), torch.empty_like(stepper.c)
     N.check(N.lib.rfn_beam_loop_ex4(C.byref(stepper.d), b.B, b.W, b.S, stepper.table, stepper.comb.data_ptr(),
                                     stepper.cproj.data_ptr(), stepper.h.data_ptr(), stepper.c.data_ptr(), h_alt.data_ptr(),

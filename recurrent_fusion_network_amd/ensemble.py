@@ -17,8 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .decode import (MAX_BEAM, MAX_STEPS, BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity,
-                     _length_penalty, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, keep_candidates_n)
+from .decode import (MAX_BEAM, MAX_STEPS, _Consensus, _Constraints, _diverse_beams, _Diversity, _length_penalty, _Scoring,
+                     _sorted_done_beams, _Stepper, ScoreBuffers, host_beam_loop, host_greedy_loop, keep_candidates_n)
 
 
 # Every entry point takes `att_lens` as RecurrentFusionModel's do (INTEGRATION.md "Ragged attention maps"): the per-image row counts
@@ -79,26 +79,8 @@ class EnsembleDecoder:
         cons = _Constraints.parse(opt, V1, S)
         steppers = self._steppers(fc_feats, att_feats, att_lens)
         dev = steppers[0].h.device
-        st = N.stream_ptr()
-        logit_sum = torch.empty(B, V1, device=dev)
         logit_m = torch.empty(B, V1, device=dev)
-        bufs = GreedyBuffers(B, S, V1, dev, bos=True)      # `it` = the BOS token fed at t = 0
-        logp_all, seq, seq_lp, unf, it = bufs.logp_all, bufs.seq, bufs.seq_lp, bufs.unf, bufs.it
-        if cons is not None:
-            cons.bind(B, dev)
-        for t in range(S + 1):
-            if t >= 1:
-                prev = logp_all[:, t - 1]
-                if cons is not None:
-                    cons.blocklist(seq, seq.stride(0), 1, t)
-                    cons.mask(prev)
-                N.check(N.lib.rfn_greedy_pick(prev.data_ptr(), prev.stride(0), B, V1, t, it.data_ptr(),
-                                              seq[:, t - 1].data_ptr(), seq.stride(0), seq_lp[:, t - 1].data_ptr(),
-                                              seq_lp.stride(0), unf[t - 1].data_ptr() if t > 1 else None,
-                                              unf[t].data_ptr(), st), 'rfn_greedy_pick')
-            self._averaged_step(steppers, it, logit_sum, logit_m)
-            out = logp_all[:, t]
-            N.check(N.lib.rfn_log_softmax_fwd(logit_sum.data_ptr(), V1, B, V1, B, out.stride(0), 0, out.data_ptr(), st))
+        bufs = host_greedy_loop(lambda ids, out: self._averaged_step(steppers, ids, out, logit_m), B, S, V1, dev, cons)
         return bufs.read_back()        # nothing is read back before this: the call synchronises here, once
 
     @torch.no_grad()
@@ -206,28 +188,12 @@ class EnsembleDecoder:
         keep = None if keep_n is None else {'n': keep_n}
         steppers = self._steppers(fc_feats, att_feats, att_lens, W)       # row k * W + q = image k
         dev = steppers[0].h.device
-        st = N.stream_ptr()
-        b = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1)
-        rows = b.rows
-        topv, topi = b.top_lists()
-        logit_sum = torch.empty(rows, V1, device=dev)
-        logit_m = torch.empty(rows, V1, device=dev)
-        if cons is not None:
-            cons.bind(rows, dev)
-        for t in range(S + 1):
-            if t >= 1:
-                b.step(topv, topi, V1, t, div)
-                if t == S:
-                    break                      # the reference runs one more decoder step whose output is never used
-                for sp in steppers:
-                    sp.reorder(b.order)
-            self._averaged_step(steppers, b.ids, logit_sum, logit_m)
-            if cons is not None:     # the lists of step t + 1 from the beam arrays rfn_beam_step_topk has just forked
-                cons.blocklist(b.bs, 1, rows, t + 1)
-                cons.topk(logit_sum, W, topv, topi)
-            else:
-                N.check(N.lib.rfn_log_softmax_topk(logit_sum.data_ptr(), V1, rows, V1, W, topv.data_ptr(), topi.data_ptr(), st),
-                        'rfn_log_softmax_topk')
+        logit_m = torch.empty(B * W, V1, device=dev)
+
+        def reorder(order):
+            for sp in steppers:
+                sp.reorder(order)
+        b = host_beam_loop(lambda ids, out: self._averaged_step(steppers, ids, out, logit_m), reorder, B, W, S, V1, dev, cons, div)
         seq, seq_lp, top_seq, top_prob, self.done_beams = _sorted_done_beams(b, alpha, cs, div.groups if div is not None else 1, keep)
         self.consensus = cs.result if cs is not None else None
         self.candidates = None if keep is None else {'seq': keep['seq'], 'n_cand': keep['n_cand']}

@@ -24,7 +24,9 @@ from . import _native as N
 from .distill import TopKTeacher
 from .decode import (MAX_BEAM, MAX_STEPS, BeamBuffers, GreedyBuffers, _Consensus, _Constraints, _diverse_beams, _Diversity, _LazyList,
                      _length_penalty, _Lexical, _Sampling, _Scoring, _sorted_done_beams, _Stepper, ScoreBuffers, early_exit,
-                     keep_candidates_n, run_beam_loop, run_greedy_loop, _Stochastic, StochasticBuffers)
+                     host_beam_loop, host_greedy_loop, keep_candidates_n, run_beam_loop, run_greedy_loop, _Stochastic,
+                     StochasticBuffers)
+from .mos import MixtureOfSoftmax, _MosFn
 
 _INIT = 0.1
 
@@ -395,6 +397,72 @@ class _DecoderLossFn(torch.autograd.Function):
         return (None,) * 10 + (d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
 
 
+class _HiddenFn(torch.autograd.Function):
+    """Phase 2 without its output layer, for a model whose head is a mixture of softmaxes (rfn.h "mixture of softmaxes"):
+    rfn_decoder_fwd_hidden -> the (S * B, R) time-major rows the logit layer would read (a copy: the head's node keeps them);
+    backward runs rfn_decoder_bwd_hidden from the head's d hidden.  The logit.* gradient slots of the decoder bucket are
+    zero-filled: `logit` stays in the model, unused, as in the reference (misc/ReviewNetModel.py:59-60)."""
+
+    @staticmethod
+    def _run(model, d, B, S, table, comb, h0, c0, ids, ws, train, seed):
+        N.check(N.lib.rfn_decoder_fwd_hidden(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                             ids.data_ptr(), ids.stride(0), ws.data_ptr(), ws.numel(), int(train), seed,
+                                             N.stream_ptr()), 'rfn_decoder_fwd_hidden')
+
+    @staticmethod
+    def forward(ctx, model, save_bwd, drop, seed, ids, comb, h0, c0, *params):
+        d = model._dims_for(drop)
+        train = bool(save_bwd)
+        B, S = ids.shape
+        dev = comb.device
+        comb, h0, c0, ids = comb.contiguous(), h0.contiguous(), c0.contiguous(), ids.contiguous()
+        table = model._param_table(params, model._decoder_slots)
+        ws = torch.empty(N.lib.rfn_decoder_ws_bytes(C.byref(d), B, S, int(train)), dtype=torch.uint8, device=dev)
+        _HiddenFn._run(model, d, B, S, table, comb, h0, c0, ids, ws, train, seed)
+        off = N.lib.rfn_decoder_hidden(C.byref(d), B, S, int(train), ws.data_ptr()) - ws.data_ptr()
+        hidden = ws[off:off + 4 * S * B * d.R].view(torch.float32).view(S * B, d.R).clone()
+        if train:
+            ctx.model, ctx.seed, ctx.B, ctx.S, ctx.drop = model, seed, B, S, drop
+            ctx.ids, ctx.params, ctx.consumed = ids, params, False
+            ctx.save_for_backward(comb, h0, c0, ws)
+        return hidden
+
+    @staticmethod
+    def backward(ctx, d_hidden):
+        model, B, S = ctx.model, ctx.B, ctx.S
+        comb, h0, c0, ws = ctx.saved_tensors
+        d = model._dims_for(ctx.drop)
+        dev = comb.device
+        table = model._param_table(ctx.params, model._decoder_slots)
+        flats, by_slot, gtable = model._grad_buffers(['decoder'], dev)
+        if ctx.consumed:      # a second backward over the same graph: recompute the pass first (see _PrefixFn.backward)
+            _HiddenFn._run(model, d, B, S, table, comb, h0, c0, ctx.ids, ws, True, ctx.seed)
+        ctx.consumed = True
+        d_hidden = d_hidden.contiguous()
+        d_comb, d_h0, d_c0 = torch.empty_like(comb), torch.empty_like(h0), torch.empty_like(c0)
+        N.check(N.lib.rfn_decoder_bwd_hidden(C.byref(d), B, S, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(),
+                                             ctx.ids.data_ptr(), ctx.ids.stride(0), d_hidden.data_ptr(), d_comb.data_ptr(),
+                                             d_h0.data_ptr(), d_c0.data_ptr(), gtable, ws.data_ptr(), ws.numel(), ctx.seed,
+                                             N.stream_ptr()), 'rfn_decoder_bwd_hidden')
+        model._bucket_done('decoder', flats['decoder'])
+        return (None, None, None, None, None, d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
+
+
+class _MosBucketGrads:
+    """Gradient sink of the model's head (mos._MosFn): the flat 'mos' bucket, handed over like every other bucket."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def buffers(self, dev):
+        self.flats, by_slot, _ = self.model._grad_buffers(['mos'], dev)
+        return [by_slot[s] for s in self.model._mos_slots]
+
+    def done(self):
+        self.model._bucket_done('mos', self.flats['mos'])
+        return (None,) * len(self.model._mos_slots)
+
+
 class RecurrentFusionModel(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -434,6 +502,12 @@ class RecurrentFusionModel(nn.Module):
                                            for _ in range(self.num_review_steps)])
         self.reason_linear = nn.Linear(R, self.top_words_count)
         self.decoder = _DecoderParams(E, R, A, self.decoder_maxout)
+        # opts.py --use_mos / --num_expert: a mixture-of-softmaxes head in place of log_softmax(logit(h)); `logit` stays,
+        # unused, as in the reference (misc/ReviewNetModel.py:59-60,122-125)
+        self.use_mos = int(getattr(opt, 'use_mos', 0) or 0)
+        if self.use_mos:
+            self.num_expert = int(getattr(opt, 'num_expert', 10))
+            self.mos = MixtureOfSoftmax(R, R, self.num_expert, self.vocab_size + 1)
         self.init_weights()
 
         # RFN_GEMM_OPT_* bits handed to every GEMM of the path (rfn.h); a data-parallel host sets
@@ -444,18 +518,25 @@ class RecurrentFusionModel(nn.Module):
         self._dims = {}
         self._param_cache = {}
         self._slot_names = N.param_names(self._dims_for(False))
+        # the head's parameters follow the path's slots (the path's tables are indexed by slot and never read beyond their own)
+        self._mos_slots = []
+        if self.use_mos:
+            self._mos_slots = list(range(len(self._slot_names), len(self._slot_names) + len(self.mos.slot_names)))
+            self._slot_names = self._slot_names + ['mos.' + n for n in self.mos.slot_names]
         schema = dict(self.named_parameters())
         missing = [n for n in self._slot_names if n not in schema]
         if missing or len(schema) != len(self._slot_names):
             raise N.RfnError('parameter schema mismatch between module and librfn_hip.so: %s' % missing[:3])
         is_dec = lambda n: n.startswith(('embed.', 'logit.', 'decoder.'))  # noqa: E731
-        self._prefix_slots = [i for i, n in enumerate(self._slot_names) if not is_dec(n)]
+        self._prefix_slots = [i for i, n in enumerate(self._slot_names) if not is_dec(n) and not n.startswith('mos.')]
         self._decoder_slots = [i for i, n in enumerate(self._slot_names) if is_dec(n)]
         # gradient buckets, in the order their gradients become final during backward: the decoder, the
         # fusion "core" (everything of phase 1 except the per-encoder stage-I weights) and two buckets per
         # encoder (rfn_prefix_bwd_wgrad parts 1 and 2; all a-buckets are produced before the first b-bucket).  Each bucket is one flat buffer = one all-reduce = one Adam launch.
         enc_re = re.compile(r'^review_steps_individual\.\d+\.lstm\.(\d+)\.(att_model\.att_2_att_h|att_model\.h_2_att_h|H2h|z2h)\.')
         self._bucket_slots = {'decoder': list(self._decoder_slots), 'core': []}
+        if self.use_mos:
+            self._bucket_slots['mos'] = list(self._mos_slots)    # the head's bucket: final before the decoder's
         for i in range(M):
             self._bucket_slots['enc%da' % i] = []    # H2h, z2h, h_2_att_h of encoder i (rfn_prefix_bwd_wgrad part 1)
             self._bucket_slots['enc%db' % i] = []    # att_2_att_h of encoder i            (part 2)
@@ -581,7 +662,7 @@ class RecurrentFusionModel(nn.Module):
         return table
 
     def bucket_names(self):
-        return ['decoder'] + list(self._prefix_buckets)
+        return (['mos'] if self.use_mos else []) + ['decoder'] + list(self._prefix_buckets)
 
     def bucket_layout(self, name):
         """(params, offsets, total) of one bucket: parameters back to back, each start 16-B aligned."""
@@ -695,7 +776,50 @@ class RecurrentFusionModel(nn.Module):
             self._prefix_cache = ([weakref.ref(t) for t in ins], stamp, tuple(o.detach() for o in out))
         return out
 
+    # ---- mixture-of-softmaxes head (opt.use_mos) ---------------------------------------------------------------------
+    def _mos_refuse(self, option, why):
+        """What a mixture-of-softmaxes model does not do yet is refused by name, never silently run through the logit layer."""
+        if self.use_mos:
+            raise ValueError('use_mos: %s is not available for a mixture-of-softmaxes model (%s)' % (option, why))
+
+    def _mos_refuse_path_flags(self):
+        bad = int(self.path_flags) & (N.PATH_OPT_PERSIST_ALL | N.PATH_OPT_DEC_UNHOISTED)
+        if self.use_mos and bad:
+            raise N.RfnError('use_mos: path_flags selects RFN_PATH_OPT_PERSIST_* / RFN_PATH_OPT_DEC_UNHOISTED (bits %d); the '
+                             'decoder pass without its output layer takes the hoisted cell only' % bad)
+
+    def _decode_hidden(self, ids, comb, h, c, drop, seed):
+        """-> the (S * B, R) time-major rows the output layer reads (rfn_decoder_fwd_hidden), one autograd node."""
+        self._mos_refuse_path_flags()
+        params = self._params_of(self._decoder_slots)
+        return _HiddenFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids, comb, h, c, *params)
+
+    def _mos_head(self, hidden, spec):
+        params = self._params_of(self._mos_slots)
+        return _MosFn.apply(self.mos.md, spec, _MosBucketGrads(self), torch.is_grad_enabled(), hidden, *params)
+
+    @torch.no_grad()
+    def decoder_hidden(self, fc_feats, att_feats, seq, att_lens=None):
+        """The decoder's outputs on the ground-truth prefix, before any output layer -> (B, S, R), S as forward finds it: the
+        rows `logit` (or the mixture-of-softmaxes head) reads, under dropout the dropped-out ones.  A probing utility; runs
+        under no_grad in the module's mode."""
+        train = bool(self.training)
+        seed = self._step_seed(train)
+        S = self._decoder_steps(seq)
+        comb, h, c, _ = self._prefix(fc_feats, att_feats, train, seed, att_lens)
+        dev = comb.device
+        hidden = _HiddenFn.apply(self, False, train, seed, seq[:, :S].to(dev).long(), comb, h, c, *self._params_of(self._decoder_slots))
+        return hidden.view(S, seq.size(0), self.rnn_size).transpose(0, 1).contiguous()
+
     def _decode_teacher_forced(self, ids, comb, h, c, drop, seed, ss_prob=0.0, n=1):
+        if self.use_mos:
+            if ss_prob > 0:
+                self._mos_refuse('ss_prob > 0', 'scheduled sampling steps through the logit layer')
+            if n != 1:
+                self._mos_refuse('n rows per image', 'the pass without its output layer carries one row per image')
+            B, S, V1 = ids.size(0), ids.size(1), self.vocab_size + 1
+            hidden = self._decode_hidden(ids, comb, h, c, drop, seed)
+            return self._mos_head(hidden, {'kind': 'logp', 'shape': (B, S, V1), 'inner': B, 's_inner': S * V1, 's_outer': V1})
         params = self._params_of(self._decoder_slots)
         return _DecoderFn.apply(self, torch.is_grad_enabled(), bool(drop), seed, ids, comb, h, c, float(ss_prob), 1.0, n,
                                 *params)[0]
@@ -730,6 +854,7 @@ class RecurrentFusionModel(nn.Module):
         S = self._decoder_steps(seq)          # may read `seq` back once: do it before queueing phase 1
         g = int(self.dedup_seq_per_img)
         if g > 1:
+            self._mos_refuse('dedup_seq_per_img', 'the fan-out of one image\'s rows was not taught the head')
             if train and (self.drop_prob_fusion > 0 or self.drop_prob_reason > 0):
                 raise N.RfnError('dedup_seq_per_img needs drop_prob_fusion = drop_prob_reason = 0')
             rows, n_feat = seq.size(0), fc_feats[0].size(0)
@@ -804,6 +929,13 @@ class RecurrentFusionModel(nn.Module):
         cache on disk.  Same arguments, same `last_distill`, same refusals; the meaning is the dense teacher's with -inf off
         the K ids (the K entries are renormalised; the tail mass is dropped)."""
         from .criteria import _MLMFn
+        if self.use_mos:
+            if teacher is not None:
+                self._mos_refuse('teacher=', 'the distillation kernels read the logit layer\'s rows')
+            if self.ss_prob > 0:
+                self._mos_refuse('ss_prob > 0', 'scheduled sampling steps through the logit layer')
+            if int(self.dedup_seq_per_img) > 1:
+                self._mos_refuse('dedup_seq_per_img', 'the fan-out of one image\'s rows was not taught the head')
         if teacher is not None:
             if self.ss_prob > 0:
                 raise N.RfnError('distillation does not combine with scheduled sampling (ss_prob = %g): the teacher\'s rows are '
@@ -837,9 +969,14 @@ class RecurrentFusionModel(nn.Module):
         if masks.stride(1) != 1:
             masks = masks.contiguous()
         eps = float(crit.label_smoothing_epsilon) if crit.use_label_smoothing else 0.0
-        params = self._params_of(self._decoder_slots)
-        lang = _DecoderLossFn.apply(self, torch.is_grad_enabled(), train, seed, seq[:, :S], seq[:, 1:S + 1], masks[:, 1:S + 1], eps,
-                                    kd, terms, comb, h, c, *params)
+        if self.use_mos:      # hidden pass + the head's loss form: neither log_prob nor its gradient is materialised
+            hidden = self._decode_hidden(seq[:, :S], comb, h, c, train, seed)
+            lang = self._mos_head(hidden, {'kind': 'loss', 'B': seq.size(0), 'T': S, 'target': seq[:, 1:S + 1],
+                                           'mask': masks[:, 1:S + 1], 'eps': eps})
+        else:
+            params = self._params_of(self._decoder_slots)
+            lang = _DecoderLossFn.apply(self, torch.is_grad_enabled(), train, seed, seq[:, :S], seq[:, 1:S + 1], masks[:, 1:S + 1],
+                                        eps, kd, terms, comb, h, c, *params)
         if teacher is not None:
             self.last_distill = {'xe': terms[0], 'kd': terms[1]} if kd is not None else {'xe': lang.detach(), 'kd': None}
         heads = list(reason.unbind(0))
@@ -988,6 +1125,11 @@ class RecurrentFusionModel(nn.Module):
         beam_size = opt.get('beam_size', 1)
         temperature = opt.get('temperature', 1.0)
         samp = _Sampling.parse(opt)
+        if self.use_mos and beam_size <= 1:
+            if not sample_max:
+                self._mos_refuse('sample_max = 0', 'the sampled pass draws inside the step-wise decoder, logit layer included')
+            if torch.is_grad_enabled():
+                self._mos_refuse('sample under grad', 'greedy decoding is stepped from the host: call it under no_grad')
         if beam_size > 1:
             if samp is not None:
                 raise ValueError('top_k / top_p / sample_n apply to multinomial sampling, not to beam search')
@@ -1017,6 +1159,12 @@ class RecurrentFusionModel(nn.Module):
         force = opt.get('force_ids', None)
         if (not sample_max and cons is None and samp is None) or force is not None:
             out = self._sample_replayed(comb, h, c, train, seed, want_grad, temperature, force)
+        elif self.use_mos:       # greedy, stepped from the host: the loop EnsembleDecoder.sample runs (decode.host_greedy_loop)
+            with torch.no_grad():
+                stepper = _Stepper(self, comb.detach(), h.detach().clone(), c.detach().clone(), train, seed)
+                bufs = host_greedy_loop(lambda ids, o: stepper.step(ids, out=o, want='logits'), h.size(0), self.seq_length,
+                                        self.vocab_size + 1, comb.device, cons)
+                out = bufs.read_back()
         else:
             out = self._sample_device_loop(comb, h, c, train, seed, sample_max, temperature, cons, samp, cs)
         return (*out, reason_pred)
@@ -1034,6 +1182,7 @@ class RecurrentFusionModel(nn.Module):
         under no_grad.  opt: 'temperature', and 'force_ids' (B*n, S) to replay given tokens teacher-forced; every other
         decoding key is refused.  n = 1 is sample(..., {'sample_max': 0}) bit for bit.  The uniforms hook `_ss_uniforms` is
         (2, S+1, B*n)."""
+        self._mos_refuse('sample_group', 'the differentiated sampled pass steps through the logit layer')
         n = int(n)
         if n < 1:
             raise ValueError('sample_group draws n >= 1 captions per image (got %d)' % n)
@@ -1074,6 +1223,7 @@ class RecurrentFusionModel(nn.Module):
         restricted distribution is not renormalised.  Every other key raises ValueError by name.  Runs under no_grad only; dropout
         follows the module's mode, as in sample_beam.  n <= 32, seq_length <= 64; needs the hoisted decoder cell.  EnsembleDecoder
         has no such method, and no gradient estimator is built on the weights."""
+        self._mos_refuse('sample_distinct', 'stochastic beam search is a device loop with the logit layer inside')
         B, S, V1 = self._check_inputs(fc_feats, att_feats), self.seq_length, self.vocab_size + 1
         sb = _Stochastic.parse(opt, n, S)
         if sb.n > V1:
@@ -1186,6 +1336,9 @@ class RecurrentFusionModel(nn.Module):
         d = self._dims_for(False)
         table = self._param_table(self._params_of(self._decoder_slots), self._decoder_slots)
         per_call = so.rows_per_call(n, S, V1)
+        if self.use_mos:      # the head's K expert rows per caption row: K times fewer rows per call
+            per_call = max(n, per_call // self.num_expert // n * n)
+            return self._score_mos(bufs, so, comb, h, c, rows, n, per_call)
         ws_bytes = N.lib.rfn_decoder_score_ws_bytes(C.byref(d), min(rows, per_call), S, n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         for r0 in range(0, rows, per_call):
@@ -1196,6 +1349,29 @@ class RecurrentFusionModel(nn.Module):
                                             bufs.feed.stride(0), sl(bufs.target), bufs.target.stride(0), int(so.include_end),
                                             sl(bufs.tok_lp), sl(bufs.rank), sl(bufs.ent), bufs.tok_lp.stride(0), sl(bufs.cap_lp),
                                             sl(bufs.cap_len), ws.data_ptr(), ws_bytes, n, N.stream_ptr()), 'rfn_decoder_score')
+        return bufs.result()
+
+    def _score_mos(self, bufs, so, comb, h, c, rows, n, per_call):
+        """score() of a mixture-of-softmaxes model: the hidden pass, the head's time-major log-prob rows in the place of the
+        logits (their log-sum-exp is 0 up to rounding), then rfn_score_logits / rfn_score_captions as rfn_decoder_score runs
+        them.  With n > 1 an image's thought vectors are repeated physically (the hidden pass carries one row per image)."""
+        S, V1, st = bufs.steps, self.vocab_size + 1, N.stream_ptr()
+        md, params = self.mos.md, self._params_of(self._mos_slots)
+        for r0 in range(0, rows, per_call):
+            r1 = min(rows, r0 + per_call)
+            m = r1 - r0
+            cb = comb[:, r0 // n:r1 // n]
+            if n > 1:
+                cb = cb.repeat_interleave(n, dim=1)
+            hidden = self._decode_hidden(bufs.feed[r0:r1, :S], cb.contiguous(), h[r0:r1], c[r0:r1], False, 0)
+            logp = torch.empty(S * m, V1, device=hidden.device)
+            N.mos_fwd(md, hidden, params, logp, N.mos_workspace(md, S * m, False, hidden.device))
+            sl = lambda t: N.ptr(None if t is None else t[r0:r1])  # noqa: E731
+            N.check(N.lib.rfn_score_logits(logp.data_ptr(), V1, m, S, 0, V1, sl(bufs.target), bufs.target.stride(0),
+                                           int(so.include_end), sl(bufs.tok_lp), sl(bufs.rank), sl(bufs.ent), bufs.tok_lp.stride(0), st),
+                    'rfn_score_logits')
+            N.check(N.lib.rfn_score_captions(sl(bufs.tok_lp), bufs.tok_lp.stride(0), sl(bufs.target), bufs.target.stride(0), m, S, V1,
+                                             int(so.include_end), sl(bufs.cap_lp), sl(bufs.cap_len), st), 'rfn_score_captions')
         return bufs.result()
 
     def sample_beam(self, fc_feats, att_feats, opt={}, att_lens=None):
@@ -1239,6 +1415,7 @@ class RecurrentFusionModel(nn.Module):
         if lex is not None and (div is not None or cs is not None):
             raise ValueError('require cannot be combined with group_size > 1 or consensus')
         if lex is not None:
+            self._mos_refuse('require', 'lexically constrained beam search is a device loop with the logit layer inside')
             self._need_hoisted('require needs', N.PATH_OPT_DEC_UNHOISTED, ValueError)
         keep_n = keep_candidates_n(opt, beam_size)
         keep = None if keep_n is None else {'n': keep_n}
@@ -1249,11 +1426,17 @@ class RecurrentFusionModel(nn.Module):
             seed = _fresh_seed() if drop else 0
             comb_b, h_b, c_b, reason = self._prefix(fc_feats, att_feats, drop, seed, att_lens)
             dev = comb_b.device
-            # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
-            stepper = _Stepper(self, comb_b, h_b.repeat_interleave(W, dim=0).contiguous(),
-                               c_b.repeat_interleave(W, dim=0).contiguous(), drop, seed)
-            bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1, lex.G if lex is not None else 1)
-            run_beam_loop(stepper, bufs, cons, div, lex.bind(dev) if lex is not None else None)
+            h_w, c_w = h_b.repeat_interleave(W, dim=0).contiguous(), c_b.repeat_interleave(W, dim=0).contiguous()
+            if self.use_mos:     # stepped from the host: the loop EnsembleDecoder.sample_beam runs (decode.host_beam_loop); a
+                # host-stepped stepper's rows do not share thought vectors, so they are repeated physically
+                stepper = _Stepper(self, comb_b.repeat_interleave(W, dim=1), h_w, c_w, drop, seed)
+                bufs = host_beam_loop(lambda ids, o: stepper.step(ids, out=o, want='logits'), stepper.reorder, B, W, S, V1, dev,
+                                      cons, div)
+            else:
+                # the W beam rows of image k (rows k*W .. k*W+W-1) read the image's thought vectors: comb stays (T2, B, R)
+                stepper = _Stepper(self, comb_b, h_w, c_w, drop, seed)
+                bufs = BeamBuffers(B, W, S, dev, div.groups if div is not None else 1, lex.G if lex is not None else 1)
+                run_beam_loop(stepper, bufs, cons, div, lex.bind(dev) if lex is not None else None)
             lex_out = {} if lex is not None else None
             seq, seq_lp, top_seq, top_prob, done_beams = _sorted_done_beams(bufs, alpha, cs, div.groups if div is not None else 1, keep,
                                                                             lex_out)

@@ -112,6 +112,8 @@ class GraphedTrainStep:
 
     def _check_capturable(self):
         model = self.model
+        if getattr(model, 'use_mos', 0):
+            raise N.RfnError('GraphedTrainStep: use_mos -- the captured step was not taught the mixture-of-softmaxes head')
         if model.grad_ready_hook is not None:
             raise N.RfnError('GraphedTrainStep: a grad_ready_hook (parallel.GradSync) cannot be combined with a captured step')
         if self.device_rng:
