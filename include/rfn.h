@@ -821,6 +821,33 @@ int rfn_rl_loss_ex(const float* input, int64_t ld_in, const int64_t* seq, int64_
                    float entropy_reg, const float* old_logprobs, int64_t ld_old, int use_ppo, float ppo_clip,
                    const float* gscale_dev, float* scratch, float* loss_out, int accumulate_loss, float* d_input,
                    int64_t ld_din, float* d_logprobs_all, int64_t dlp_sb, int64_t dlp_st, void* stream);
+/* ---- policy-gradient loss from the logits ----------------------------------------------------------------------------------
+ * The same policy + entropy terms straight from the LOGITS of a teacher-forced replay of given captions (the loss of
+ * RecurrentFusionModel.rl_loss): neither logprobs_all (B, T, V+1) nor its gradient exists, so captions drawn by the no-grad
+ * device loops (rfn_decoder_loop_ex2, the beam loops, stochastic beam search) can be trained on.  `logits`: time-major rows
+ * r = t * B + b with row stride ldl, as rfn_xe_logits_* take them.  Per row, with lp_v = x_v - lse, p_v = exp(lp_v),
+ * tok = seq[b, t] (clamped into [0, V1) as rfn_xe_logits_* clamp targets), m0 = seq[b, t] > 0, mk = 1 at t == 0 and
+ * seq[b, t - 1] > 0 after it, rw = reward[b * ld_rw + t]:
+ *   Hm   = sum_v lp_v * p_v                                  (only evaluated where entropy_reg * m0 != 0; 0 otherwise)
+ *   pol  = lp_tok * rw, or rfn_rl_loss's PPO-clip surrogate of lp_tok, old_logprobs[b, t] and ppo_clip (it clamps surr1)
+ *   loss_out[0] (+)= sum_{b,t} ( -pol * mk + entropy_reg * m0 * Hm ) / B     (rfn_rl_loss's loss; terms summed in a fixed order)
+ *   d x_v = a * ([v == tok] - p_v) + e * p_v * (lp_v - Hm),  a = -(g / B) * mk * d pol / d lp_tok,  e = (g / B) * entropy_reg * m0
+ * _fwd: row_stats (3*T*B floats) = lse, Hm, lp_tok as T*B time-major rows; tok_lp (B, ld_tok_lp >= T) = lp_tok, the expression
+ * x[tok] - lse: the bits rfn_log_softmax_fwd writes at that position; scratch: B*T floats, 3*B*T with terms_out; terms_out (may be
+ * NULL) = {sum -pol * mk / B, sum entropy_reg * m0 * Hm / B}, the two terms each summed on its own.  _bwd overwrites the logits with
+ * d loss / d logits, g = gscale * gscale_dev[0] (gscale_dev may be NULL), from the same seq / reward / old_logprobs and _fwd's
+ * row_stats.  A row with a == 0 and e == 0 (mk == 0 and m0 == 0; a zero reward without an entropy term) is written as exact
+ * zeros; with e == 0 the entropy expression is not evaluated.  No atomics: two runs give the same bits.  Rows are read 16 B per
+ * lane under rfn_xe_logits_*'s conditions and element-wise otherwise.
+ * RFN_ERR_SHAPE: B, T or V1 < 1, ldl < V1, ld_tok_lp < T.  RFN_ERR_ARG: a NULL pointer (old_logprobs may be NULL unless
+ * use_ppo; gscale_dev and terms_out may be NULL).  Shape checks come first. */
+int rfn_rl_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* seq, int64_t ld_seq,
+                      const float* reward, int64_t ld_rw, float entropy_reg, const float* old_logprobs, int64_t ld_old,
+                      int use_ppo, float ppo_clip, float* row_stats, float* tok_lp, int64_t ld_tok_lp, float* scratch,
+                      float* loss_out, int accumulate_loss, float* terms_out, void* stream);
+int rfn_rl_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* seq, int64_t ld_seq,
+                      const float* reward, int64_t ld_rw, float entropy_reg, const float* old_logprobs, int64_t ld_old,
+                      int use_ppo, float ppo_clip, const float* row_stats, float gscale, const float* gscale_dev, void* stream);
 /* nn.MultiLabelMarginLoss, mean reduction (misc/utils.py:186-190), scaled by `scale`:
  * loss_out[0] (+)= scale * MLM(pred, target); dpred (overwritten) = scale * gscale * dMLM/dpred. */
 int rfn_multilabel_margin(const float* pred, int B, int K, const int64_t* target, float scale,
@@ -1524,6 +1551,37 @@ int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* para
  * both outputs NULL. */
 int rfn_scst_reward_group(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, int B, int n, int T,
                           int baseline, float* out, double* out64, void* stream);
+/* The logits-only pair with n rows per image (additive: rfn_decoder_fwd_ex / _bwd_ex keep refusing log_prob == NULL with n > 1).
+ * rfn_decoder_logits_fwd issues rfn_decoder_fwd_ex's launches as far as the logit product and leaves the time-major rows
+ * r = t * B + b at rfn_decoder_logits_ex(d, B, S, train, n, ws) (row stride V1); the workspace is rfn_decoder_ws_bytes_ex(d, B, S,
+ * train, n) bytes and train = 1 keeps what the backward needs.  rfn_decoder_logits_bwd is rfn_decoder_bwd_ex started from the
+ * d loss / d logits a criterion left over those rows (rfn_xe_logits_bwd, rfn_rl_logits_bwd): the log-softmax backward is the only
+ * step that reads log_prob, everything behind it takes its row counts from B and n.  d_comb comes back (T2, B / n, R), summed
+ * over each image's rows.  n > 1 needs the hoisted cell (RFN_ERR_UNSUPPORTED), shapes and pointers are checked as in the _ex
+ * forms. */
+int rfn_decoder_logits_fwd(const rfn_dims* d, int B, int S, const float* const* params, const float* comb /* (T2,B/n,R) */,
+                           const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids, void* ws, size_t ws_bytes,
+                           int train, uint64_t seed, int rows_per_image, void* stream);
+float* rfn_decoder_logits_ex(const rfn_dims* d, int B, int S, int train, int rows_per_image, void* ws);
+int rfn_decoder_logits_bwd(const rfn_dims* d, int B, int S, const float* const* params, const float* comb, const int64_t* ids,
+                           int64_t ld_ids, float* d_comb /* (T2,B/n,R) */, float* d_h0, float* d_c0, float* const* grads, void* ws,
+                           size_t ws_bytes, uint64_t seed, int rows_per_image, void* stream);
+/* The reward of a DISTINCT-sample set: the n rows of image k are a sample without replacement (stochastic beam search) with
+ * importance weights w (rfn_beam_step_sbs's `weight`, B doubles).  The normalised importance-weighted policy-gradient estimator
+ * with its built-in baseline (Kool, van Hoof and Welling, "Stochastic Beams and Where to Find Them", ICML 2019).  With
+ * s_j = ((bleu4_j * bleu4_weight) + (cider_j * cider_weight)) + 0.0 (a NULL scorer is 0 * weight), over the rows of the image
+ * with w_j > 0 only, j ascending:
+ *   Wsum = ((0.0 + w_j0) + w_j1) + ...        q_j = w_j / Wsum        base = ((0.0 + q_j0 * s_j0) + q_j1 * s_j1) + ...  (baseline 1)
+ *   reward[k*n+j, :] = (q_j * (s_j - base)) * n, broadcast over T;      baseline 0: base = 0.
+ * Rows with w_j <= 0 (dead rows, the threshold row) or a NaN weight enter no sum and get exactly 0.0 whatever their score; an
+ * image without a weighted row, or with a non-finite Wsum, gets zeros.  The factor n puts the reward on the group step's scale:
+ * the criterion divides by B = images * n, and sum_j q_j stands where the group step has (1 / n) sum_j.  A NaN score on a
+ * weighted row poisons its own image only.  fp64, every sum, product and quotient rounded on its own; out / out64 as above; one
+ * launch, no allocation, no synchronisation.
+ * RFN_ERR_SHAPE: B < 1, T < 1, n < 1, B % n != 0, baseline not 0 or 1, baseline 1 with n < 3 (n = 2 leaves one weighted row,
+ * whose coefficient is identically 0).  RFN_ERR_ARG: both scores NULL, weight NULL or both outputs NULL. */
+int rfn_scst_reward_distinct(const double* cider, double cider_weight, const double* bleu, double bleu4_weight, const double* weight,
+                             int B, int n, int T, int baseline, float* out, double* out64, void* stream);
 
 /* ---- consensus reranking (minimum-Bayes-risk decoding under CIDEr-D; off by default, the reference has none) ---------------------
  * Of the n candidate captions of an image, keep the one that agrees most with the others under CIDEr-D (csrc/rfn_reward.hip).

@@ -310,6 +310,14 @@ def _load():
         'rfn_decoder_fwd_hidden': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, SZ, I, U64, P]),
         'rfn_decoder_hidden': (P, [DP, I, I, I, P]),
         'rfn_decoder_bwd_hidden': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, P, P, P, P, P, SZ, U64, P]),
+        # policy-gradient loss from the logits (rfn.h): the criterion pair, the logits-only decoder pair with rows_per_image, and
+        # the reward of a distinct-sample set
+        'rfn_rl_logits_fwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, I, F, P, P, L, P, P, I, P, P]),
+        'rfn_rl_logits_bwd': (C.c_int, [P, L, I, I, I, P, L, P, L, F, P, L, I, F, P, F, P, P]),
+        'rfn_decoder_logits_fwd': (C.c_int, [DP, I, I, P, P, P, P, P, L, P, SZ, I, U64, I, P]),
+        'rfn_decoder_logits_ex': (P, [DP, I, I, I, I, P]),
+        'rfn_decoder_logits_bwd': (C.c_int, [DP, I, I, P, P, P, L, P, P, P, P, P, SZ, U64, I, P]),
+        'rfn_scst_reward_distinct': (C.c_int, [P, C.c_double, P, C.c_double, P, I, I, I, I, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

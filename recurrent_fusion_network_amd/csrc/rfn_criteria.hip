@@ -704,6 +704,195 @@ extern "C" int rfn_rl_loss(const float* input, int64_t ld_in, const int64_t* seq
                           ld_din, d_logprobs_all, dlp_sb, dlp_st, stream);
 }
 
+// ---- the same criterion straight from the logits (rfn.h rfn_rl_logits_fwd; misc/utils.py:50-72 on F.log_softmax rows) ---------
+// Rows as the XE pair takes them (x = the time-major logits row r = t * B + b), tok = seq[b, t] clamped as its targets are;
+// m0, mk, pol exactly as rl_loss_k writes them, on lp_tok = x[tok] - lse (the bits rfn_log_softmax_fwd puts there).
+//   forward : lse (log_softmax_row), Hm = sum_v lp_v * exp(lp_v) (only where entropy_reg * m0 != 0, else 0), lp_tok
+//             -> row_stats[0 / 1 / 2][r]; tok_lp[b, t] = lp_tok; -pol * mk + entropy_reg * m0 * Hm -> row_loss[b * T + t]
+//             (and, when the caller wants the two terms for logging, each on its own -> row_terms[0 / 1][b * T + t])
+//   backward: d x_v = a * ([v == tok] - p_v) + e * p_v * (lp_v - Hm), written over the logits; a = -(g / B) * mk * d pol / d lp_tok,
+//             e = (g / B) * entropy_reg * m0.  a == 0 and e == 0: exact zeros; e == 0: the entropy term is not evaluated.
+struct RlRow {
+    long tok;
+    float m0, mk, rw, old;
+};
+__device__ __forceinline__ RlRow rl_row(const int64_t* __restrict__ seq, long ld_seq, const float* __restrict__ reward, long ld_rw,
+                                        const float* __restrict__ old_lp, long ld_old, int use_ppo, int b, int t, int V1) {
+    RlRow q;
+    const int64_t s = seq[b * ld_seq + t];
+    q.tok = (s < 0 || s >= V1) ? 0 : (long)s;
+    q.m0 = (s > 0) ? 1.f : 0.f;
+    q.mk = (t == 0) ? 1.f : ((seq[b * ld_seq + t - 1] > 0) ? 1.f : 0.f);
+    q.rw = reward[b * ld_rw + t];
+    q.old = use_ppo ? old_lp[b * ld_old + t] : 0.f;
+    return q;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void rl_logits_fwd_k(const float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ seq, long ld_seq,
+                                                       const float* __restrict__ reward, long ld_rw, float entropy_reg,
+                                                       const float* __restrict__ old_lp, long ld_old, int use_ppo, float ppo_clip,
+                                                       float* __restrict__ row_stats, float* __restrict__ tok_lp, long ld_tl,
+                                                       float* __restrict__ row_loss, float* __restrict__ row_terms) {
+    __shared__ float red[4];
+    const int r = blockIdx.x, t = r / B, b = r - t * B;      // time-major rows
+    const float* x = logits + r * ldl;
+    f32x4 xr[LSM_R4];
+    const float lse = log_softmax_row<VEC>(x, V1, xr, red);
+    const RlRow q = rl_row(seq, ld_seq, reward, ld_rw, old_lp, ld_old, use_ppo, b, t, V1);
+    float Hm = 0.f;
+    if (entropy_reg != 0.f && q.m0 != 0.f) {                 // block-uniform
+        float s = 0.f;
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+#pragma unroll
+            for (int j = 0; j < LSM_R4; ++j)
+                if (threadIdx.x + 256 * j < n4) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float lp = xr[j][e] - lse;
+                        s += lp * expf(lp);
+                    }
+                }
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) {
+                const float lp = x[v] - lse;
+                s += lp * expf(lp);
+            }
+        }
+        Hm = block_sum_256(s, red);
+    }
+    if (threadIdx.x == 0) {
+        const float lpt = x[q.tok] - lse;
+        float pol;
+        if (use_ppo) {
+            const float ratio = expf(lpt) / (1e-5f + expf(q.old));
+            const float s1 = ratio * q.rw;
+            const float s2 = fminf(fmaxf(s1, 1.f - ppo_clip), 1.f + ppo_clip) * q.rw;
+            pol = fminf(s1, s2);
+        } else {
+            pol = lpt * q.rw;
+        }
+        const long n = (long)T * B;
+        row_stats[r] = lse;
+        row_stats[n + r] = Hm;
+        row_stats[2 * n + r] = lpt;
+        tok_lp[b * ld_tl + t] = lpt;
+        row_loss[b * T + t] = -pol * q.mk + entropy_reg * q.m0 * Hm;
+        if (row_terms) {                                     // the two terms on their own, for logging
+            row_terms[b * T + t] = -pol * q.mk;
+            row_terms[n + b * T + t] = entropy_reg * q.m0 * Hm;
+        }
+    }
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void rl_logits_bwd_k(float* __restrict__ logits, long ldl, int B, int T, int V1,
+                                                       const int64_t* __restrict__ seq, long ld_seq,
+                                                       const float* __restrict__ reward, long ld_rw, float entropy_reg,
+                                                       const float* __restrict__ old_lp, long ld_old, int use_ppo, float ppo_clip,
+                                                       float gcoef, const float* __restrict__ gdev,
+                                                       const float* __restrict__ row_stats) {
+    const int r = blockIdx.x, t = r / B, b = r - t * B;
+    float* x = logits + r * ldl;
+    const RlRow q = rl_row(seq, ld_seq, reward, ld_rw, old_lp, ld_old, use_ppo, b, t, V1);
+    const long n = (long)T * B;
+    const float gc = gdev ? gcoef * gdev[0] : gcoef;         // d loss / B, read on the device
+    float a = 0.f;
+    if (q.mk != 0.f) {
+        float dpol = q.rw;
+        if (use_ppo) {                                       // rl_loss_k's d_inp
+            const float ratio = expf(row_stats[2 * n + r]) / (1e-5f + expf(q.old));
+            const float s1 = ratio * q.rw;
+            const float s2 = fminf(fmaxf(s1, 1.f - ppo_clip), 1.f + ppo_clip) * q.rw;
+            const float ds1 = ratio * q.rw;
+            const float ds2 = (s1 > 1.f - ppo_clip && s1 < 1.f + ppo_clip) ? ds1 * q.rw : 0.f;
+            dpol = (s1 <= s2) ? ds1 : ds2;
+        }
+        a = -gc * q.mk * dpol;
+    }
+    const float e = (q.m0 != 0.f && entropy_reg != 0.f) ? gc * entropy_reg * q.m0 : 0.f;
+    if (a == 0.f && e == 0.f) {                              // exact zeros (block-uniform): masked rows, zero rewards
+        if constexpr (VEC) {
+            const int n4 = V1 >> 2;
+            for (int i = threadIdx.x; i < n4; i += 256) *reinterpret_cast<f32x4*>(x + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            for (int v = threadIdx.x; v < V1; v += 256) x[v] = 0.f;
+        }
+        return;
+    }
+    const float lse = row_stats[r], Hm = row_stats[n + r];
+    const long tok = q.tok;
+    auto grad = [&](float xv, bool is_tok) {
+        const float lp = xv - lse;
+        const float p = expf(lp);
+        const float pg = a * ((is_tok ? 1.f : 0.f) - p);
+        return (e != 0.f) ? pg + e * p * (lp - Hm) : pg;     // e == 0: no trace of the entropy term
+    };
+    if constexpr (VEC) {
+        const int n4 = V1 >> 2;
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+            f32x4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = grad(v[k], 4 * i + k == tok);
+            *reinterpret_cast<f32x4*>(x + 4 * i) = o;
+        }
+    } else {
+        for (int v = threadIdx.x; v < V1; v += 256) x[v] = grad(x[v], v == tok);
+    }
+}
+static int rl_logits_check(const void* logits, int64_t ldl, int B, int T, int V1, const void* seq, const void* reward,
+                           const void* old_logprobs, int use_ppo, const void* row_stats) {
+    if (B <= 0 || T <= 0 || V1 <= 0 || ldl < V1) return RFN_ERR_SHAPE;
+    if (!logits || !seq || !reward || !row_stats || (use_ppo && !old_logprobs)) return RFN_ERR_ARG;
+    return RFN_OK;
+}
+extern "C" int rfn_rl_logits_fwd(const float* logits, int64_t ldl, int B, int T, int V1, const int64_t* seq, int64_t ld_seq,
+                                 const float* reward, int64_t ld_rw, float entropy_reg, const float* old_logprobs, int64_t ld_old,
+                                 int use_ppo, float ppo_clip, float* row_stats, float* tok_lp, int64_t ld_tok_lp, float* scratch,
+                                 float* loss_out, int accumulate_loss, float* terms_out, void* stream) {
+    const int rc = rl_logits_check(logits, ldl, B, T, V1, seq, reward, old_logprobs, use_ppo, row_stats);
+    if (rc != RFN_OK) return rc;
+    if (ld_tok_lp < T) return RFN_ERR_SHAPE;
+    if (!tok_lp || !scratch || !loss_out) return RFN_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    float* row_terms = terms_out ? scratch + (size_t)B * T : nullptr;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(rl_logits_fwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, seq, (long)ld_seq,
+                           reward, (long)ld_rw, entropy_reg, old_logprobs, (long)ld_old, use_ppo, ppo_clip, row_stats, tok_lp,
+                           (long)ld_tok_lp, scratch, row_terms);
+    else
+        hipLaunchKernelGGL(rl_logits_fwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, seq, (long)ld_seq,
+                           reward, (long)ld_rw, entropy_reg, old_logprobs, (long)ld_old, use_ppo, ppo_clip, row_stats, tok_lp,
+                           (long)ld_tok_lp, scratch, row_terms);
+    RFN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, scratch, B * T, 1.0f / (float)B, loss_out, accumulate_loss);
+    RFN_CHECK_LAUNCH();
+    for (int k = 0; terms_out && k < 2; ++k) {
+        hipLaunchKernelGGL(sum_k, dim3(1), dim3(256), 0, st, row_terms + (size_t)k * B * T, B * T, 1.0f / (float)B, terms_out + k, 0);
+        RFN_CHECK_LAUNCH();
+    }
+    return RFN_OK;
+}
+extern "C" int rfn_rl_logits_bwd(float* logits, int64_t ldl, int B, int T, int V1, const int64_t* seq, int64_t ld_seq,
+                                 const float* reward, int64_t ld_rw, float entropy_reg, const float* old_logprobs, int64_t ld_old,
+                                 int use_ppo, float ppo_clip, const float* row_stats, float gscale, const float* gscale_dev,
+                                 void* stream) {
+    const int rc = rl_logits_check(logits, ldl, B, T, V1, seq, reward, old_logprobs, use_ppo, row_stats);
+    if (rc != RFN_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (lsm_vec_ok(logits, ldl, V1, nullptr, 0, 0))
+        hipLaunchKernelGGL(rl_logits_bwd_k<true>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, seq, (long)ld_seq,
+                           reward, (long)ld_rw, entropy_reg, old_logprobs, (long)ld_old, use_ppo, ppo_clip, gscale / (float)B,
+                           gscale_dev, row_stats);
+    else
+        hipLaunchKernelGGL(rl_logits_bwd_k<false>, dim3(B * T), dim3(256), 0, st, logits, (long)ldl, B, T, V1, seq, (long)ld_seq,
+                           reward, (long)ld_rw, entropy_reg, old_logprobs, (long)ld_old, use_ppo, ppo_clip, gscale / (float)B,
+                           gscale_dev, row_stats);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
 // ---- nn.MultiLabelMarginLoss (mean) -----------------------------------------------------------------
 // Row b: targets = ids before the first -1; loss_b = sum_{j in targets} sum_{i not target}
 // max(0, 1 - x[j] + x[i]) / K.  One block per row; hit counts per target through LDS integer atomics.

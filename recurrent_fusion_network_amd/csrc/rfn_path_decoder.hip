@@ -509,19 +509,11 @@ extern "C" int rfn_decoder_bwd(const rfn_dims* d, int B, int S, const float* con
     return rfn_decoder_bwd_ex(d, B, S, prm, comb, h0, c0, ids, ld_ids, log_prob, d_log_prob, d_comb, d_h0, d_c0, grd, ws, ws_bytes,
                               seed_arg, 1, st);
 }
-extern "C" int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
-                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids,
-                                  const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0, float* d_c0,
-                                  float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg, int rows_per_image, void* st) {
-    RFN_TRY(check_dims(d));
-    RfnSeed seed;
-    RFN_TRY(path_seed(d, seed_arg, &seed));
-    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
-    const int n = rows_per_image;
-    RFN_TRY(rows_per_image_ok(d, B, n));
-    if (!prm || !comb || !ids || (!log_prob != !d_log_prob) || !d_comb || !d_h0 || !d_c0 || !grd || !ws || (n > 1 && !log_prob))
-        return RFN_ERR_ARG;
-    (void)h0; (void)c0;
+// The backward pass on a checked call.  d_log_prob == NULL: the logits rows of the workspace already hold d logits, with any n
+// (nothing below the log-softmax backward reads log_prob, and every later step takes its row counts from B and n).
+static int decoder_bwd_body(const rfn_dims* d, int B, int S, int n, const float* const* prm, const float* comb, const int64_t* ids,
+                            int64_t ld_ids, const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0, float* d_c0,
+                            float* const* grd, void* ws, size_t ws_bytes, RfnSeed seed, void* st) {
     const DecoderLayout Lo = decoder_layout(d, B, S, 1, n);
     if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
     float* W = (float*)ws;
@@ -539,6 +531,56 @@ extern "C" int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* 
     RFN_TRY(gemm_logits_dx(S * B, R, V1, dlg, prm[P.logit_w()], c.dhe, c.gx));
     RFN_TRY(dec_hoisted(d) ? c.sweep_hoisted() : c.sweep_unhoisted());
     return c.tail(dec_hoisted(d));
+}
+extern "C" int rfn_decoder_bwd_ex(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,
+                                  const float* h0, const float* c0, const int64_t* ids, int64_t ld_ids,
+                                  const float* log_prob, const float* d_log_prob, float* d_comb, float* d_h0, float* d_c0,
+                                  float* const* grd, void* ws, size_t ws_bytes, uint64_t seed_arg, int rows_per_image, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !ids || (!log_prob != !d_log_prob) || !d_comb || !d_h0 || !d_c0 || !grd || !ws || (n > 1 && !log_prob))
+        return RFN_ERR_ARG;
+    (void)h0; (void)c0;
+    return decoder_bwd_body(d, B, S, n, prm, comb, ids, ld_ids, log_prob, d_log_prob, d_comb, d_h0, d_c0, grd, ws, ws_bytes, seed, st);
+}
+
+// ---- the logits-only pair with n rows per image (rfn.h "policy-gradient loss from the logits") --------------------------------
+// rfn_decoder_fwd_ex with log_prob == NULL and rfn_decoder_bwd_ex from the d logits in the workspace, for any rows_per_image:
+// the launches of those two calls, nothing else.  rfn_decoder_logits_ex: where the time-major rows lie under that layout.
+extern "C" int rfn_decoder_logits_fwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb, const float* h0,
+                                      const float* c0, const int64_t* ids, int64_t ld_ids, void* ws, size_t ws_bytes, int train,
+                                      uint64_t seed_arg, int rows_per_image, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !h0 || !c0 || !ids || !ws) return RFN_ERR_ARG;
+    const DecoderLayout Lo = decoder_layout(d, B, S, train, n);
+    if (ws_bytes < Lo.total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    return decoder_fwd_body(d, B, S, n, prm, comb, h0, c0, ids, ld_ids, nullptr, (float*)ws, Lo, seed, st);
+}
+extern "C" float* rfn_decoder_logits_ex(const rfn_dims* d, int B, int S, int train, int rows_per_image, void* ws) {
+    if (check_dims(d) != RFN_OK || B < 1 || S < 1 || rows_per_image < 1 || B % rows_per_image || !ws) return nullptr;
+    return (float*)ws + decoder_layout(d, B, S, train, rows_per_image).logits;
+}
+extern "C" int rfn_decoder_logits_bwd(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb, const int64_t* ids,
+                                      int64_t ld_ids, float* d_comb, float* d_h0, float* d_c0, float* const* grd, void* ws,
+                                      size_t ws_bytes, uint64_t seed_arg, int rows_per_image, void* st) {
+    RFN_TRY(check_dims(d));
+    RfnSeed seed;
+    RFN_TRY(path_seed(d, seed_arg, &seed));
+    if (B < 1 || S < 1) return RFN_ERR_SHAPE;
+    const int n = rows_per_image;
+    RFN_TRY(rows_per_image_ok(d, B, n));
+    if (!prm || !comb || !ids || !d_comb || !d_h0 || !d_c0 || !grd || !ws) return RFN_ERR_ARG;
+    if (ws_bytes < decoder_layout(d, B, S, 1, n).total * sizeof(float)) return RFN_ERR_WORKSPACE;
+    return decoder_bwd_body(d, B, S, n, prm, comb, ids, ld_ids, nullptr, nullptr, d_comb, d_h0, d_c0, grd, ws, ws_bytes, seed, st);
 }
 // The same sweep from a given d hidden (rfn.h "mixture of softmaxes"): the output layer's backward ran elsewhere.
 extern "C" int rfn_decoder_bwd_hidden(const rfn_dims* d, int B, int S, const float* const* prm, const float* comb,

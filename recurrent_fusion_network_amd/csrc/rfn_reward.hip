@@ -638,6 +638,56 @@ __global__ void rw_reward_group_k(const double* __restrict__ cider, double cider
     if (out64) out64[g] = v;
 }
 
+// ---- the reward of a distinct-sample set (rfn.h rfn_scst_reward_distinct) -----------------------------------------------------------
+// The n rows of an image are a sample WITHOUT replacement (stochastic beam search, rfn_beam_step_sbs) with importance weights w_j:
+// the normalised importance-weighted policy-gradient estimator with its built-in baseline of Kool, van Hoof and Welling,
+// "Stochastic Beams and Where to Find Them" (ICML 2019), section 4.2 / appendix: q_j = w_j / sum_i w_i over the rows with w > 0,
+// base = sum_j q_j * s_j, coefficient q_j * (s_j - base), times n so that the criterion's 1 / (images * n) leaves sum_j q_j in the
+// place of the group step's (1 / n) sum_j.  Rows with w <= 0 (dead rows, the threshold row) or a NaN weight enter no sum and get 0.0.
+__device__ __forceinline__ double rw_mixed_score(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu,
+                                                 double bleu4_weight, int r) {
+#pragma clang fp contract(off)
+    const double sb = bleu ? bleu[(long)r * RW_N + 3] : 0.0;
+    const double sc = cider ? cider[r] : 0.0;
+    const double tb = sb * bleu4_weight, tc = sc * cider_weight;
+    return (tb + tc) + 0.0;
+}
+__global__ void rw_reward_distinct_k(const double* __restrict__ cider, double cider_weight, const double* __restrict__ bleu,
+                                     double bleu4_weight, const double* __restrict__ weight, int B, int n, int T, int baseline,
+                                     float* __restrict__ out, double* __restrict__ out64) {
+#pragma clang fp contract(off)
+    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (long)B * T) return;
+    const int r = (int)(g / T), k0 = r - r % n;
+    double v = 0.0;
+    const double w = weight[r];
+    if (w > 0.0) {
+        double wsum = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double wi = weight[k0 + i];
+            if (wi > 0.0) wsum = wsum + wi;
+        }
+        if (wsum - wsum == 0.0) {                 // finite (w > 0 rows exist: this one)
+            double base = 0.0;
+            if (baseline)
+                for (int i = 0; i < n; ++i) {
+                    const double wi = weight[k0 + i];
+                    if (wi > 0.0) {
+                        const double qi = wi / wsum;
+                        const double term = qi * rw_mixed_score(cider, cider_weight, bleu, bleu4_weight, k0 + i);
+                        base = base + term;
+                    }
+                }
+            const double q = w / wsum;
+            const double diff = rw_mixed_score(cider, cider_weight, bleu, bleu4_weight, r) - base;
+            const double c = q * diff;
+            v = c * (double)n;
+        }
+    }
+    if (out) out[g] = (float)v;
+    if (out64) out64[g] = v;
+}
+
 // ---- consensus (minimum-Bayes-risk) reranking (rfn.h "consensus reranking") ---------------------------------------------------
 // The n candidates of an image are cooked ONCE as that image's "references" (rw_refs_k, cd_ref_vec_k); cd_pair_k then walks
 // candidate i against every candidate j with cd_pair_term, the loop body of cd_hyp_k, so a pair is cd_hyp_k's bits.
@@ -1297,6 +1347,18 @@ extern "C" int rfn_scst_reward_group(const double* cider, double cider_weight, c
     const long cnt = (long)B * T;
     rw_reward_group_k<<<rfn_cdiv(cnt, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, B, n, T, baseline,
                                                                           out, out64);
+    RFN_CHECK_LAUNCH();
+    return RFN_OK;
+}
+
+extern "C" int rfn_scst_reward_distinct(const double* cider, double cider_weight, const double* bleu, double bleu4_weight,
+                                        const double* weight, int B, int n, int T, int baseline, float* out, double* out64,
+                                        void* stream) {
+    if (B < 1 || T < 1 || n < 1 || B % n || (baseline != 0 && baseline != 1) || (baseline == 1 && n < 3)) return RFN_ERR_SHAPE;
+    if ((!cider && !bleu) || !weight || (!out && !out64)) return RFN_ERR_ARG;
+    const long cnt = (long)B * T;
+    rw_reward_distinct_k<<<rfn_cdiv(cnt, 256), 256, 0, (hipStream_t)stream>>>(cider, cider_weight, bleu, bleu4_weight, weight, B, n, T,
+                                                                             baseline, out, out64);
     RFN_CHECK_LAUNCH();
     return RFN_OK;
 }

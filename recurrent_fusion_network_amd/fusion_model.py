@@ -397,6 +397,85 @@ class _DecoderLossFn(torch.autograd.Function):
         return (None,) * 10 + (d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
 
 
+class _DecoderRLFn(torch.autograd.Function):
+    """Phase 2 + the policy and entropy terms of the RL criterion as ONE autograd node, _DecoderLossFn's shape with n rows per
+    image: rfn_decoder_logits_fwd stops at the time-major logits, rfn_rl_logits_fwd turns them into the loss, the rows' statistics
+    and the tokens' log-probs; backward writes d logits over the logits (rfn_rl_logits_bwd, scaled by the upstream gradient read
+    on the device) and rfn_decoder_logits_bwd runs from there.  Neither logprobs_all (rows, T, V+1) nor its gradient exists
+    (misc/RecurrentFusionModel.py:623-658 replayed teacher-forced + misc/utils.py:50-72).
+
+    `rl` = (seq (B, T) int64, reward (B, T) f32, old_logprobs (B, T) f32 or None, entropy_reg, ppo_clip): constants held by the
+    node.  `out`: a dict that receives 'logprobs' (B, T) and 'terms' (2 floats: policy, entropy)."""
+
+    @staticmethod
+    def _criterion_fwd(d, B, T, logits, rl, stats, tok_lp, scratch, loss, terms, st):
+        seq, reward, old, ent, clip = rl
+        N.check(N.lib.rfn_rl_logits_fwd(logits, d.V1, B, T, d.V1, seq.data_ptr(), seq.stride(0), reward.data_ptr(), reward.stride(0),
+                                        ent, N.ptr(old), 0 if old is None else old.stride(0), int(old is not None), clip,
+                                        stats.data_ptr(), tok_lp.data_ptr(), tok_lp.stride(0), scratch.data_ptr(), loss.data_ptr(), 0,
+                                        N.ptr(terms), st), 'rfn_rl_logits_fwd')
+
+    @staticmethod
+    def _decoder_fwd(d, B, T, n, table, comb, h0, c0, ids, ws, train, seed, st, what='rfn_decoder_logits_fwd'):
+        N.check(N.lib.rfn_decoder_logits_fwd(C.byref(d), B, T, table, comb.data_ptr(), h0.data_ptr(), c0.data_ptr(), ids.data_ptr(),
+                                             ids.stride(0), ws.data_ptr(), ws.numel(), int(train), seed, n, st), what)
+        return N.lib.rfn_decoder_logits_ex(C.byref(d), B, T, int(train), n, ws.data_ptr())
+
+    @staticmethod
+    def forward(ctx, model, save_bwd, drop, seed, ids, rl, n, out, comb, h0, c0, *params):
+        d = model._dims_for(drop)
+        B, T = ids.shape
+        dev = comb.device
+        comb, h0, c0, ids = comb.contiguous(), h0.contiguous(), c0.contiguous(), ids.contiguous()
+        table = model._param_table(params, model._decoder_slots)
+        train = bool(save_bwd)
+        ws = torch.empty(N.lib.rfn_decoder_ws_bytes_ex(C.byref(d), B, T, int(train), n), dtype=torch.uint8, device=dev)
+        st = N.stream_ptr()
+        logits = _DecoderRLFn._decoder_fwd(d, B, T, n, table, comb, h0, c0, ids, ws, train, seed, st)
+        stats = torch.empty(3 * T * B, device=dev)
+        tok_lp = torch.empty(B, T, device=dev)
+        terms = torch.empty(2, device=dev)
+        loss = torch.zeros(1, device=dev)
+        _DecoderRLFn._criterion_fwd(d, B, T, logits, rl, stats, tok_lp, torch.empty(3 * B * T, device=dev), loss, terms, st)
+        out['logprobs'], out['terms'] = tok_lp, terms
+        if train:
+            ctx.model, ctx.seed, ctx.B, ctx.T, ctx.drop, ctx.n = model, seed, B, T, drop, n
+            ctx.ids, ctx.rl, ctx.params, ctx.consumed = ids, rl, params, False
+            ctx.save_for_backward(comb, h0, c0, stats, ws)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        model, B, T, n = ctx.model, ctx.B, ctx.T, ctx.n
+        comb, h0, c0, stats, ws = ctx.saved_tensors
+        seq, reward, old, ent, clip = ctx.rl
+        d = model._dims_for(ctx.drop)
+        dev = comb.device
+        st = N.stream_ptr()
+        table = model._param_table(ctx.params, model._decoder_slots)
+        flats, by_slot, gtable = model._grad_buffers(['decoder'], dev)
+        if ctx.consumed:
+            # the first backward turned the logits into their gradient and the activations into theirs: a second backward over
+            # the same graph recomputes the pass first (same inputs, same dropout seed, the weights as they are now)
+            logits = _DecoderRLFn._decoder_fwd(d, B, T, n, table, comb, h0, c0, ctx.ids, ws, True, ctx.seed, st,
+                                               'rfn_decoder_logits_fwd (recompute)')
+            stats = torch.empty_like(stats)
+            _DecoderRLFn._criterion_fwd(d, B, T, logits, ctx.rl, stats, torch.empty(B, T, device=dev), torch.empty(B * T, device=dev),
+                                        torch.zeros(1, device=dev), None, st)
+        ctx.consumed = True
+        g = g.contiguous().float()
+        logits = N.lib.rfn_decoder_logits_ex(C.byref(d), B, T, 1, n, ws.data_ptr())
+        N.check(N.lib.rfn_rl_logits_bwd(logits, d.V1, B, T, d.V1, seq.data_ptr(), seq.stride(0), reward.data_ptr(), reward.stride(0),
+                                        ent, N.ptr(old), 0 if old is None else old.stride(0), int(old is not None), clip,
+                                        stats.data_ptr(), 1.0, g.data_ptr(), st), 'rfn_rl_logits_bwd')
+        d_comb, d_h0, d_c0 = torch.empty_like(comb), torch.empty_like(h0), torch.empty_like(c0)
+        N.check(N.lib.rfn_decoder_logits_bwd(C.byref(d), B, T, table, comb.data_ptr(), ctx.ids.data_ptr(), ctx.ids.stride(0),
+                                             d_comb.data_ptr(), d_h0.data_ptr(), d_c0.data_ptr(), gtable, ws.data_ptr(), ws.numel(),
+                                             ctx.seed, n, st), 'rfn_decoder_logits_bwd')
+        model._bucket_done('decoder', flats['decoder'])
+        return (None,) * 8 + (d_comb, d_h0, d_c0) + (None,) * len(ctx.params)
+
+
 class _HiddenFn(torch.autograd.Function):
     """Phase 2 without its output layer, for a model whose head is a mixture of softmaxes (rfn.h "mixture of softmaxes"):
     rfn_decoder_fwd_hidden -> the (S * B, R) time-major rows the logit layer would read (a copy: the head's node keeps them);
@@ -577,6 +656,7 @@ class RecurrentFusionModel(nn.Module):
         self._last_flat_grads = {}
         self._steps_cache = None
         self.last_distill = None         # forward_loss with a teacher: {'xe', 'kd'}, the two loss terms as 0-dim device tensors
+        self.last_rl = None              # rl_loss: {'logprobs' (rows, T), 'policy', 'entropy'} (device tensors)
         # set by graphed.GraphedTrainStep while it captures / warms up: run exactly this many decoder steps instead of
         # stopping at the first all-zero label column (the loader's masks are zero on the extra steps)
         self.fixed_decoder_steps = None
@@ -982,6 +1062,65 @@ class RecurrentFusionModel(nn.Module):
         heads = list(reason.unbind(0))
         return lang + _MLMFn.apply(float(reason_weight) / len(heads), top_words, *heads), heads
 
+    def rl_loss(self, fc_feats, att_feats, seq, reward, top_words, entropy_reg=0.0, reason_weight=1.0, n=1, old_logprobs=None,
+                ppo_clip=0.2, att_lens=None):
+        """The policy-gradient step's replay AND criterion in one call (INTEGRATION.md "Policy-gradient loss from the logits") ->
+        (loss, reason_pred): the value and the gradients, to rounding, of
+            seq_, lp, lp_all, reason_pred = model.sample_group(fc_feats, att_feats, n, {'force_ids': seq})
+            loss = rl_crit(lp, seq_, reward, lp_all, entropy_reg, reason_pred, top_words, reason_weight, old_logprobs, opt)
+        with `rl_crit` a ReviewNetRewardCriterion (train_rl.py:160-203, misc/utils.py:44-84), without logprobs_all (rows, T, V+1),
+        its gradient and the passes over them: the policy and entropy terms come straight from the logits and their backward
+        writes d logits in place (rfn_rl_logits_fwd / _bwd).  So captions from ANY decode can be trained on -- the fast no-grad
+        loops (sample with sample_n / top_k / top_p), a beam search's candidates, sample_distinct -- not only the differentiated
+        sampled pass.
+
+        seq (rows, T) int64, 1 <= T <= seq_length: captions as sample / sample_group / sample_distinct hand them out (zeros from
+        the END on), rows image-major, rows = images * n with features per image.  The decoder runs T steps, fed BOS and
+        seq[:, :T-1], scored against seq[:, :T]; nothing is read back, so a caller who wants the reference's early-exit trim passes
+        what sample returned.  reward (rows, T) or (rows, 1) f32.  PPO is on iff old_logprobs (rows, T) is given (ppo_clip as
+        opt.ppo_clip).  Stages I / II run once per image; dropout follows the module's mode with a fresh seed (the replay draws its
+        own masks, as the reference's PPO epochs do).  Feature tensors that require grad get their gradients; att_lens works.
+        `self.last_rl` = {'logprobs': (rows, T) the tokens' log-probs, detached (what a PPO loop keeps as sample_logprobs_old),
+        'policy', 'entropy': the two terms of the loss as 0-dim device tensors}."""
+        from .criteria import _MLMFn
+        self._mos_refuse('rl_loss', 'the policy-gradient kernels read the logit layer\'s rows')
+        if self.fixed_decoder_steps is not None or getattr(self, '_seed_dev', None) is not None:
+            raise N.RfnError('rl_loss: the model is owned by a running GraphedTrainStep; the RL step is not captured')
+        n = int(n)
+        if n < 1:
+            raise ValueError('rl_loss takes n >= 1 rows per image (got %d)' % n)
+        B = self._check_inputs(fc_feats, att_feats)
+        if not torch.is_tensor(seq) or seq.dim() != 2 or seq.size(0) != B * n or seq.dtype != torch.long:
+            raise N.RfnError('rl_loss: seq must be int64 (%d, T) for %d images and n = %d, got %s %s'
+                             % (B * n, B, n, getattr(seq, 'dtype', type(seq).__name__), tuple(getattr(seq, 'shape', ()))))
+        rows, T = seq.shape
+        if not 1 <= T <= self.seq_length:
+            raise N.RfnError('rl_loss: seq has T = %d columns, this model decodes 1 <= T <= seq_length = %d' % (T, self.seq_length))
+        if not torch.is_tensor(reward) or reward.dim() != 2 or reward.size(0) != rows or reward.size(1) not in (1, T):
+            raise N.RfnError('rl_loss: reward must be (%d, %d) or (%d, 1), got %s' % (rows, T, rows, tuple(getattr(reward, 'shape', ()))))
+        if old_logprobs is not None and (not torch.is_tensor(old_logprobs) or tuple(old_logprobs.shape) != (rows, T)):
+            raise N.RfnError('rl_loss: old_logprobs must be (%d, %d), got %s' % (rows, T, tuple(getattr(old_logprobs, 'shape', ()))))
+        if n > 1:
+            self._need_hoisted('rl_loss: n rows per image need')
+        train = bool(self.training)
+        seed = self._step_seed(train)
+        dev = fc_feats[0].device
+        comb, h, c, reason = self._prefix(fc_feats, att_feats, train, seed, att_lens)
+        if n > 1:      # the state fans out to the rows (autograd sums it back); the thought vectors stay per image
+            h, c = h.repeat_interleave(n, dim=0), c.repeat_interleave(n, dim=0)
+        seq = seq.to(dev).contiguous()
+        ids = torch.zeros(rows, T, dtype=torch.long, device=dev)      # column t = the token fed at step t; column 0 = BOS
+        ids[:, 1:] = seq[:, :T - 1]
+        reward = reward.detach().to(dev).float().expand(rows, T).contiguous()
+        old = None if old_logprobs is None else old_logprobs.detach().to(dev).float().contiguous()
+        out = {}
+        params = self._params_of(self._decoder_slots)
+        lang = _DecoderRLFn.apply(self, torch.is_grad_enabled(), train, seed, ids, (seq, reward, old, float(entropy_reg), float(ppo_clip)),
+                                  n, out, comb, h, c, *params)
+        self.last_rl = {'logprobs': out['logprobs'], 'policy': out['terms'][0], 'entropy': out['terms'][1]}
+        heads = list(reason.unbind(0))
+        return lang + _MLMFn.apply(float(reason_weight) / len(heads), top_words, *heads), heads
+
     def _decoder_steps(self, seq):
         """Number of decoder steps: the reference breaks at the first all-zero column i >= 1 (:274).  The
         answer for a given (tensor, version) is cached, so a caller that reuses one label tensor pays the
@@ -1222,7 +1361,8 @@ class RecurrentFusionModel(nn.Module):
         call) and the decoding constraints 'block_ngram', 'banned_ids', 'bad_endings' -- the weights are then relative: the
         restricted distribution is not renormalised.  Every other key raises ValueError by name.  Runs under no_grad only; dropout
         follows the module's mode, as in sample_beam.  n <= 32, seq_length <= 64; needs the hoisted decoder cell.  EnsembleDecoder
-        has no such method, and no gradient estimator is built on the weights."""
+        has no such method.  To train on the set: rewards.get_self_critical_reward_distinct turns the weights into the normalised
+        importance-weighted policy-gradient coefficients (with their built-in baseline) and rl_loss(..., n=n) replays the rows."""
         self._mos_refuse('sample_distinct', 'stochastic beam search is a device loop with the logit layer inside')
         B, S, V1 = self._check_inputs(fc_feats, att_feats), self.seq_length, self.vocab_size + 1
         sb = _Stochastic.parse(opt, n, S)

@@ -481,6 +481,55 @@ def scst_group_reward(scorer, gen_result, gts, n_refs, n, cider_weight=1.0, base
     return out
 
 
+_DISTINCT_BASELINES = {'none': 0, 'weighted': 1}
+
+
+def _distinct_weight(weight, rows, n, dev):
+    """`weight` of a distinct-sample set -> a contiguous (rows,) float64 device tensor: RecurrentFusionModel.stochastic_beams
+    ['weight'] (B, n), or the dict itself."""
+    if isinstance(weight, dict):
+        weight = weight['weight']
+    if not torch.is_tensor(weight) or weight.numel() != rows:
+        raise ValueError('weight needs one entry per row (%d = images * %d), got %s' % (rows, n, tuple(getattr(weight, 'shape', ()))))
+    return weight.to(dev, torch.float64).contiguous().view(rows)
+
+
+def scst_distinct_reward(scorer, cands_rows, weight, gts, n_refs, n, cider_weight=1.0, baseline='weighted', out64=None,
+                         bleu_scorer=None, bleu4_weight=0.0):
+    """The reward that makes a sample_distinct set trainable (rfn.h rfn_scst_reward_distinct; Kool, van Hoof and Welling 2019):
+    cands_rows (B*n, T) are the n distinct captions per image, image-major, `weight` their importance weights
+    (model.stochastic_beams['weight'], (B, n) float64, or that dict).  With q_j = w_j / sum_i w_i over the image's rows with
+    w > 0 and s the mixed score: baseline 'weighted': reward = n * q_j * (s_j - sum_i q_i * s_i); 'none': n * q_j * s_j.  Dead
+    rows and the threshold row (w = 0) get exactly 0.  Fed to rl_loss(..., n=n) this is the normalised importance-weighted
+    policy gradient.  The weighted baseline needs n >= 3: with n = 2 the one weighted row's coefficient is identically zero.
+    Weights, bleu_scorer and out64 as scst_group_reward; one launch behind the scoring, nothing synchronises."""
+    if baseline not in _DISTINCT_BASELINES:
+        raise ValueError("baseline is 'weighted' or 'none', got %r" % (baseline,))
+    n = int(n)
+    rows, T = cands_rows.shape
+    if n < 1 or rows % n:
+        raise ValueError('%d rows are not n = %d captions per image' % (rows, n))
+    if baseline == 'weighted' and n < 3:
+        raise ValueError("the weighted baseline needs n >= 3 captions per image: the last live row is the threshold and weighs 0, so "
+                         "n = 2 leaves one weighted sample whose coefficient is identically zero (baseline='none' takes any n)")
+    if gts.shape[0] * n != rows:
+        raise ValueError('%d rows of %d captions per image need %d images of references, got %d' % (rows, n, rows // n, gts.shape[0]))
+    if scorer is None and bleu_scorer is None:
+        raise ValueError('scst_distinct_reward needs a CIDEr-D scorer, a BLEU-D scorer or both')
+    dev = cands_rows.device
+    w = _distinct_weight(weight, rows, n, dev)
+    res = cands_rows.to(torch.int64)
+    row_img = _group_row_img(rows, n, dev)
+    scores = None if scorer is None else scorer.score_ids(res, row_img, gts, n_refs)
+    bleu = None if bleu_scorer is None else bleu_scorer.score_ids(res, row_img, gts, n_refs)
+    out = torch.empty(rows, T, dtype=torch.float32, device=dev)
+    N.check(N.lib.rfn_scst_reward_distinct(N.ptr(scores), C.c_double(cider_weight), N.ptr(bleu),
+                                           C.c_double(0.0 if bleu is None else bleu4_weight), w.data_ptr(), rows, n, T,
+                                           _DISTINCT_BASELINES[baseline], out.data_ptr(), N.ptr(out64), N.stream_ptr()),
+            'rfn_scst_reward_distinct')
+    return out
+
+
 def consensus(scorer, cands, n_cand=None, weights=None, end_token=True, want_pairs=False):
     """Consensus (minimum-Bayes-risk) reranking of decoded candidates: CiderD.consensus on `scorer` (table or corpus df).  Any
     other scorer raises NotImplementedError (only the CIDEr-D utility is on the device)."""
@@ -617,4 +666,26 @@ def get_self_critical_reward_group(data, gen_result, n, opt, device=False, score
         return scst_group_reward(scorer, gen_result, gts, n_refs, n, w, how, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
     out64 = torch.empty(rows, T, dtype=torch.float64, device=gen_result.device)
     scst_group_reward(scorer, gen_result, gts, n_refs, n, w, how, out64=out64, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
+    return out64.cpu().numpy()
+
+
+def get_self_critical_reward_distinct(data, gen_result, stochastic_beams, opt, device=False, scorer=None, bleu_scorer=None):
+    """The reward of a step trained on RecurrentFusionModel.sample_distinct's set: gen_result (B*n, T) are the n distinct captions
+    per image, stochastic_beams the model's `stochastic_beams` (its 'weight' is (B, n)), data['gts'] the B images' references.
+    With opt.use_baseline (the default) the estimator's built-in weighted baseline is used (n >= 3), with opt.use_baseline = 0
+    none.  Weights of the scores as get_self_critical_reward_group.  -> numpy (B*n, T) float64, or the device (B*n, T) float32
+    tensor with device=True."""
+    scorer, bleu_scorer, w, w_b, base = _reward_terms(opt, scorer, bleu_scorer)
+    rows, T = gen_result.shape
+    weight = stochastic_beams['weight'] if isinstance(stochastic_beams, dict) else stochastic_beams
+    if weight.dim() != 2 or weight.size(0) != len(data['gts']) or weight.numel() != rows:
+        raise ValueError('%d rows need stochastic_beams[\'weight\'] of shape (%d images, n) with images * n = rows, got %s'
+                         % (rows, len(data['gts']), tuple(weight.shape)))
+    n = weight.size(1)
+    gts, n_refs = pad_gts(data['gts'], gen_result.device)
+    how = 'weighted' if base else 'none'
+    if device:
+        return scst_distinct_reward(scorer, gen_result, weight, gts, n_refs, n, w, how, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
+    out64 = torch.empty(rows, T, dtype=torch.float64, device=gen_result.device)
+    scst_distinct_reward(scorer, gen_result, weight, gts, n_refs, n, w, how, out64=out64, bleu_scorer=bleu_scorer, bleu4_weight=w_b)
     return out64.cpu().numpy()
