@@ -1790,6 +1790,64 @@ int rfn_decoder_bwd_hidden(const rfn_dims* d, int B, int S, const float* const* 
                            float* d_h0, float* d_c0, float* const* grads, void* ws, size_t ws_bytes, uint64_t seed,
                            void* stream);
 
+/* ---- attention maps (where the model looked when it wrote a word; the reference never returns its attention weights) ------------
+ * Every forward kernel writes its softmax weights because the backward needs them; these entry points hand them out and compose
+ * the three levels into one word-to-region map per (caption row, encoder) (csrc/rfn_attnmap.hip).  Notation: T1, T2, M, L_i of
+ * rfn_dims; rows = B * n caption rows, image-major, image k = row / n; S decoder steps.
+ *
+ * Accessors: addresses inside the workspace of a FINISHED forward pass, valid until the next call on that workspace.
+ *   rfn_prefix_alpha1(d, B, train, i, ws): a1_i[t1, b, l], (T1, B, L_i) contiguous -- stage I, encoder i over its regions; under
+ *     ragged maps (rfn_prefix_fwd_ex with att_len) columns l >= the image's length hold exact zeros.
+ *   rfn_prefix_alpha2(d, B, train, ws):    a2[t2, i, b, t1], (T2, M, B, T1) contiguous -- stage II over encoder i's thought vectors.
+ *   rfn_decoder_alpha(d, B, S, train, n, ws): aD[s, row, t2], (S, B, T2) contiguous, B counting rows -- the decoder over the fused
+ *     thought vectors, from rfn_decoder_fwd[_ex] / _fwd_hidden / _logits_fwd / rfn_decoder_score.
+ *   (d, B, S, train, n) are those of the pass.  Workspaces of BOTH sizes keep every step's weights at the same offsets, and every
+ *   form of the passes (persistent chains, the un-hoisted decoder cell) writes them there, so an inference-size pass (train = 0)
+ *   suffices; a caller that wants inference weights passes dims whose dropout probabilities are 0.  NULL for bad dims, B or S < 1,
+ *   an encoder outside [0, M), n that does not divide B, or ws == NULL.  No existing entry point changed for these.
+ *
+ * rfn_attn_rollout, one launch per encoder: for every row r, k = r / n, every step s < S and every region l < L
+ *   G[r, s, l] = sum_{t2 < T2} aD[s, r, t2] * ( sum_{t1 < T1} a2[t2, k, t1] * a1[t1, k, l] )
+ *   in exactly this nesting, both sums ascending from 0.f (products may be contracted into the adds); no atomics: two runs give
+ *   the same bits.  Rows of row-stochastic inputs give a row-stochastic G.  This composes attention WEIGHTS only; it is not a
+ *   gradient attribution (the LSTM states carry information too).
+ *   aD at aD[s * d_ss + r * d_sr + t2]; a2 (this encoder's slab) at a2[t2 * a2_st + k * a2_sb + t1] -- for the accessor's layout
+ *   a2 = rfn_prefix_alpha2(..) + i * B * T1, a2_st = M * B * T1, a2_sb = T1; a1 at a1[t1 * a1_st + k * a1_sb + l]; out at
+ *   out[r * o_sr + s * o_ss + l], unit stride in l.
+ *   len (rows,) int32 or NULL (every step live), clamped to [0, S]: steps s >= len[r] are written as exact zeros, and a row with
+ *   len 0 loads nothing.  att_len (rows / n,) int32 or NULL, clamped to [1, L] as the ragged forward clamps it: columns
+ *   l >= att_len[k] are written as exact zeros and a1 is not loaded there.
+ *   One wave per (row, tile of 256 columns): 16 B per lane where L % 4 == 0, a1 and out are 16-B aligned and a1_st, a1_sb, o_sr,
+ *   o_ss are multiples of 4; element-wise with 64-column tiles otherwise (same sums, same bits).  The row's aD (S x T2), the
+ *   image's a2 (T2 x T1) and the inner sums of the tile (T2 x tile) are staged in LDS; the a1 rows of a tile are read once.
+ *   LDS limit: (S * T2 + T2 * T1 + T2 * tile) floats (the first two rounded up to 4) <= 64 KiB.  A map that qualifies for the
+ *   16-B form but whose 256-column tile does not fit takes the 64-column element-wise form; what does not fit that either is
+ *   RFN_ERR_UNSUPPORTED -- there is no kernel without the LDS stage.
+ *   Checks, in this order: RFN_ERR_SHAPE for rows, n, S, T1, T2 or L < 1, rows % n != 0, o_sr or o_ss < L, d_sr < T2,
+ *   a2_sb < T1, a1_sb or a1_st < L; RFN_ERR_ARG for aD, a2, a1 or out NULL; then RFN_ERR_UNSUPPORTED.
+ *
+ * rfn_attn_map_stats, one launch per encoder over G (G[r * g_sr + s * g_ss + l]); per (row, step), at [r * S + s]:
+ *   peak int32: the first argmax over l;  entropy f32: -sum_l G log G in nats, 0 log 0 = 0;  mass f32: the sum of G[r, s, l] over the
+ *   l with region_mask[r * m_sr + s * m_ss + l] != 0 (uint8) -- written only when a mask is given (mass may then not be NULL).
+ *   Dead steps (s >= len[r]) get peak = -1, entropy = 0, mass = 0 and their map row is not read.  One wave per (row, step), lane-
+ *   strided partial sums then xor shuffles: a fixed order.  RFN_ERR_SHAPE: rows, S or L < 1, g_sr or g_ss < L, with a mask m_sr or
+ *   m_ss < L.  RFN_ERR_ARG: G, peak or entropy NULL, a mask without mass.
+ *
+ * rfn_attn_decoder_copy: out[r * o_sr + s * o_ss + t2] = s < len[r] ? aD[s * d_ss + r * d_sr + t2] : 0 -- the decoder weights
+ *   caption-major with the rollout's zeroing; dead steps are not loaded.  RFN_ERR_SHAPE: rows, S or T2 < 1, d_sr, o_sr or o_ss < T2.
+ *   RFN_ERR_ARG: aD or out NULL.
+ * No allocation, no synchronisation (capturable in a graph). */
+float* rfn_prefix_alpha1(const rfn_dims* d, int B, int train, int enc, void* ws);
+float* rfn_prefix_alpha2(const rfn_dims* d, int B, int train, void* ws);
+float* rfn_decoder_alpha(const rfn_dims* d, int B, int S, int train, int rows_per_image, void* ws);
+int rfn_attn_rollout(const float* aD, int64_t d_ss, int64_t d_sr, const float* a2, int64_t a2_st, int64_t a2_sb, const float* a1,
+                     int64_t a1_st, int64_t a1_sb, const int32_t* len, const int32_t* att_len, int rows, int n, int S, int T1, int T2,
+                     int L, float* out, int64_t o_sr, int64_t o_ss, void* stream);
+int rfn_attn_map_stats(const float* G, int64_t g_sr, int64_t g_ss, const int32_t* len, const uint8_t* region_mask, int64_t m_sr,
+                       int64_t m_ss, int rows, int S, int L, int32_t* peak, float* entropy, float* mass, void* stream);
+int rfn_attn_decoder_copy(const float* aD, int64_t d_ss, int64_t d_sr, const int32_t* len, int rows, int S, int T2, float* out,
+                          int64_t o_sr, int64_t o_ss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

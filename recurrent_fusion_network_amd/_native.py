@@ -318,6 +318,13 @@ def _load():
         'rfn_decoder_logits_ex': (P, [DP, I, I, I, I, P]),
         'rfn_decoder_logits_bwd': (C.c_int, [DP, I, I, P, P, P, L, P, P, P, P, P, SZ, U64, I, P]),
         'rfn_scst_reward_distinct': (C.c_int, [P, C.c_double, P, C.c_double, P, I, I, I, I, P, P, P]),
+        # attention maps (rfn.h): the weights a finished pass left in its workspace, their rollout, its statistics
+        'rfn_prefix_alpha1': (P, [DP, I, I, I, P]),
+        'rfn_prefix_alpha2': (P, [DP, I, I, P]),
+        'rfn_decoder_alpha': (P, [DP, I, I, I, I, P]),
+        'rfn_attn_rollout': (C.c_int, [P, L, L, P, L, L, P, L, L, P, P, I, I, I, I, I, I, P, L, L, P]),
+        'rfn_attn_map_stats': (C.c_int, [P, L, L, P, P, L, L, I, I, I, P, P, P, P]),
+        'rfn_attn_decoder_copy': (C.c_int, [P, L, L, P, I, I, I, P, L, L, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol

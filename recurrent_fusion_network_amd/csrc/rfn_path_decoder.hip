@@ -245,6 +245,11 @@ extern "C" float* rfn_decoder_hidden(const rfn_dims* d, int B, int S, int train,
     if (check_dims(d) != RFN_OK || B < 1 || S < 1 || !ws) return nullptr;
     return (float*)ws + decoder_layout(d, B, S, train).hd + (size_t)B * d->R;
 }
+// rfn.h "attention maps": the (S, B, T2) attention weights every form of the teacher-forced pass leaves in its workspace
+extern "C" float* rfn_decoder_alpha(const rfn_dims* d, int B, int S, int train, int rows_per_image, void* ws) {
+    if (check_dims(d) != RFN_OK || B < 1 || S < 1 || rows_per_image < 1 || B % rows_per_image != 0 || !ws) return nullptr;
+    return (float*)ws + decoder_layout(d, B, S, train, rows_per_image).ald;
+}
 
 extern "C" float* rfn_decoder_logits(const rfn_dims* d, int B, int S, int train, void* ws) {
     if (check_dims(d) != RFN_OK || B < 1 || S < 1 || !ws) return nullptr;

@@ -9,6 +9,15 @@ extern "C" size_t rfn_prefix_ws_bytes(const rfn_dims* d, int B, int train) {
     if (check_dims(d) != RFN_OK || B < 1) return 0;
     return prefix_layout(d, B, train).total * sizeof(float);
 }
+// rfn.h "attention maps": where a finished forward pass left its attention weights (every form of the pass writes them there)
+extern "C" float* rfn_prefix_alpha1(const rfn_dims* d, int B, int train, int enc, void* ws) {
+    if (check_dims(d) != RFN_OK || B < 1 || enc < 0 || enc >= d->M || !ws) return nullptr;
+    return (float*)ws + prefix_layout(d, B, train).al1[enc];
+}
+extern "C" float* rfn_prefix_alpha2(const rfn_dims* d, int B, int train, void* ws) {
+    if (check_dims(d) != RFN_OK || B < 1 || !ws) return nullptr;
+    return (float*)ws + prefix_layout(d, B, train).al2;
+}
 
 namespace {
 // Stage-I attention of step t, all M encoders: ONE set of operand tables for every form of the forward launch (grouped, het,

@@ -1514,6 +1514,27 @@ class RecurrentFusionModel(nn.Module):
                                              int(so.include_end), sl(bufs.cap_lp), sl(bufs.cap_len), st), 'rfn_score_captions')
         return bufs.result()
 
+    def attention(self, fc_feats, att_feats, seq, opt={}, att_lens=None):
+        """Where the model looked when it wrote each word of the captions it is GIVEN (rfn.h "attention maps", INTEGRATION.md
+        "Attention maps"; the reference never returns its attention weights) -> a dict of device tensors, caption rows image-major:
+            'encoder'  list of M (B, T1, L_i)      stage I: encoder i's review steps over its regions
+            'fusion'   (B, T2, M, T1)              stage II: each fusion step over encoder i's thought vectors
+            'decoder'  (rows, steps, T2)           the decoder over the fused thought vectors, zeros at dead steps
+            'rollout'  list of M (rows, steps, L_i)  G_i[r, s, l] = sum_t2 decoder[r, s, t2] * (sum_t1 fusion[k, t2, i, t1] *
+                                                   encoder_i[k, t1, l]), k = r // n: the three levels composed (rfn_attn_rollout)
+            'length'   (rows,) int32               live steps per row: the caption's words and its END, at most steps
+            'peak', 'entropy', 'mass'  lists of M (rows, steps), when opt['outputs'] names them: the first argmax region (-1 at
+                                                   dead steps), the map's entropy in nats, and the weight inside
+                                                   opt['region_mask'] (a list of M (rows, steps, L_i) bool / uint8 device tensors,
+                                                   None entries allowed -- their 'mass' entry is None)
+        seq, opt['n'] and steps = min(T, seq_length) + 1 exactly as score() takes them; opt['max_rows'] bounds the rows of one
+        decoder call.  Always runs under no_grad with dropout off.  Stages I / II run once per image; the decoder runs the pass
+        that stops before the output layer (no logits: a use_mos model works unchanged).  Rollout composes attention weights only
+        -- it is not a gradient attribution (saliency() is).  Refused by name before any launch: path_flags that select another
+        decoder form than the hoisted cell, a model owned by a running GraphedTrainStep, unknown opt keys, a bad region_mask."""
+        from .attention_maps import attention
+        return attention(self, fc_feats, att_feats, seq, opt, att_lens)
+
     def sample_beam(self, fc_feats, att_feats, opt={}, att_lens=None):
         """misc/RecurrentFusionModel.py:352-543, batched and device-resident.
 
